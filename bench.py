@@ -7,7 +7,14 @@ already resident in HBM: the ordered weighted-sum reduction of D client buckets
 libfa.so's C ABI (fa_reduce_part on the context's own slots).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload northstar|c2|c3|c4|c5|c5r]
-                  [--scaling strong|weak] [--layout range|rs|chain] [--no-cpu-baseline] [--no-secondary]
+                  [--scaling strong|weak] [--layout range|rs|chain] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-secondary] [--no-live-pmc]]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step and the
+launch-stream roofline figures the timed steps give for free).  `--full` adds every other leg: the live PMC
+traffic passes, the CPU baselines, the parity check of the timed result against the oracle, the per-launch
+event times and read-only ceilings, and the secondary workloads / rounds / end-to-end / multi-GPU legs.
+`--dump-outputs DIR` writes the result of the last timed step as DIR/<name>.npy (float32) after the steps.
 
 One process per GPU.  `--gpus N` with N > 1 starts its own N rank processes
 (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in their env) unless a launcher such as
@@ -901,6 +908,29 @@ def device_to_host(ptr, count, dtype):
     return out
 
 
+DUMP_MAX_BYTES = 32 << 20  # --dump-outputs: the files of one run together (all ranks)
+DUMP_SAMPLE_SEED = 0xD05EED
+
+
+def dump_array(dirname, name, arr, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the host array `arr` (a bf16 result as its uint16 bits) as <dirname>/<name>.npy in
+    float32.  An array past `max_bytes` is written as a fixed sample of itself: its first and last element
+    and the elements at indices drawn from default_rng(DUMP_SAMPLE_SEED), in index order -- the same indices
+    in every run on an array of that length, so two runs' files compare element for element."""
+    import numpy as np
+    a = np.asarray(arr).reshape(-1)
+    k = max(2, (max_bytes - 4096) // 4)  # 4096: room for the .npy headers
+    if a.size > k:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        a = a[np.unique(np.concatenate([[0, a.size - 1], rng.integers(0, a.size, size=k - 2)]))]
+    if a.dtype == np.uint16:  # bf16 bits: the upper half of the fp32 word
+        a = (a.astype(np.uint32) << 16).view(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, name + ".npy")
+    np.save(path, np.ascontiguousarray(a, np.float32))
+    return path
+
+
 def _read_rate(torch, setup, stream, launch, reps, passes=1):
     """GB/s of one read-only launch form over the setup's client slots: one launch per range piece (a bucket
     set held in pieces, e.g. C5 on one GPU, is reduced one launch per piece too), bytes of all pieces / the
@@ -977,16 +1007,19 @@ def settle(freed_bytes):
     time.sleep(min(8.0, freed_bytes / 30e9))
 
 
-def timed_loop(torch, setup, steps, warmup, stream, dist, barrier, per_launch=10):
+def timed_loop(torch, setup, steps, warmup, stream, dist, barrier, per_launch=10, after_timed=None):
     """`steps` steps back to back, bracketed by barrier + synchronize: returns (wall seconds, region_ms, kern_ms).
 
     The timed region holds nothing but the steps: one HIP event pair on the launch stream brackets all of
     them (region_ms = their device time / steps -- the roofline's average launch duration), with no event
     between steps (an event pair per step added 7-12 us of wall time per step, gpurun_out r02s71).
     kern_ms: per-launch event pairs from a separate loop of `per_launch` steps after the timed region
-    (kernel_ms_min / _median)."""
+    (kernel_ms_min / _median; none with per_launch=0).  `after_timed` runs once the timed region has closed,
+    before those further launches (the output dump of the last timed step)."""
     if not hasattr(stream, "cuda_stream"):  # Event.record on a non-stream crashes inside the HIP runtime
         raise TypeError("timed_loop needs a torch.cuda.Stream, got %r" % (stream,))
+    if after_timed is None:
+        after_timed = lambda: None  # noqa: E731
     for i in range(warmup):
         setup.launch(i, stream)
     torch.cuda.synchronize()
@@ -1003,6 +1036,7 @@ def timed_loop(torch, setup, steps, warmup, stream, dist, barrier, per_launch=10
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     region_ms = a.elapsed_time(b) / steps
+    after_timed()
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_launch)]
     for i, (x, y) in enumerate(evs):
         x.record(stream)
@@ -1282,10 +1316,17 @@ def main():
     ap.add_argument("--layout", default="range", choices=["range", "rs", "chain"])
     ap.add_argument("--chunks", type=int, default=16,
                     help="rs / chain layouts: chunks (reduce of chunk c+1 overlaps the exchange of chunk c)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps also run every other leg: live PMC traffic passes, CPU baselines, "
+                         "parity against the oracle, per-launch events and read ceilings, the secondary legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the result of the last one as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of a result past %d MiB)" % (DUMP_MAX_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave the secondary legs out")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="take roofline.traffic from profiles/pmc_traffic.json instead of two PMC passes run now")
+                    help="with --full: take roofline.traffic from profiles/pmc_traffic.json instead of two PMC "
+                         "passes run now")
     ap.add_argument("--dist-backend", default="auto",
                     help="auto (nccl = RCCL over xGMI when every rank has its own GPU, else gloo), nccl or gloo")
     ap.add_argument("--tune", default="", help="block,max_blocks,unroll,load_policy,store_policy (fa_tuning)")
@@ -1311,6 +1352,8 @@ def main():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.ctx_multi:
         return ctx_multi(args)
+    if not args.full:  # a plain run: set up, warm up, the timed steps, the line
+        args.no_cpu_baseline = args.no_secondary = args.no_live_pmc = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -1398,9 +1441,17 @@ def main():
         layout_desc = layout_desc_of(args.layout, c1 - c0, world, args.chunks)
     torch.cuda.synchronize()
 
+    def dump(arr):  # --dump-outputs: what the last timed step computed (this rank's part of it)
+        if args.dump_outputs:
+            progress("wrote " + dump_array(args.dump_outputs, "out" if world == 1 else "out_rank%d" % rank, arr,
+                                           DUMP_MAX_BYTES // world))
+
     # the dominant kernel alone (roofline), HIP events on its stream
     timeouts0 = fa.phased_timeouts(device)
-    wall_k, kavg, kern_ms = timed_loop(torch, setup, args.steps, args.warmup, stream, dist, barrier)
+    last_set = (args.warmup + args.steps - 1) % setup.nsets  # the input set of the last timed step
+    wall_k, kavg, kern_ms = timed_loop(
+        torch, setup, args.steps, args.warmup, stream, dist, barrier, per_launch=10 if args.full else 0,
+        after_timed=(lambda: dump(setup.agg.copy_output(last_set))) if args.layout == "range" else None)
     timeouts = fa.phased_timeouts(device) - timeouts0  # > 0: the persistent grid was not co-resident
     if args.layout == "range":
         wall = wall_k
@@ -1414,21 +1465,23 @@ def main():
         finally:
             fa.set_tuning(walk=walk0)
         timeouts += fa.phased_timeouts(device) - timeouts0 - timeouts
+        dump(res.float().cpu().numpy())
     wall = max_over_ranks(wall)
-    # parity of what was timed, read back and checked now that the timed region is closed
-    if args.layout == "range":
-        par = parity_guarded(lambda: setup.parity(0))
-    else:
-        par = parity_guarded(lambda: client_sharded_parity(shard, setup, args.layout, res, n, world, rank,
-                                                           args.chunks, D if strong else D * world))
-        res = None
-    par = parity_over_ranks(torch, dist, world, backend, par)
+    # --full: parity of what was timed, read back and checked now that the timed region is closed
+    par = None
+    if args.full:
+        if args.layout == "range":
+            par = parity_guarded(lambda: setup.parity(0))
+        else:
+            par = parity_guarded(lambda: client_sharded_parity(shard, setup, args.layout, res, n, world, rank,
+                                                               args.chunks, D if strong else D * world))
+        par = parity_over_ranks(torch, dist, world, backend, par)
+    res = None
 
     achieved = setup.algo_bytes() / (kavg * 1e-3) / 1e9
-    read_peak = read_stream_peak(fa, torch, setup, stream) if args.layout == "range" and not under_profiler() \
-        else None
-    read_ind = read_plain_peak(fa, torch, setup, stream) if args.layout == "range" and not under_profiler() \
-        else None
+    ceilings = args.full and args.layout == "range" and not under_profiler()  # read-only launches of their own
+    read_peak = read_stream_peak(fa, torch, setup, stream) if ceilings else None
+    read_ind = read_plain_peak(fa, torch, setup, stream) if ceilings else None
     # ranks sharing one GPU (rehearsal) run the one-shot walk, so no committed profile of the phased kernel
     # describes their launches: no traffic then
     committed = (None, None) if shared_gpus else traffic_from_profile(args.workload, world,
@@ -1443,6 +1496,7 @@ def main():
         "warmup": args.warmup,
         "ms_per_step": round(wall / args.steps * 1e3, 4),
         "higher_is_better": True,
+        "full": args.full,
         "scaling": args.scaling,
         "vs_baseline": None,
         "dtype": in_dt,
@@ -1462,8 +1516,9 @@ def main():
                      "algorithmic_bytes_per_launch": setup.algo_bytes(),
                      "kernel_ms_avg": round(kavg, 4),
                      "kernel_ms_avg_source": "HIP events on the launch stream bracketing the %d timed steps" % args.steps,
-                     "kernel_ms_min": round(min(kern_ms), 4), "kernel_ms_median": round(statistics.median(kern_ms), 4),
-                     "kernel_ms_per_launch_events_avg": round(statistics.mean(kern_ms), 4),
+                     "kernel_ms_min": round(min(kern_ms), 4) if kern_ms else None,
+                     "kernel_ms_median": round(statistics.median(kern_ms), 4) if kern_ms else None,
+                     "kernel_ms_per_launch_events_avg": round(statistics.mean(kern_ms), 4) if kern_ms else None,
                      "kernel": "rank %d's launch (%s)" % (rank, "its range of every bucket" if args.layout == "range"
                                                          else "its clients' local reduction"),
                      "phased_meeting_timeouts": int(max_over_ranks(timeouts)),

@@ -17,8 +17,9 @@ import pytest
 
 from conftest import ROOT
 
+sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
-BENCH = os.path.join(ROOT, "bench.py")
+BENCH =os.path.join(ROOT, "bench.py")
 
 
 def run_bench(args, env=None, timeout=240, tmp=None):
@@ -49,8 +50,8 @@ PIECES = ["--piece-split-kib", "-1", "--piece-span-kib", str(256 << 10)]  # ns_w
 
 @pytest.mark.parametrize("layout", ["range", "rs"])
 def test_pieced_workload_prints_its_line(fa, torch_gpu, layout):
-    line = run_bench(["--workload", "ns_w8", "--layout", layout, "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                      "--no-secondary", "--no-live-pmc"] + PIECES)
+    line = run_bench(["--workload", "ns_w8", "--layout", layout, "--steps", "3", "--warmup", "1", "--full",
+                      "--no-cpu-baseline", "--no-secondary", "--no-live-pmc"] + PIECES)
     ok(line["parity"])
     assert line["value"] > 0 and line["roofline"]["phased_meeting_timeouts"] == 0
     if layout == "range":
@@ -62,11 +63,36 @@ def test_pieced_workload_prints_its_line(fa, torch_gpu, layout):
 def test_read_stream_peak_of_bf16_and_rotated_workloads(fa, torch_gpu, workload):
     """The read-only rate beside a config's kernel: a bf16 workload (C3) is read as the fp32 words its bytes
     make, and a workload whose input set fits the MALL (C2, 3 sets rotated) is read set by set."""
-    line = run_bench(["--workload", workload, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-secondary",
-                      "--no-live-pmc"])
+    line = run_bench(["--workload", workload, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                      "--no-secondary", "--no-live-pmc"])
     ok(line["parity"])
     rf = line["roofline"]
     assert rf["read_stream_peak"] > 1000 and 0.5 < rf["frac_of_read_stream"] < 1.2, rf
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_result(fa, torch_gpu, O, tmp_path):
+    """A run without --full: the line with ms_per_step over exactly --steps steps and no other leg (no parity,
+    no CPU baseline, no secondary, no per-launch events or read ceilings), and --dump-outputs writes the last
+    timed step's result -- C2 rotates 3 input sets; step warmup + steps - 1 = 4 reads set 1 -- in float32:
+    past the size bound, so the fixed sample, bit-exact against the oracle's chain at the sampled indices."""
+    import numpy as np
+    import bench
+    line = run_bench(["--gpus", "1", "--workload", "c2", "--steps", "3", "--warmup", "2",
+                      "--dump-outputs", str(tmp_path)])
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 2
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "GiB/s" and line["dtype"] == "f32"
+    assert line["parity"] is None and line["cpu_baseline"] is None and "secondary" not in line
+    rf = line["roofline"]
+    assert rf["kernel_ms_avg"] > 0 and rf["kernel_ms_min"] is None and rf["read_stream_peak"] is None
+    assert os.listdir(tmp_path) == ["out.npy"]
+    got = np.load(tmp_path / "out.npy")
+    D, n = bench.WORKLOADS["c2"][:2]
+    assert got.dtype == np.float32 and got.nbytes <= bench.DUMP_MAX_BYTES < n * 4
+    idx = np.unique(np.concatenate([[0, n - 1], np.random.default_rng(bench.DUMP_SAMPLE_SEED).integers(
+        0, n, size=(bench.DUMP_MAX_BYTES - 4096) // 4 - 2)]))  # dump_array's sample of an array of n elements
+    assert idx.size == got.size
+    ref, _ = O.sampled_chain(0x5EED + 1, bench.Setup._weights(D), idx[::64].astype(np.uint64), None, False)
+    assert np.array_equal(got[::64].view(np.uint32), ref.view(np.uint32))
 
 
 @pytest.mark.parametrize("layout", ["range", "rs"])
@@ -91,8 +117,8 @@ def test_ctx_multi_host_inclusive_parity(fa, torch_gpu):
 def test_two_rank_rehearsal_parity_everywhere(fa, torch_gpu):
     """The driver's N > 1 launch rehearsed on one GPU (bench.py spawns 2 ranks, gloo): the main range line
     and the weak-range, rs and chain secondaries each carry a parity object summed over both ranks."""
-    line = run_bench(["--gpus", "2", "--workload", "ns_w8", "--steps", "3", "--warmup", "1", "--no-live-pmc"],
-                     timeout=300)
+    line = run_bench(["--gpus", "2", "--workload", "ns_w8", "--steps", "3", "--warmup", "1", "--full",
+                      "--no-live-pmc"], timeout=300)
     assert line["n_gpus"] == 2
     ok(line["parity"], 2 * 1024)
     assert line["parity"]["ranks"] == 2

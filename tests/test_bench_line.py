@@ -168,6 +168,25 @@ def test_round6_full_record_compacts_to_its_printed_line():
     assert "frac_copy_ind" in got["secondary"]["sync_c2"] and "e2e_fedavg_tail_ms" in got["secondary"]["round_c2"]
 
 
+def test_dump_array_writes_float32_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: a small result whole, a bf16 result (uint16 bits) as the fp32 values it holds, and a
+    result past the bound as the same ordered sample in every run, both ends included, within the bound."""
+    import numpy as np
+    import bench
+    a = np.arange(1000, dtype=np.float32) * 0.5
+    assert np.array_equal(np.load(bench.dump_array(str(tmp_path), "small", a)), a)
+    bits = np.array([0x3F80, 0xC000, 0x0000, 0x7F80], np.uint16)  # 1, -2, 0, inf
+    got = np.load(bench.dump_array(str(tmp_path / "sub"), "bf", bits))
+    assert got.dtype == np.float32 and np.array_equal(got, np.array([1.0, -2.0, 0.0, np.inf], np.float32))
+    big = np.arange(100_000, dtype=np.float32)
+    p1 = bench.dump_array(str(tmp_path), "big1", big, max_bytes=4096 + 4 * 5000)
+    p2 = bench.dump_array(str(tmp_path), "big2", big.copy(), max_bytes=4096 + 4 * 5000)
+    s1, s2 = np.load(p1), np.load(p2)
+    assert np.array_equal(s1, s2) and s1.dtype == np.float32 and 4000 < s1.size <= 5000
+    assert s1[0] == 0 and s1[-1] == 99_999 and np.all(np.diff(s1) > 0)
+    assert os.path.getsize(p1) <= 4096 + 4 * 5000
+
+
 def test_timed_loop_refuses_a_non_stream():
     """timed_loop records HIP events on the stream it is given; anything else (a bool once reached it and
     crashed inside the HIP runtime, r06s11-s20) is a TypeError before any launch."""

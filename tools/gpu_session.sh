@@ -37,16 +37,16 @@ for s in $STEPS; do
         timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
         rc=$?; tail -3 "$OUT/smoke.log"; ok_or_fail $rc smoke ;;
     bench)
-        FA_BENCH_FULL="$OUT/bench_full.json" timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+        FA_BENCH_FULL="$OUT/bench_full.json" timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
         rc=$?; cat "$OUT/bench.json"; wc -c "$OUT/bench.json"; tail -3 "$OUT/bench.err"; ok_or_fail $rc bench ;;
     prof)
         timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-            python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-live-pmc > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
+            python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary --no-live-pmc > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
         rc=$?; tail -3 "$OUT/prof.err"; ok_or_fail $rc prof ;;
     pmc)
         for c in FETCH_SIZE WRITE_SIZE; do
             timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmc_$c" -o run -- \
-                python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-live-pmc > "$OUT/pmc_$c.json" 2> "$OUT/pmc_$c.err"
+                python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary --no-live-pmc > "$OUT/pmc_$c.json" 2> "$OUT/pmc_$c.err"
             rc=$?; tail -2 "$OUT/pmc_$c.err"; ok_or_fail $rc pmc_$c
         done ;;
     pmcw)  # the same passes for the secondary workloads whose traffic bench.py reports
@@ -54,7 +54,7 @@ for s in $STEPS; do
         rc=$?; ok_or_fail $rc pmcw ;;
     layouts)
         for L in rs chain; do
-            timeout -k 10 300 python bench.py --layout $L --steps 10 --no-cpu-baseline --no-secondary --no-live-pmc > "$OUT/bench_$L.json" 2> "$OUT/bench_$L.err"
+            timeout -k 10 300 python bench.py --layout $L --steps 10 --full --no-cpu-baseline --no-secondary --no-live-pmc > "$OUT/bench_$L.json" 2> "$OUT/bench_$L.err"
             rc=$?; cat "$OUT/bench_$L.json"; tail -2 "$OUT/bench_$L.err"; ok_or_fail $rc layout_$L
         done ;;
     h2d)
@@ -63,7 +63,7 @@ for s in $STEPS; do
             rc=$?; tail -1 "$OUT/h2d.jsonl"; tail -2 "$OUT/h2d.err"; ok_or_fail $rc h2d_$G
         done ;;
     ranks)  # multi-rank rehearsal of the driver's N>1 launch: bench.py spawns 2 ranks, which share the one GPU over gloo
-        timeout -k 10 600 python bench.py --gpus 2 --steps 5 --warmup 2 > "$OUT/bench_2ranks.json" 2> "$OUT/bench_2ranks.err"
+        timeout -k 10 600 python bench.py --gpus 2 --steps 5 --warmup 2 --full > "$OUT/bench_2ranks.json" 2> "$OUT/bench_2ranks.err"
         rc=$?; cat "$OUT/bench_2ranks.json"; tail -3 "$OUT/bench_2ranks.err"; ok_or_fail $rc ranks ;;
     rslaunch)  # local launch pattern of the rs / chain layouts at 4 and 8 ranks (tools/rs_launch.py)
         for W in 8 4; do
