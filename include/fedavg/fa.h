@@ -17,14 +17,28 @@
  * Numerics (tests/, DESIGN.md "Parity"):
  *   FA_FEDAVG  out_i = sum_k w_k x_{k,i} as an ordered fp32 FMA chain in client
  *              order starting from +0 (== libtorch acc.add_(x_k, w_k)),
- *              bf16 inputs widened exactly, bf16 output rounded to nearest-even
- *              once at the end.  Bit-exact vs oracle/ on every GPU layout
+ *              bf16 and fp16 inputs widened exactly (fp16 subnormals
+ *              included), a bf16 or fp16 output rounded to nearest-even once
+ *              at the end.  Bit-exact vs oracle/ on every GPU layout
  *              except FA_SHARD_CLIENT_RS (summation order changes, <=1e-6
  *              relative to sum_k |w_k x_k|).
  *   FA_LITERAL out_i = fl(fl(x_i + x_i) / divisor), x = the LAST client
  *              submitted (aggregator.cpp:63-88 with parts/parts_ aliased,
  *              systemAPI.cpp:34-37); divisor defaults to kTrainSize_10 = 1000
- *              (aggregator.cpp:48).  Correctly rounded division.
+ *              (aggregator.cpp:48).  Correctly rounded division.  A 16-bit
+ *              output is fl16(fl32(fl32(x + x) / divisor)).
+ *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
+ *              binary16, round-to-nearest-even: values that round beyond 65504
+ *              become +-inf, results below 2^-14 become fp16 subnormals (never
+ *              flushed), a NaN result is some quiet NaN (the payload is not
+ *              specified).
+ *   Dtype pairs (in -> out): f32 -> f32, f32 -> bf16, bf16 -> f32, bf16 -> bf16,
+ *              f16 -> f16, f16 -> f32, f32 -> f16.  bf16 <-> f16 is refused with
+ *              FA_ERR_ARG (fa_bucket_define, fa_reduce_device).
+ *   FA_F16 was added without a new FA_ABI_VERSION (a new enum value is additive):
+ *              a library without it answers FA_ERR_ARG ("bad dtype") to dtype 2,
+ *              e.g. from fa_fill_uniform(NULL, 0, FA_F16, ...), which touches no
+ *              device -- that is how a caller probes for fp16.
  */
 #ifndef FEDAVG_FA_H_
 #define FEDAVG_FA_H_
@@ -40,7 +54,7 @@ extern "C" {
 
 typedef struct fa_ctx fa_ctx; /* opaque: device slots, streams, pinned staging */
 
-typedef enum { FA_F32 = 0, FA_BF16 = 1 } fa_dtype;
+typedef enum { FA_F32 = 0, FA_BF16 = 1, FA_F16 = 2 /* IEEE binary16 */ } fa_dtype;
 typedef enum { FA_FEDAVG = 0, FA_LITERAL = 1 } fa_mode;
 
 typedef enum {
@@ -50,7 +64,7 @@ typedef enum {
     FA_ERR_NOMEM = -3,   /* device or pinned allocation failed */
     FA_ERR_STATE = -4,   /* call out of order (e.g. finalize before any submit) */
     FA_ERR_NODEV = -5,   /* no usable gfx950 device */
-    FA_ERR_ALIGN = -6,   /* pointer not 4-byte (f32) / 2-byte (bf16) aligned */
+    FA_ERR_ALIGN = -6,   /* pointer not 4-byte (f32) / 2-byte (bf16, f16) aligned */
     FA_ERR_NCCL = -7     /* an RCCL call failed (FA_SHARD_CLIENT_RS) */
 } fa_status;
 
@@ -61,8 +75,8 @@ typedef enum {
  * into an fp32 partial, and an RCCL reduce-scatter over xGMI (one communicator per GPU, ncclCommInitAll in
  * this process) sums the partials piece by piece, overlapped with the reduction of the next piece
  * (fa_tuning.rs_chunks pieces; GPU g ends with block g of every piece, fa_rs_segments).  The summation
- * order changes: within 1e-6 of sum_k |w_k x_k| (bit-exact at n_gpus = 1).  A bf16 output is the fp32
- * result rounded once to bf16 on each GPU after the exchange (so within one bf16 rounding of that). */
+ * order changes: within 1e-6 of sum_k |w_k x_k| (bit-exact at n_gpus = 1).  A bf16 or fp16 output is the fp32
+ * result rounded once to that type on each GPU after the exchange (so within one such rounding of that). */
 #define FA_SHARD_CLIENT_RS 0x2
 /* Accumulate on arrival (range layout, FedAvg): as soon as receipts 0..k-1 of a round are all in, their
  * ordered chain is enqueued (continued in an fp32 accumulator), so the phase end only reduces the
@@ -91,6 +105,7 @@ void fa_destroy(fa_ctx* ctx);
 /* One reduced bucket = the flattened named_parameters() of one model part
  * (model_part 1 -> parts[0].layers[0], aggregator.cpp:64; model_part m >= 2 ->
  * parts[1].layers[m-2], :118).  Allocates n_clients device slots per GPU. */
+/* in / out: one of the dtype pairs above (bf16 <-> f16: FA_ERR_ARG, naming both). */
 int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_dtype out, int n_clients,
                      fa_mode mode);
 /* kTrainSize_10 of aggregator.cpp:48 for FA_LITERAL buckets (default 1000). */
@@ -221,7 +236,8 @@ int fa_sync(fa_ctx* ctx);
  * starts at d_init[i] instead of +0 (used to split clients across launches or
  * GPUs bit-exactly).  Enqueued on hip_stream (a hipStream_t; NULL = the
  * ctx's compute stream of `gpu`); returns without synchronizing.  ctx may be
- * NULL except for bf16 output with D > 128 (needs ctx scratch). */
+ * NULL except for a bf16 or fp16 output with D > 128 (needs ctx scratch:
+ * FA_ERR_ARG without one).  A bf16 <-> f16 pair: FA_ERR_ARG. */
 int fa_reduce_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const float* h_weights, int D, size_t n,
                      fa_dtype in, void* d_out, fa_dtype out, fa_mode mode, const float* d_init, void* hip_stream);
 
@@ -260,7 +276,7 @@ int fa_release_stream(int device, void* hip_stream);
 
 /* Synthetic input generator on device, identical to oracle/fa_oracle.c:
  * element i = uniform[-1,1) from splitmix64(seed ^ client<<40 ^ (idx0+i)),
- * bf16 = round-to-nearest-even of that value. */
+ * bf16 and fp16 = round-to-nearest-even of that value. */
 int fa_fill_uniform(void* d_dst, size_t n, fa_dtype dt, uint64_t seed, uint32_t client, uint64_t idx0,
                     void* hip_stream);
 
@@ -278,10 +294,10 @@ typedef struct {
                          eighth, 3 the same with the odd eighths walked backwards (one-shot grid only),
                          4 phased: a persistent grid (one workgroup per CU) reduces a phase into LDS and
                          registers, then writes it, so the output never streams beside the inputs,
-                         5 (default) phased with a larger register stage (fewer phases; bf16 inputs
-                         take the form of walk 6), 6 phased with 512-thread workgroups (2 waves per
+                         5 (default) phased with a larger register stage (fewer phases; bf16 and
+                         fp16 inputs take the form of walk 6), 6 phased with 512-thread workgroups (2 waves per
                          SIMD).  Buckets smaller than one phase (walk 4: 18.9 M, walks 5 and 6:
-                         23.1 M elements per GPU on 256 CUs, f32 or bf16) take walk 2.  The phased
+                         23.1 M elements per GPU on 256 CUs, f32, bf16 or fp16) take walk 2.  The phased
                          kernels always use nt loads and sc1 stores.  With walk 5, a bucket below one
                          phase with >= 16 clients takes one phase sized to it */
     int rs_chunks;    /* FA_SHARD_CLIENT_RS: pieces per round (default 8) */

@@ -18,11 +18,13 @@ import numpy as np
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "lib", "libfa.so")
 
-F32, BF16 = 0, 1
+F32, BF16, F16 = 0, 1, 2  # F16: IEEE binary16 (torch.float16 / np.float16)
 FEDAVG, LITERAL = 0, 1
 SHARD_RANGE, SHARD_CLIENT_RS, ACCUMULATE_ON_ARRIVAL, TEST_SHARED_DEVICE = 0x1, 0x2, 0x4, 0x100
 OK, ERR_ARG, ERR_HIP, ERR_NOMEM, ERR_STATE, ERR_NODEV, ERR_ALIGN, ERR_NCCL = 0, -1, -2, -3, -4, -5, -6, -7
-DTYPE_SIZE = {F32: 4, BF16: 2}
+DTYPE_SIZE = {F32: 4, BF16: 2, F16: 2}
+# host view of a reduced bucket: numpy has no bf16, so a bf16 output comes back as its uint16 bits
+_OUT_NP = {F32: np.float32, BF16: np.uint16, F16: np.float16}
 
 _lib = None
 
@@ -76,6 +78,8 @@ def lib():
         "fa_submit_pinned": (I, [P, I, I, P, F]),
         "fa_submit_gather": (I, [P, I, I, I, P, P, F]),
         "fa_submit_gather_pinned": (I, [P, I, I, I, P, P, F]),
+        "fa_submit_piece_pinned": (I, [P, I, I, S, P, S]),
+        "fa_submit_commit": (I, [P, I, I, F]),
         "fa_finalize": (I, [P, I, P]),
         "fa_finalize_gather": (I, [P, I, I, P, P, I]),
         "fa_host_alloc": (I, [S, ctypes.POINTER(P)]),
@@ -255,7 +259,8 @@ PLAN_ONE_SHOT, PLAN_SCALAR, PLAN_PHASED = 0, 1, 2
 def plan_chain(in_dtype, out_dtype, n, n_clients, walk=0, cus=256):
     """fa_diag_plan_chain (diagnostic, host arithmetic): (kind, phases) of the launch one FedAvg chain over a
     16-byte aligned bucket of n elements takes under fa_tuning.walk `walk` (0 = the process default) on `cus`
-    CUs; kind PLAN_PHASED with phases > 1 means chip-wide meetings."""
+    CUs; kind PLAN_PHASED with phases > 1 means chip-wide meetings.  F16 takes the plans of BF16; a
+    BF16 <-> F16 pair raises FaError(ERR_ARG)."""
     k, ph = ctypes.c_int(), ctypes.c_longlong()
     check(lib().fa_diag_plan_chain(in_dtype, out_dtype, n, n_clients, walk, cus, ctypes.byref(k), ctypes.byref(ph)))
     return k.value, ph.value
@@ -424,6 +429,15 @@ class Aggregator:
         fn = lib().fa_submit_gather_pinned if pinned else lib().fa_submit_gather
         check(fn(self.handle, part_id, slot, len(pieces), ptrs, sizes, float(weight)))
 
+    def submit_piece(self, part_id, slot, byte_offset, piece):
+        """fa_submit_piece_pinned: bytes [byte_offset, + piece.nbytes) of the slot from `piece`, a view of a
+        PinnedBuffer the caller keeps unchanged until finalize returns; submit_commit makes them a receipt."""
+        piece = np.ascontiguousarray(piece)
+        check(lib().fa_submit_piece_pinned(self.handle, part_id, slot, byte_offset, piece.ctypes.data, piece.nbytes))
+
+    def submit_commit(self, part_id, slot, weight=1.0):
+        check(lib().fa_submit_commit(self.handle, part_id, slot, float(weight)))
+
     def sync_states(self, part_id, weights=None, stream=None):
         """fa_sync_part: every client slot of the part := the FedAvg of all slots (in place, async)."""
         wp = None
@@ -446,7 +460,7 @@ class Aggregator:
             check(lib().fa_finalize(self.handle, part_id, None))
         n, _, out_dtype = self.parts[part_id][:3]
         if out is None:
-            out = np.empty(n, np.float32 if out_dtype == F32 else np.uint16)
+            out = np.empty(n, _OUT_NP[out_dtype])
         check(lib().fa_finalize(self.handle, part_id, out.ctypes.data))
         return out
 
@@ -520,7 +534,7 @@ class Aggregator:
     def copy_output(self, part_id, out=None):
         n, _, out_dtype = self.parts[part_id][:3]
         if out is None:
-            out = np.empty(n, np.float32 if out_dtype == F32 else np.uint16)
+            out = np.empty(n, _OUT_NP[out_dtype])
         check(lib().fa_copy_output(self.handle, part_id, out.ctypes.data))
         return out
 

@@ -16,8 +16,8 @@ code never does.
   (``param.data = view``), so training updates the slot in place and the
   optimizers keep their Parameter objects;
 * aggregation is one in-place launch over all slots (``fa_sync_device``: the
-  ordered fp32 FMA chain, rounded once to the parameter dtype and written back
-  to every slot) instead of a per-tensor loop.
+  ordered fp32 FMA chain, rounded once to the parameter dtype -- fp32, bf16 or
+  fp16 -- and written back to every slot) instead of a per-tensor loop.
 
 Buffers (BatchNorm running statistics) stay per client, as in the reference,
 where only parameters are trained state.
@@ -49,8 +49,8 @@ class ClientStates:
         self.names = [n for n, _ in first.named_parameters()]
         self.shapes = [tuple(p.shape) for _, p in first.named_parameters()]
         dtypes = {p.dtype for _, p in first.named_parameters()}
-        if len(dtypes) != 1 or next(iter(dtypes)) not in (torch.float32, torch.bfloat16):
-            raise ValueError("parameters must all be fp32 or all bf16, got %s" % dtypes)
+        if len(dtypes) != 1 or next(iter(dtypes)) not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError("parameters must all be fp32, all bf16 or all fp16, got %s" % dtypes)
         self.dtype = next(iter(dtypes))
         self.device = next(first.parameters()).device
         self.n = sum(int(np.prod(s)) for s in self.shapes)
@@ -98,5 +98,5 @@ class ClientStates:
         import sys
         fa = sys.modules.get(__name__.rpartition(".")[0]) or importlib.import_module(__name__.rpartition(".")[0])
         import torch
-        dt = fa.F32 if self.dtype == torch.float32 else fa.BF16
+        dt = {torch.float32: fa.F32, torch.bfloat16: fa.BF16, torch.float16: fa.F16}[self.dtype]
         fa.sync_device(self.slots(), w, self.n, dt, stream=self.stream)

@@ -103,7 +103,14 @@ int fail(int code, const char* fmt, ...) {
     } while (0)
 
 inline size_t dsize(fa_dtype t) { return t == FA_F32 ? 4 : 2; }
-inline bool dvalid(int t) { return t == FA_F32 || t == FA_BF16; }
+inline bool dvalid(int t) { return t == FA_F32 || t == FA_BF16 || t == FA_F16; }
+// The refusal of a dtype pair the kernels do not have (fa::dtype_pair_ok): bf16 <-> f16.
+#define FA_PAIR(in, out)                                                                                    \
+    do {                                                                                                    \
+        if (!fa::dtype_pair_ok((fa_dtype)(in), (fa_dtype)(out)))                                            \
+            return fail(FA_ERR_ARG, "no %s -> %s reduction (a 16-bit bucket keeps its type or goes through f32)", \
+                        fa::dtype_name((fa_dtype)(in)), fa::dtype_name((fa_dtype)(out)));                   \
+    } while (0)
 
 // Restores the caller's current device on scope exit.
 struct DeviceGuard {
@@ -240,7 +247,7 @@ struct GpuRes {
     uint64_t copy_ev_gen = 0;      // the batch copy_ev was last recorded after
     std::map<hipStream_t, uint64_t> waited;  // per stream: the copy batch it last waited for
     hipEvent_t step_ev = nullptr;  // orders the rs exchange of a piece after its reduction
-    void* scratch = nullptr;       // fp32 chain accumulator for bf16-out, D > kMaxClients
+    void* scratch = nullptr;       // fp32 chain accumulator for a 16-bit output, D > kMaxClients
     // fa_output_crc32: the piece table (pinned staging + device copy) and the per-piece results, grown on use
     char* crc_host = nullptr;
     char* crc_dev = nullptr;
@@ -287,7 +294,7 @@ struct Part {
     std::vector<int> npiece;
     std::vector<size_t> piece_len;
     std::vector<void*> dout;       // per GPU: the output (range: cnt elements of `out`; rs: its fp32 shard)
-    std::vector<void*> dout16;     // rs with a bf16 output: per GPU, its shard rounded to bf16 (the copy-out's source)
+    std::vector<void*> dout16;     // rs with a 16-bit output: per GPU, its shard rounded to it (the copy-out's source)
     std::vector<float*> partial;   // rs: per GPU, fp32 partial over its clients, npad elements
     std::vector<float*> acc;       // FA_ACCUMULATE_ON_ARRIVAL: per GPU, fp32 chain of the reduced prefix
     std::vector<hipEvent_t> done;  // per GPU: orders the copy-out after the reduction (see mark_done)
@@ -326,7 +333,7 @@ struct fa_ctx {
 
 namespace {
 
-// Scratch of at least `bytes` on GPU g (only used by bf16 output with D > kMaxClients).
+// Scratch of at least `bytes` on GPU g (only used by a 16-bit output with D > kMaxClients).
 int ensure_scratch(fa_ctx* ctx, int g, size_t bytes) {
     GpuRes& r = ctx->gpu[g];
     if (r.scratch_bytes >= bytes) return FA_OK;
@@ -364,7 +371,7 @@ int reduce_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clien
     bool vec = true;
     if (mode == FA_FEDAVG)
         for (int k = 0; k < D; ++k) vec = vec && (((uintptr_t)clients[k] % 16) / si == phase);
-    const size_t out_vec_bytes = (size_t)V * so;  // 16 or 32 (f32 out of bf16) or 8 (bf16 out of f32)
+    const size_t out_vec_bytes = (size_t)V * so;  // 16 or 32 (f32 out of 16-bit) or 8 (16-bit out of f32)
     vec = vec && ((uintptr_t)dst + (size_t)head * so) % std::min<size_t>(16, out_vec_bytes) == 0;
     if (init) vec = vec && ((uintptr_t)init + (size_t)head * 4) % 16 == 0;
 
@@ -379,7 +386,7 @@ int reduce_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clien
         if (out == FA_F32) {
             acc = static_cast<float*>(dst);
         } else {
-            if (!ctx) return fail(FA_ERR_ARG, "bf16 output with D > %d needs a ctx for scratch", fa::kMaxClients);
+            if (!ctx) return fail(FA_ERR_ARG, "%s output with D > %d needs a ctx for scratch", fa::dtype_name(out), fa::kMaxClients);
             int rc = ensure_scratch(ctx, g, n * 4);
             if (rc) return rc;
             acc = static_cast<float*>(ctx->gpu[g].scratch);
@@ -582,7 +589,7 @@ void set_rs_runs(Part& p, int G, int chunks) {
             if (hi > lo) rr.push_back(Run{off, lo, hi - lo});
             off += q;
         }
-        p.run_src[(size_t)g] = p.out == FA_BF16 ? p.dout16[(size_t)g] : p.dout[(size_t)g];
+        p.run_src[(size_t)g] = p.out != FA_F32 ? p.dout16[(size_t)g] : p.dout[(size_t)g];
     }
 }
 
@@ -980,13 +987,13 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
         FA_NCCL(ncclGroupEnd());
         off += q;
     }
-    if (p.out == FA_BF16) {  // the fp32 shard rounded once to bf16 (fma(x, 1, +0) = x: the sums are never -0)
+    if (p.out != FA_F32) {  // the fp32 shard rounded once to bf16 / fp16 (fma(x, 1, +0) = x: the sums are never -0)
         const float one = 1.0f;
         for (int g = 0; g < G; ++g) {
             GpuRes& r = ctx->gpu[(size_t)g];
             DeviceGuard dg(r.dev);
             const void* shard = p.dout[(size_t)g];
-            int rc = reduce_on(ctx, g, rtu, &shard, &one, 1, p.npad / (size_t)G, FA_F32, p.dout16[(size_t)g], FA_BF16,
+            int rc = reduce_on(ctx, g, rtu, &shard, &one, 1, p.npad / (size_t)G, FA_F32, p.dout16[(size_t)g], p.out,
                                FA_FEDAVG, 1.0f, nullptr, r.comm);
             if (rc) return rc;
         }
@@ -1657,6 +1664,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     g_err.clear();
     if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
     if (!dvalid(in) || !dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
+    FA_PAIR(in, out);
     if (mode != FA_FEDAVG && mode != FA_LITERAL) return fail(FA_ERR_ARG, "bad mode");
     if (n_clients < 1) return fail(FA_ERR_ARG, "n_clients must be >= 1");
     const bool rs = (ctx->flags & FA_SHARD_CLIENT_RS) != 0;
@@ -1728,9 +1736,9 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
         }
         p.stride[g] = slot_stride(p.piece_len[g] * dsize(in), ctx->tuning.slot_skew);
         // one allocation: the slots (piece-major: piece j of every held slot, then piece j+1), then the
-        // output (range: cnt of `out`; rs: the fp32 shard, + its bf16 rounding for a bf16 output), then the
+        // output (range: cnt of `out`; rs: the fp32 shard, + its rounding for a bf16 / fp16 output), then the
         // rs partial or the eager accumulator, each 4 KiB aligned
-        const size_t shard16_bytes = rs && out == FA_BF16 ? (p.npad / G * 2 + 4095) / 4096 * 4096 : 0;
+        const size_t shard16_bytes = rs && out != FA_F32 ? (p.npad / G * 2 + 4095) / 4096 * 4096 : 0;
         const size_t out_bytes = rs ? p.npad / G * 4 : p.cnt[g] * dsize(out);
         const size_t out_off = (size_t)p.npiece[g] * held * p.stride[g];
         const size_t extra_off = out_off + (out_bytes + 4095) / 4096 * 4096 + shard16_bytes;
@@ -2101,6 +2109,7 @@ int fa_reduce_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const f
     if (!d_clients || !h_weights) return fail(FA_ERR_ARG, "client or weight array is null");
     if (D < 1) return fail(FA_ERR_ARG, "D must be >= 1");
     if (!dvalid(in) || !dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
+    FA_PAIR(in, out);
     if (mode != FA_FEDAVG && mode != FA_LITERAL) return fail(FA_ERR_ARG, "bad mode");
     if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -2285,6 +2294,7 @@ extern "C" int fa_diag_plan_chain(int in, int out, size_t n, int nc, int walk, i
     g_err.clear();
     if (!dvalid(in) || !dvalid(out) || walk < 0 || walk > 6 || cus < 0 || nc < 0)
         return fail(FA_ERR_ARG, "bad plan arguments");
+    FA_PAIR(in, out);
     fa::Tuning tu = defaults().tu;
     if (walk) tu.walk = walk - 1;
     const fa::ChainPlan pl =
@@ -2296,7 +2306,7 @@ extern "C" int fa_diag_plan_chain(int in, int out, size_t n, int nc, int walk, i
 
 // Diagnostic, not part of the ABI in fa.h: the plan of every launch one FA_SHARD_CLIENT_RS round enqueues for a
 // FedAvg bucket of n elements over n_clients clients on n_gpus GPUs of `cus` CUs (as reduce_part does: each
-// GPU's piece reductions into its fp32 partial, then, for a bf16 output, the rounding of its shard), under the
+// GPU's piece reductions into its fp32 partial, then, for a bf16 or fp16 output, the rounding of its shard), under the
 // process-default tuning with `chunks` pieces (0 = the default).  *launches counts them, *phased_launches
 // those that take the phased kernel, *max_phases the most phases of one launch.  Pure host arithmetic.
 extern "C" int fa_diag_rs_plan(size_t n, int n_gpus, int n_clients, int chunks, int in, int out, int cus,
@@ -2304,6 +2314,7 @@ extern "C" int fa_diag_rs_plan(size_t n, int n_gpus, int n_clients, int chunks, 
     g_err.clear();
     if (n_gpus < 1 || n_clients < 1 || chunks < 0 || !dvalid(in) || !dvalid(out) || cus < 0)
         return fail(FA_ERR_ARG, "bad rs plan arguments");
+    FA_PAIR(in, out);
     const CtxTuning ct = defaults();
     const fa::Tuning rtu = rs_launch_tuning(ct.tu);
     const size_t unit = (size_t)n_gpus * kShardUnit, npad = (n + unit - 1) / unit * unit;
@@ -2322,7 +2333,7 @@ extern "C" int fa_diag_rs_plan(size_t n, int n_gpus, int n_clients, int chunks, 
         if (c1 > c0)
             for (auto& pc : pieces)
                 note(fa::plan_chain((fa_dtype)in, FA_F32, (int64_t)((pc.second - pc.first) / V), c1 - c0, true, rtu, cus));
-        if (out == FA_BF16) note(fa::plan_chain(FA_F32, FA_BF16, (int64_t)(npad / n_gpus / 4), 1, true, rtu, cus));
+        if (out != FA_F32) note(fa::plan_chain(FA_F32, (fa_dtype)out, (int64_t)(npad / n_gpus / 4), 1, true, rtu, cus));
     }
     if (launches) *launches = nl;
     if (phased_launches) *phased_launches = np;

@@ -7,6 +7,11 @@
 
 namespace fa {
 
+// The (input, output) dtype pairs the library reduces: a bucket keeps its dtype, widens to fp32 or is rounded
+// from fp32.  The two 16-bit formats never convert into each other (bf16 <-> fp16 is refused, FA_ERR_ARG).
+inline bool dtype_pair_ok(fa_dtype in, fa_dtype out) { return in == out || in == FA_F32 || out == FA_F32; }
+inline const char* dtype_name(fa_dtype t) { return t == FA_F32 ? "f32" : t == FA_BF16 ? "bf16" : "f16"; }
+
 // Clients per launch.  Pointers + weights travel in the kernel-argument segment
 // (1.5 KiB of the 4 KiB kernarg segment), read with scalar loads; more clients continue the chain in
 // another pass.  128 covers C5 (D = 128) in one pass.

@@ -10,13 +10,13 @@
 // named_parameters() of a model part).  A wave reads 1 KiB contiguous from U
 // client buckets (16 B per lane, one global_load_dwordx4 each), then runs the
 // ordered FMA chain acc = fma(x_k, w_k, acc) in client order for the 4 (f32)
-// or 8 (bf16) elements it owns, and writes the result once.  Client pointers
+// or 8 (bf16, fp16) elements it owns, and writes the result once.  Client pointers
 // and weights sit in the kernel-argument segment (scalar loads, uniform per
 // wave); more than kMaxClients clients are handled by further passes that
 // continue the chain from the fp32 accumulator (bit-identical to one chain).
 //
 // Numerics follow oracle/fa_oracle.c exactly: fmaf chain from +0, exact bf16
-// widening, one round-to-nearest-even at the end; literal mode uses IEEE
+// (and fp16) widening, one round-to-nearest-even at the end; literal mode uses IEEE
 // division (hipcc's default correctly rounded f32 divide).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,6 +75,16 @@ __device__ __forceinline__ uint32_t f32_to_bf16(float f) {
     return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
+// fp16 (FA_F16, IEEE binary16): plain casts on _Float16, which hipcc lowers to v_cvt_f32_f16 (exact,
+// subnormals included) and v_cvt_f16_f32 (round-to-nearest-even under the kernels' default float mode, which
+// keeps f16 and f32 denormals; beyond 65504 -> inf, NaN -> a quiet NaN).  bf16 buckets are tagged uint16_t,
+// so fp16 takes _Float16 itself as its element tag.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ uint32_t f32_to_f16x2(float lo, float hi) {
+    return __builtin_bit_cast(uint32_t, f16x2{(_Float16)lo, (_Float16)hi});
+}
+
 // Element-type traits: a lane owns 16 bytes of every input bucket.
 template <typename T> struct In;
 template <> struct In<float> {
@@ -99,6 +109,18 @@ template <> struct In<uint16_t> {
         return bf16_to_f32(reinterpret_cast<const uint16_t*>(p)[i]);
     }
 };
+template <> struct In<_Float16> {
+    static constexpr int kVec = 8;
+    __device__ static __forceinline__ void widen(u32x4 r, float* x) {
+        // the whole 16 bytes at once: __builtin_bit_cast of one element of r (r.y, ...) reads r's first dword
+        const f16x8 h = __builtin_bit_cast(f16x8, r);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = (float)h[j];
+    }
+    __device__ static __forceinline__ float scalar(const void* p, int64_t i) {
+        return (float)reinterpret_cast<const _Float16*>(p)[i];
+    }
+};
 
 template <typename T> struct Out;
 template <> struct Out<float> {
@@ -114,19 +136,32 @@ template <> struct Out<float> {
         reinterpret_cast<float*>(base)[i] = a;
     }
 };
-template <> struct Out<uint16_t> {
+// 16-bit outputs: pack2(lo, hi) is two elements rounded once each, in one dword (lo in the low half); the
+// vector stores here and the packed LDS rows of the phased kernel (pack_rows16) are made of it.
+template <typename T> struct Out16 {
     template <int V, int SP>
     __device__ static __forceinline__ void store(void* base, int64_t e, const float* a) {
         uint16_t* p = reinterpret_cast<uint16_t*>(base) + e;
         if constexpr (V == 8) {
-            st16<SP>(p, u32x4{f32_to_bf16(a[0]) | (f32_to_bf16(a[1]) << 16), f32_to_bf16(a[2]) | (f32_to_bf16(a[3]) << 16),
-                              f32_to_bf16(a[4]) | (f32_to_bf16(a[5]) << 16), f32_to_bf16(a[6]) | (f32_to_bf16(a[7]) << 16)});
+            st16<SP>(p, u32x4{Out<T>::pack2(a[0], a[1]), Out<T>::pack2(a[2], a[3]), Out<T>::pack2(a[4], a[5]),
+                              Out<T>::pack2(a[6], a[7])});
         } else {
-            st8<SP>(p, u32x2{f32_to_bf16(a[0]) | (f32_to_bf16(a[1]) << 16), f32_to_bf16(a[2]) | (f32_to_bf16(a[3]) << 16)});
+            st8<SP>(p, u32x2{Out<T>::pack2(a[0], a[1]), Out<T>::pack2(a[2], a[3])});
         }
+    }
+};
+template <> struct Out<uint16_t> : Out16<uint16_t> {
+    __device__ static __forceinline__ uint32_t pack2(float lo, float hi) {
+        return f32_to_bf16(lo) | (f32_to_bf16(hi) << 16);
     }
     __device__ static __forceinline__ void scalar(void* base, int64_t i, float a) {
         reinterpret_cast<uint16_t*>(base)[i] = (uint16_t)f32_to_bf16(a);
+    }
+};
+template <> struct Out<_Float16> : Out16<_Float16> {
+    __device__ static __forceinline__ uint32_t pack2(float lo, float hi) { return f32_to_f16x2(lo, hi); }
+    __device__ static __forceinline__ void scalar(void* base, int64_t i, float a) {
+        reinterpret_cast<_Float16*>(base)[i] = (_Float16)a;
     }
 };
 
@@ -271,15 +306,15 @@ constexpr int kPhasedThreads = 256;
 constexpr int kSyncRing = 8;
 
 // An LDS row holds a lane's finished vector (the whole chain is done before it is stored), so it is kept in
-// the OUTPUT dtype: rounded once to bf16 there exactly as the global store would, same bits, and a bf16
-// output fits twice the rows (the 512-thread bf16 form: 20 instead of 10, a phase of 33.5 M elements
-// instead of 23.1 M).
-template <typename OUT> using LdsT = typename std::conditional<std::is_same<OUT, uint16_t>::value, uint16_t, float>::type;
+// the OUTPUT dtype: rounded once to bf16 (or fp16) there exactly as the global store would, same bits, and a
+// 16-bit output fits twice the rows (the 512-thread bf16 / fp16 form: 20 instead of 10, a phase of 33.5 M
+// elements instead of 23.1 M).
+template <typename OUT> using LdsT = typename std::conditional<sizeof(OUT) == 2, uint16_t, float>::type;
 
 template <typename IN, int REGS, int TH = kPhasedThreads, typename OUT = float>
 struct Phased {  // vectors per lane per phase: LDS (160 KiB per workgroup) + registers
     static constexpr int V = In<IN>::kVec;
-    // 256 threads: f32 -> f32 40; 512 threads: bf16 -> bf16 20, bf16 -> f32 10
+    // 256 threads: f32 -> f32 40; 512 threads: bf16 -> bf16 and f16 -> f16 20, bf16 / f16 -> f32 10
     static constexpr int RL = 160 * 1024 / (TH * V * (int)sizeof(LdsT<OUT>));
     static constexpr int RR = REGS / V;  // REGS 128: 32 / 16 vectors (arch VGPRs); 192: 48 / 24 (+ AGPRs)
 };
@@ -364,20 +399,19 @@ __device__ __forceinline__ void put(const ClientTable& t, int nc, void* out, int
     }
 }
 
-// LDS rows of a bf16 output: the finished vector as bf16 bits (pack_bf16), stored as they are.
-template <int V>
-__device__ __forceinline__ void pack_bf16(uint16_t* row, const float* acc) {
+// LDS rows of a 16-bit output: the finished vector as bf16 or fp16 bits (pack_rows16), stored as they are
+// (put_bits16).
+template <typename OUT, int V>
+__device__ __forceinline__ void pack_rows16(uint16_t* row, const float* acc) {
     if constexpr (V == 8) {
-        *reinterpret_cast<u32x4*>(row) =
-            u32x4{f32_to_bf16(acc[0]) | (f32_to_bf16(acc[1]) << 16), f32_to_bf16(acc[2]) | (f32_to_bf16(acc[3]) << 16),
-                  f32_to_bf16(acc[4]) | (f32_to_bf16(acc[5]) << 16), f32_to_bf16(acc[6]) | (f32_to_bf16(acc[7]) << 16)};
+        *reinterpret_cast<u32x4*>(row) = u32x4{Out<OUT>::pack2(acc[0], acc[1]), Out<OUT>::pack2(acc[2], acc[3]),
+                                               Out<OUT>::pack2(acc[4], acc[5]), Out<OUT>::pack2(acc[6], acc[7])};
     } else {
-        *reinterpret_cast<u32x2*>(row) =
-            u32x2{f32_to_bf16(acc[0]) | (f32_to_bf16(acc[1]) << 16), f32_to_bf16(acc[2]) | (f32_to_bf16(acc[3]) << 16)};
+        *reinterpret_cast<u32x2*>(row) = u32x2{Out<OUT>::pack2(acc[0], acc[1]), Out<OUT>::pack2(acc[2], acc[3])};
     }
 }
 template <int V, bool SYNC>
-__device__ __forceinline__ void put_bf16_bits(const ClientTable& t, int nc, void* out, int64_t e, const uint16_t* row) {
+__device__ __forceinline__ void put_bits16(const ClientTable& t, int nc, void* out, int64_t e, const uint16_t* row) {
     auto one = [&](void* base) {
         uint16_t* p = reinterpret_cast<uint16_t*>(base) + e;
         if constexpr (V == 8) st16<kStSc1>(p, *reinterpret_cast<const u32x4*>(row));
@@ -398,7 +432,7 @@ __global__ __launch_bounds__(TH) void fedavg_phased_kernel(const ClientTable t, 
                                                                        unsigned long long* tl) {
     constexpr int V = In<IN>::kVec, T = TH, RL = Phased<IN, REGS, TH, OUT>::RL, RR = Phased<IN, REGS, TH, OUT>::RR;
     constexpr int U = TH > 256 ? 8 : 16;  // loads in flight per wave (2 waves per SIMD at 512 threads)
-    constexpr bool kPacked = std::is_same<LdsT<OUT>, uint16_t>::value;  // LDS rows hold bf16 output bits
+    constexpr bool kPacked = sizeof(LdsT<OUT>) == 2;  // LDS rows hold the 16-bit output's bits
     __shared__ LdsT<OUT> buf[RL * T * V];
     // thread 0 takes the ticket; its value is first needed at the phase-0 meeting, so the atomic's
     // latency hides under the phase's loads
@@ -468,7 +502,7 @@ __global__ __launch_bounds__(TH) void fedavg_phased_kernel(const ClientTable t, 
                 float acc[V];
                 chain_vec<IN, U, true, INIT>(t, nc, init, head + v * V, acc);
                 if constexpr (kPacked) {
-                    pack_bf16<V>(reinterpret_cast<uint16_t*>(&buf[(i * T + threadIdx.x) * V]), acc);
+                    pack_rows16<OUT, V>(reinterpret_cast<uint16_t*>(&buf[(i * T + threadIdx.x) * V]), acc);
                 } else {
 #pragma unroll
                     for (int j = 0; j < V; ++j) buf[(i * T + threadIdx.x) * V + j] = acc[j];
@@ -501,7 +535,7 @@ __global__ __launch_bounds__(TH) void fedavg_phased_kernel(const ClientTable t, 
             const int64_t v = row_vec(i);
             if (v < nvec) {
                 if constexpr (kPacked)
-                    put_bf16_bits<V, SYNC>(t, nc, out, head + v * V,
+                    put_bits16<V, SYNC>(t, nc, out, head + v * V,
                                            reinterpret_cast<const uint16_t*>(&buf[(i * T + threadIdx.x) * V]));
                 else
                     put<OUT, V, SYNC>(t, nc, out, head + v * V, reinterpret_cast<const float*>(&buf[(i * T + threadIdx.x) * V]));
@@ -946,21 +980,45 @@ hipError_t launch_phased_r(PhasedDevice* d, const ClientTable& t, int nc, const 
 // more than the one-shot grid's interleaving (C2, D = 8: 0.085 vs 0.075 ms).
 constexpr int kSizedMinClients = 16;
 
-template <typename T> constexpr fa_dtype dtype_of() { return std::is_same<T, float>::value ? FA_F32 : FA_BF16; }
+template <typename T> constexpr fa_dtype dtype_of() {
+    return std::is_same<T, float>::value ? FA_F32 : std::is_same<T, _Float16>::value ? FA_F16 : FA_BF16;
+}
+
+// The element tags of a dtype pair, for the dispatchers: f(Tag<IN>, Tag<OUT>) with the kernels' element types
+// of (in, out), or hipErrorInvalidValue for a pair the library does not reduce (dtype_pair_ok: bf16 <-> fp16,
+// which the C ABI refuses with a message before it gets here).  One ladder instead of one per launcher.
+template <typename T> struct Tag { using type = T; };
+template <class F>
+hipError_t with_type(fa_dtype dt, F&& f) {
+    switch (dt) {
+        case FA_F32: return f(Tag<float>{});
+        case FA_BF16: return f(Tag<uint16_t>{});
+        case FA_F16: return f(Tag<_Float16>{});
+    }
+    return hipErrorInvalidValue;
+}
+template <class F>
+hipError_t with_types(fa_dtype in, fa_dtype out, F&& f) {
+    if (!dtype_pair_ok(in, out)) return hipErrorInvalidValue;
+    if (in == FA_F32) return with_type(out, [&](auto o) { return f(Tag<float>{}, o); });
+    // a 16-bit input keeps its own type or widens to fp32
+    if (out == FA_F32) return with_type(in, [&](auto i) { return f(i, Tag<float>{}); });
+    return with_type(in, [&](auto i) { return f(i, i); });
+}
 
 // The instantiations a plan may name (threads, register-stage bytes per lane): 256-thread f32 forms with
-// the register stages of the sized phases (192, 128, 32), the 512-thread form of walk 6 and of bf16 inputs
-// (96, and 64 / 32 for sized bf16 phases), and walk 4's 128-register form.
+// the register stages of the sized phases (192, 128, 32), the 512-thread form of walk 6
+// and of bf16 / fp16 inputs (96, and 64 / 32 for their sized phases), and walk 4's 128-register form.
 template <typename IN, typename OUT>
 hipError_t launch_phased_plan(PhasedDevice* d, const ChainPlan& pl, const ClientTable& t, int nc, const float* init,
                               void* out, int64_t head, int64_t nvec, int64_t n, hipStream_t s) {
-    constexpr bool bf = std::is_same<IN, uint16_t>::value;
+    constexpr bool h16 = sizeof(IN) == 2;  // bf16 or fp16 input
     switch (pl.threads * 1000 + pl.regs) {
         case 256128: return launch_phased_r<IN, OUT, 128, 256>(d, t, nc, init, out, head, nvec, n, s);
         case 512096: return launch_phased_r<IN, OUT, 96, 512>(d, t, nc, init, out, head, nvec, n, s);
         default: break;
     }
-    if constexpr (!bf) {
+    if constexpr (!h16) {
         switch (pl.threads * 1000 + pl.regs) {
             case 256192: return launch_phased_r<IN, OUT, 192, 256>(d, t, nc, init, out, head, nvec, n, s);
             case 256032: return launch_phased_r<IN, OUT, 32, 256>(d, t, nc, init, out, head, nvec, n, s);
@@ -1015,22 +1073,22 @@ hipError_t launch_chain_t(const ClientTable& t, int nc, const float* init, void*
 ChainPlan plan_chain(fa_dtype in, fa_dtype out, int64_t nvec, int nc, bool vector_ok, const Tuning& tu, int cus) {
     ChainPlan p{vector_ok ? kPlanOneShot : kPlanScalar, 0, 0, 0};
     if (!vector_ok || cus <= 0 || tu.walk < 3 || tu.walk > 5) return p;
-    const bool bf = in == FA_BF16;
-    const int V = bf ? 8 : 4;
-    // walk 4 (fa_tuning.walk 5, the default): bf16 inputs take the 512-thread form (2 waves per SIMD hide
+    const bool h16 = in != FA_F32;  // a 16-bit input (bf16 or fp16: the same forms)
+    const int V = h16 ? 8 : 4;
+    // walk 4 (fa_tuning.walk 5, the default): bf16 and fp16 inputs take the 512-thread form (2 waves per SIMD hide
     // the widening VALU work of 8 elements per load: C3 0.430 vs 0.439 ms), f32 the 256-thread one (C4 5.43
     // vs 5.49 ms, C5's share 2.55 vs 2.56), gpurun_out r01s25
-    const int th = tu.walk == 3 ? 256 : (tu.walk == 5 || bf) ? 512 : 256;
-    int regs = tu.walk == 3 ? 128 : (tu.walk == 5 || bf) ? 96 : 192;
-    const int rl = 160 * 1024 / (th * V * (out == FA_BF16 ? 2 : 4));  // Phased<>::RL
+    const int th = tu.walk == 3 ? 256 : (tu.walk == 5 || h16) ? 512 : 256;
+    int regs = tu.walk == 3 ? 128 : (tu.walk == 5 || h16) ? 96 : 192;
+    const int rl = 160 * 1024 / (th * V * (out == FA_F32 ? 4 : 2));  // Phased<>::RL
     const int64_t lanes = (int64_t)cus * th;
     if (nvec < lanes * (rl + regs / V)) {  // below one full phase
         if (tu.walk != 4 || nc < kSizedMinClients) return p;
         const int64_t q = (nvec + lanes - 1) / lanes;
-        if (q < (bf ? 4 : 8)) return p;  // too few vectors per lane: the one-shot grid
+        if (q < (h16 ? 4 : 8)) return p;  // too few vectors per lane: the one-shot grid
         // register stages (bytes per lane) instantiated for the sized phase, largest first
         static const int kF32[] = {192, 128, 32}, kBf16[] = {96, 64, 32};
-        const int* tiers = bf ? kBf16 : kF32;
+        const int* tiers = h16 ? kBf16 : kF32;
         regs = tiers[2];  // q <= RL: LDS only, the register stage unused
         if (q > rl)
             for (int i = 0; i < 3; ++i)
@@ -1089,13 +1147,10 @@ int phased_owned_slots(int dev) { return dev >= 0 && dev < kMaxDevices ? g_phase
 
 hipError_t launch_chain(const ClientTable& t, int nc, fa_dtype in, fa_dtype outdt, const float* init, void* out,
                         int64_t head, int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
-    if (in == FA_F32 && outdt == FA_F32)
-        return launch_chain_t<float, float>(t, nc, init, out, head, nvec, n, vector_ok, tu, s);
-    if (in == FA_F32 && outdt == FA_BF16)
-        return launch_chain_t<float, uint16_t>(t, nc, init, out, head, nvec, n, vector_ok, tu, s);
-    if (in == FA_BF16 && outdt == FA_F32)
-        return launch_chain_t<uint16_t, float>(t, nc, init, out, head, nvec, n, vector_ok, tu, s);
-    return launch_chain_t<uint16_t, uint16_t>(t, nc, init, out, head, nvec, n, vector_ok, tu, s);
+    return with_types(in, outdt, [&](auto i, auto o) {
+        return launch_chain_t<typename decltype(i)::type, typename decltype(o)::type>(t, nc, init, out, head, nvec, n,
+                                                                                      vector_ok, tu, s);
+    });
 }
 
 namespace {
@@ -1115,13 +1170,10 @@ hipError_t launch_literal_t(const void* x, void* out, float divisor, int64_t hea
 
 hipError_t launch_literal(const void* x, fa_dtype in, void* out, fa_dtype outdt, float divisor, int64_t head,
                           int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
-    if (in == FA_F32 && outdt == FA_F32)
-        return launch_literal_t<float, float>(x, out, divisor, head, nvec, n, vector_ok, tu, s);
-    if (in == FA_F32 && outdt == FA_BF16)
-        return launch_literal_t<float, uint16_t>(x, out, divisor, head, nvec, n, vector_ok, tu, s);
-    if (in == FA_BF16 && outdt == FA_F32)
-        return launch_literal_t<uint16_t, float>(x, out, divisor, head, nvec, n, vector_ok, tu, s);
-    return launch_literal_t<uint16_t, uint16_t>(x, out, divisor, head, nvec, n, vector_ok, tu, s);
+    return with_types(in, outdt, [&](auto i, auto o) {
+        return launch_literal_t<typename decltype(i)::type, typename decltype(o)::type>(x, out, divisor, head, nvec, n,
+                                                                                        vector_ok, tu, s);
+    });
 }
 
 namespace {
@@ -1184,18 +1236,19 @@ hipError_t launch_sync_t(const ClientTable& t, int nc, const float* init, int64_
 
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, int64_t head, int64_t nvec,
                        int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
-    if (dt == FA_F32) return launch_sync_t<float>(t, nc, init, head, nvec, n, vector_ok, tu, s);
-    return launch_sync_t<uint16_t>(t, nc, init, head, nvec, n, vector_ok, tu, s);
+    return with_type(dt, [&](auto e) {
+        return launch_sync_t<typename decltype(e)::type>(t, nc, init, head, nvec, n, vector_ok, tu, s);
+    });
 }
 
 hipError_t launch_broadcast(const ClientTable& t, int nc, fa_dtype dt, const float* acc, int64_t n,
                             const Tuning& tu, hipStream_t s) {
     const int64_t g = grid_scalar(n, tu);
-    if (dt == FA_F32)
-        hipLaunchKernelGGL((broadcast_kernel<float>), dim3((unsigned)g), dim3(tu.block), 0, s, t, nc, acc, n);
-    else
-        hipLaunchKernelGGL((broadcast_kernel<uint16_t>), dim3((unsigned)g), dim3(tu.block), 0, s, t, nc, acc, n);
-    return hipGetLastError();
+    return with_type(dt, [&](auto e) {
+        hipLaunchKernelGGL((broadcast_kernel<typename decltype(e)::type>), dim3((unsigned)g), dim3(tu.block), 0, s, t,
+                           nc, acc, n);
+        return hipGetLastError();
+    });
 }
 
 namespace {
@@ -1224,25 +1277,22 @@ hipError_t launch_segargs_t(const SegArgs& a, int max_nc, int block, hipStream_t
 
 hipError_t launch_segargs(const SegArgs& a, fa_dtype in, fa_dtype outdt, int max_nc, const Tuning& tu, hipStream_t s) {
     if (a.nseg <= 0) return hipSuccess;
-    if (in == FA_F32 && outdt == FA_F32) return launch_segargs_t<float, float>(a, max_nc, tu.block, s);
-    if (in == FA_F32 && outdt == FA_BF16) return launch_segargs_t<float, uint16_t>(a, max_nc, tu.block, s);
-    if (in == FA_BF16 && outdt == FA_F32) return launch_segargs_t<uint16_t, float>(a, max_nc, tu.block, s);
-    return launch_segargs_t<uint16_t, uint16_t>(a, max_nc, tu.block, s);
+    return with_types(in, outdt, [&](auto i, auto o) {
+        return launch_segargs_t<typename decltype(i)::type, typename decltype(o)::type>(a, max_nc, tu.block, s);
+    });
 }
 
 hipError_t launch_segments(const SegDesc* d_segs, int nseg, int64_t blocks, fa_dtype in, fa_dtype outdt, int max_nc,
                            const Tuning& tu, hipStream_t s) {
     if (nseg <= 0) return hipSuccess;
-    if (in == FA_F32 && outdt == FA_F32) return launch_segments_t<float, float>(d_segs, nseg, blocks, max_nc, tu.block, s);
-    if (in == FA_F32 && outdt == FA_BF16)
-        return launch_segments_t<float, uint16_t>(d_segs, nseg, blocks, max_nc, tu.block, s);
-    if (in == FA_BF16 && outdt == FA_F32)
-        return launch_segments_t<uint16_t, float>(d_segs, nseg, blocks, max_nc, tu.block, s);
-    return launch_segments_t<uint16_t, uint16_t>(d_segs, nseg, blocks, max_nc, tu.block, s);
+    return with_types(in, outdt, [&](auto i, auto o) {
+        return launch_segments_t<typename decltype(i)::type, typename decltype(o)::type>(d_segs, nseg, blocks, max_nc,
+                                                                                         tu.block, s);
+    });
 }
 
 bool phased_takes(fa_dtype in, fa_dtype out, int64_t nvec, int nc, const Tuning& tu) {
-    if (tu.walk < 3 || tu.walk > 5) return false;
+    if (tu.walk < 3 || tu.walk > 5 || !dtype_pair_ok(in, out)) return false;
     PhasedDevice* d = phased_device();
     return d && plan_chain(in, out, nvec, nc, true, tu, d->cus).kind == kPlanPhased;
 }
@@ -1363,11 +1413,11 @@ hipError_t launch_fill(void* dst, int64_t n, fa_dtype dt, uint64_t seed, uint32_
                        hipStream_t s) {
     Tuning tu{256, 8192, 8, 0, 0};
     const int64_t g = grid_for(n, tu);
-    if (dt == FA_F32)
-        hipLaunchKernelGGL((fill_kernel<float>), dim3((unsigned)g), dim3(256), 0, s, dst, n, seed, client, idx0);
-    else
-        hipLaunchKernelGGL((fill_kernel<uint16_t>), dim3((unsigned)g), dim3(256), 0, s, dst, n, seed, client, idx0);
-    return hipGetLastError();
+    return with_type(dt, [&](auto e) {
+        hipLaunchKernelGGL((fill_kernel<typename decltype(e)::type>), dim3((unsigned)g), dim3(256), 0, s, dst, n, seed,
+                           client, idx0);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------ CRC-32 of output byte ranges

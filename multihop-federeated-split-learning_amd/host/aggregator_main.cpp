@@ -77,7 +77,10 @@ void usage() {
                  "       [--rounds R] [--port-base P] [--discover] [--link-mbps M] [--samples id:n,...]\n"
                  "       [--divisor K] [--last-layers L] [--no-pinned] [--layout range|rs] [--rs-chunks C]\n"
                  "       [--eager] [--stall-report S] [--receipt-timeout S] [--rx-concurrency K]\n"
-                 "       [--senders S] [--stream-min-bytes N] [--crc gpu|host] [--test-shared-device]\n";
+                 "       [--senders S] [--stream-min-bytes N] [--crc gpu|host] [--test-shared-device]\n"
+                 "A bucket takes the dtype of its first receipt's parameters (all fp32, all bf16 or all fp16, by\n"
+                 "their storage type) and is reduced and replied in it; a later receipt of another size or dtype\n"
+                 "ends the process (exit 1).\n";
 }
 
 bool parse_args(int argc, char** argv, Options* o) {
@@ -293,18 +296,22 @@ public:
             std::exit(1);
         }
         Bucket& b = buckets_[r.model_part];
-        const int es = ar.param_elem_size();  // the bucket dtype: fp32 (the reference) or bf16 (config C3)
+        // the bucket dtype, from the parameters' storage type (never from the element size: bf16 and fp16
+        // are both 2 bytes): fp32 (the reference), bf16 (config C3) or fp16 (owners that train with .half())
+        const ParamDtype pd = ar.param_dtype();
+        const int es = ar.param_elem_size();
         if (!b.defined) {
-            if (es == 0) {
-                std::cerr << "[aggregator] bucket " << r.model_part << ": parameters not all fp32 or all bf16\n";
+            if (pd == ParamDtype::None) {
+                std::cerr << "[aggregator] bucket " << r.model_part << ": parameters not all fp32, bf16 or fp16\n";
                 std::exit(1);
             }
             b.numel = (size_t)ar.param_numel();
             b.elem = es;
-            const fa_dtype dt = es == 4 ? FA_F32 : FA_BF16;
+            b.dtype = pd;
+            const fa_dtype dt = pd == ParamDtype::F32 ? FA_F32 : pd == ParamDtype::BF16 ? FA_BF16 : FA_F16;
             FA_CHECK(fa_bucket_define(ctx_, r.model_part, b.numel, dt, dt, o_.data_owners, o_.mode));
             b.defined = true;
-        } else if ((size_t)ar.param_numel() != b.numel || es != b.elem) {
+        } else if ((size_t)ar.param_numel() != b.numel || pd != b.dtype) {
             std::cerr << "[aggregator] bucket " << r.model_part << " changed size or dtype\n";
             std::exit(1);
         }
@@ -542,7 +549,8 @@ private:
     struct Bucket {
         bool defined = false;
         size_t numel = 0, bytes_in = 0;
-        int elem = 4;  // bytes per parameter element: 4 fp32, 2 bf16
+        int elem = 4;  // bytes per parameter element: 4 fp32, 2 bf16 / fp16
+        ParamDtype dtype = ParamDtype::F32;  // what the bucket was defined with; a receipt of another is refused
         Recs recs;            // the parameter records of the last pinned receipt (the streaming layout)
         size_t recs_len = 0;  // ... for archives of this length
         Receipt last;

@@ -732,13 +732,26 @@ bool TorchArchive::params_are_float() const {
     return true;
 }
 
-int TorchArchive::param_elem_size() const {
-    if (params_.empty()) return 4;
+ParamDtype TorchArchive::param_dtype() const {
+    if (params_.empty()) return ParamDtype::F32;
     const std::string& st = params_[0].storage_type;
-    if (st != "FloatStorage" && st != "BFloat16Storage") return 0;
+    const ParamDtype dt = st == "FloatStorage"      ? ParamDtype::F32
+                          : st == "BFloat16Storage" ? ParamDtype::BF16
+                          : st == "HalfStorage"     ? ParamDtype::F16
+                                                    : ParamDtype::None;
     for (auto& t : params_)
-        if (t.storage_type != st) return 0;
-    return st == "FloatStorage" ? 4 : 2;
+        if (t.storage_type != st) return ParamDtype::None;
+    return dt;
+}
+
+int TorchArchive::param_elem_size() const {
+    switch (param_dtype()) {
+        case ParamDtype::F32: return 4;
+        case ParamDtype::BF16:
+        case ParamDtype::F16: return 2;
+        case ParamDtype::None: break;
+    }
+    return 0;
 }
 
 bool TorchArchive::param_segments(std::vector<const void*>* ptrs, std::vector<size_t>* bytes) const {
@@ -773,7 +786,7 @@ static void walk_param(const TensorView& t, Fn fn) {
 
 bool TorchArchive::gather_param_bytes(uint8_t* dst, std::string* err) const {
     const int es = param_elem_size();
-    if (!es) return fail(err, "parameters are not all fp32 or all bf16");
+    if (!es) return fail(err, "parameters are not all fp32, all bf16 or all fp16");
     for (auto& t : params_) {
         if (t.contiguous) {
             std::memcpy(dst, t.data, (size_t)t.numel * (size_t)es);
@@ -876,7 +889,7 @@ bool TorchArchive::with_params_into(const float* src, uint8_t* o, std::string* e
 
 bool TorchArchive::with_param_bytes_into(const uint8_t* src, uint8_t* o, std::string* err) const {
     const int es = param_elem_size();
-    if (!es) return fail(err, "parameters are not all fp32 or all bf16");
+    if (!es) return fail(err, "parameters are not all fp32, all bf16 or all fp16");
     std::vector<void*> dsts;
     std::vector<size_t> bytes;
     if (layout_into(o, &dsts, &bytes, nullptr)) {  // contiguous parameters: copy the gaps, then the values
@@ -903,7 +916,7 @@ bool TorchArchive::layout_into(uint8_t* o, std::vector<void*>* dsts, std::vector
                                std::string* err) const {
     std::vector<std::pair<size_t, size_t>> holes;  // [lo, hi) of each parameter's values
     const int es = param_elem_size();
-    if (!es) return fail(err, "parameters are not all fp32 or all bf16");
+    if (!es) return fail(err, "parameters are not all fp32, all bf16 or all fp16");
     for (auto& t : params_) {
         if (!t.contiguous) return fail(err, "parameter " + t.name + " is strided");
         holes.push_back({(size_t)(t.data - base_), (size_t)(t.data - base_) + (size_t)t.numel * (size_t)es});

@@ -34,7 +34,7 @@ struct ZipEntry {
 
 struct TensorView {
     std::string name;           // dotted path, e.g. "0.conv1.weight"
-    std::string storage_type;   // "FloatStorage", "BFloat16Storage", "LongStorage", ...
+    std::string storage_type;   // "FloatStorage", "BFloat16Storage", "HalfStorage", "LongStorage", ...
     size_t elem_size = 0;
     std::vector<int64_t> sizes, strides;
     int64_t storage_offset = 0; // elements
@@ -43,6 +43,8 @@ struct TensorView {
     int record = -1;            // index into entries()
     const uint8_t* data = nullptr;  // first element (storage + offset) inside the archive bytes
 };
+
+enum class ParamDtype { None = 0, F32, BF16, F16 };
 
 class TorchArchive {
 public:
@@ -54,11 +56,14 @@ public:
     const std::vector<TensorView>& buffers() const { return buffers_; } // named_buffers(true) order
     int64_t param_numel() const;
     bool params_are_float() const;
-    // Bytes per parameter element when every parameter is fp32 (4) or every one is bf16 (2); 0 when
-    // they are mixed or of another type (the bucket dtype of a receipt).
+    // The bucket dtype of a receipt, from the parameters' storage type: all FloatStorage, all
+    // BFloat16Storage or all HalfStorage; None when they are mixed (Half with BFloat16 too) or of another type.
+    ParamDtype param_dtype() const;
+    // Its bytes per element: 4 (fp32), 2 (bf16, fp16); 0 for None.  The two 2-byte types differ only in
+    // param_dtype(), so a caller that reduces the values asks that, not the size.
     int param_elem_size() const;
 
-    // Contiguous pieces of the parameter bucket, in order (one per contiguous param, fp32 or bf16
+    // Contiguous pieces of the parameter bucket, in order (one per contiguous param, fp32, bf16 or fp16
     // throughout): a gather list for fa_submit_gather.  False if some param is strided or the types mix.
     bool param_segments(std::vector<const void*>* ptrs, std::vector<size_t>* bytes) const;
     // Strided-safe copy of all parameters (as fp32) into dst[param_numel()].
@@ -75,7 +80,7 @@ public:
     // The same in two steps, for a producer that writes the values itself (e.g. a D2H copy straight
     // into the outgoing frame): layout_into copies everything but the parameter values into dst and
     // returns where each parameter's values go (named_parameters order; false when a parameter is
-    // strided or the parameters are not all fp32 or all bf16); seal_params then recomputes the CRC-32
+    // strided or the parameters are not all fp32, all bf16 or all fp16); seal_params then recomputes the CRC-32
     // of the parameter records.
     bool layout_into(uint8_t* dst, std::vector<void*>* param_dsts, std::vector<size_t>* param_bytes,
                      std::string* err) const;

@@ -1,6 +1,8 @@
 // archive_tool.cpp -- CLI over host/archive and host/wire for the CPU tests.
 //   fa_archive_tool dump <archive>                  JSON: params/buffers (name, storage, shape, numel)
 //   fa_archive_tool gather <archive> <out.f32>      parameters in named_parameters order (fp32)
+//   fa_archive_tool gather-bytes <archive> <out>    the same in their own type (fp32, bf16 or fp16), raw
+//   fa_archive_tool patch-bytes <archive> <in> <out> patch for either bucket dtype: <in> holds raw values
 //   fa_archive_tool patch <archive> <in.f32> <out>  archive with new parameters + fixed CRCs
 //   fa_archive_tool frame <archive> <out>           a Message.h aggregation frame carrying it
 //   fa_archive_tool unframe <frame> <out>           the archive inside a frame (round trip)
@@ -126,7 +128,7 @@ int main(int argc, char** argv) {
     if (argc >= 2 && std::string(argv[1]) == "encode") return wire_encode(argc, argv);
     if (argc >= 3 && std::string(argv[1]) == "decode") return wire_decode(slurp(argv[2]));
     if (argc < 3) {
-        std::cerr << "usage: fa_archive_tool dump|gather|patch|frame|unframe ...\n";
+        std::cerr << "usage: fa_archive_tool dump|gather|gather-bytes|patch|patch-bytes|frame|unframe ...\n";
         return 2;
     }
     const std::string cmd = argv[1];
@@ -149,7 +151,9 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (cmd == "dump") {
-        printf("{\"param_numel\":%lld,", (long long)ar.param_numel());
+        static const char* const kDtype[] = {"none", "fp32", "bf16", "fp16"};
+        printf("{\"param_numel\":%lld,\"param_dtype\":\"%s\",\"param_elem_size\":%d,", (long long)ar.param_numel(),
+               kDtype[(int)ar.param_dtype()], ar.param_elem_size());
         dump_list("params", ar.params());
         printf(",");
         dump_list("buffers", ar.buffers());
@@ -158,6 +162,19 @@ int main(int argc, char** argv) {
         std::vector<float> v((size_t)ar.param_numel());
         if (!ar.gather_params(v.data(), &err)) return std::cerr << err << "\n", 1;
         spit(argv[3], v.data(), v.size() * 4);
+    } else if (cmd == "gather-bytes" && argc > 3) {
+        std::vector<uint8_t> v((size_t)ar.param_numel() * (size_t)ar.param_elem_size());
+        if (!ar.gather_param_bytes(v.data(), &err)) return std::cerr << err << "\n", 1;
+        spit(argv[3], v.data(), v.size());
+    } else if (cmd == "patch-bytes" && argc > 4) {
+        const std::string in = slurp(argv[3]);
+        if (!ar.param_elem_size()) return std::cerr << "parameters are not all fp32, all bf16 or all fp16\n", 1;
+        if (in.size() != (size_t)ar.param_numel() * (size_t)ar.param_elem_size())
+            return std::cerr << "wrong value count\n", 1;
+        std::string out(ar.size(), '\0');
+        if (!ar.with_param_bytes_into((const uint8_t*)in.data(), (uint8_t*)&out[0], &err))
+            return std::cerr << err << "\n", 1;
+        spit(argv[4], out.data(), out.size());
     } else if (cmd == "patch" && argc > 4) {
         const std::string in = slurp(argv[3]);
         if (in.size() != (size_t)ar.param_numel() * 4) return std::cerr << "wrong value count\n", 1;

@@ -2,11 +2,11 @@
 // Python, no torch), as the reference's aggregator process would drive it (aggregator.cpp:55-167 on
 // libfa): fa_create -> fa_bucket_define -> the client slots filled in place (fa_fill_uniform on
 // fa_bucket_slot) -> fa_reduce_part per round.  One GPU, range layout: HIP events on the launch stream;
-// the rs layout (its exchange and bf16 rounding run on the context's own exchange stream) and several GPUs
+// the rs layout (its exchange and bf16 / fp16 rounding run on the context's own exchange stream) and several GPUs
 // (FA_SHARD_RANGE or FA_SHARD_CLIENT_RS over the first G devices): host wall clock around the rounds,
 // fa_sync at both ends.  Prints one JSON line with bench.py's metric (GiB/s of client input).
 //
-//   fa_bench [--workload northstar|c2|c3|c4|c5r] [--steps K] [--warmup W] [--gpus G] [--layout range|rs]
+//   fa_bench [--workload northstar|c2|c3|c3h|c4|c5r] [--steps K] [--warmup W] [--gpus G] [--layout range|rs]
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -33,6 +33,7 @@ const Workload kWorkloads[] = {
     {"northstar", 32, (size_t)64 << 20, FA_F32, FA_F32},  // 256 MiB fp32 x 32 clients
     {"c2", 8, 12557962, FA_F32, FA_F32},                   // ResNet-18 full model, 8 owners
     {"c3", 32, 42737546, FA_BF16, FA_BF16},                // ResNet-101 (basic blocks), 32 owners, bf16
+    {"c3h", 32, 42737546, FA_F16, FA_F16},                 // the same in fp16 (same bytes as c3)
     {"c4", 64, 139611210, FA_F32, FA_F32},                 // VGG-19, 64 owners
     {"c5r", 128, (size_t)1 << 25, FA_F32, FA_F32},         // C5's per-GPU share at 8 GPUs
 };
@@ -81,7 +82,7 @@ int main(int argc, char** argv) {
     fa_ctx* ctx = nullptr;
     check(fa_create(&ctx, gpus, flags), "fa_create");
     const int part = 1, D = wl->clients;
-    const fa_dtype out = wl->out;  // the rs layout sums fp32 partials, rounded once for a bf16 output
+    const fa_dtype out = wl->out;  // the rs layout sums fp32 partials, rounded once for a bf16 or fp16 output
     const size_t n = wl->elems, s_in = wl->in == FA_F32 ? 4 : 2, s_out = out == FA_F32 ? 4 : 2;
     check(fa_bucket_define(ctx, part, n, wl->in, out, D, FA_FEDAVG), "fa_bucket_define");
     // synthetic client buckets generated in HBM (bench.py's inputs: seed 0x5EED, client k, global index)

@@ -50,7 +50,10 @@ def client_bounds(n_clients, world, rank):
 
 
 def fa_reducer(fa, in_dtype, stream=None):
-    """Local reduction on the GPU through libfa.so: (clients, weights, n, init) -> fp32 tensor."""
+    """Local reduction on the GPU through libfa.so: (clients, weights, n, init) -> fp32 tensor.
+
+    in_dtype is any bucket dtype of the library (fa.F32, fa.BF16, fa.F16): the partials and the exchange are
+    fp32 whatever the clients hold, so fp16 buckets need nothing here beyond the kernels."""
     import torch
 
     def reduce(clients, weights, n, init=None, out=None):
