@@ -27,6 +27,24 @@
  *              systemAPI.cpp:34-37); divisor defaults to kTrainSize_10 = 1000
  *              (aggregator.cpp:48).  Correctly rounded division.  A 16-bit
  *              output is fl16(fl32(fl32(x + x) / divisor)).
+ *   FA_TRIMMED coordinate-wise trimmed mean over the D clients, specified bit for bit.  For every
+ *              element i, with trim t (0 <= t, 2t < D):
+ *              1. x_{k,i} is widened to fp32 exactly (bf16, fp16 with its subnormals).
+ *              2. The D values are sorted ascending under this total order: any NaN (either sign) is
+ *                 greater than +inf; otherwise numeric order; -0 < +0; equal bit patterns are
+ *                 interchangeable.  It is the order of the unsigned key k(x) = 0xFFFFFFFF if x is NaN,
+ *                 ~bits if the sign bit is set, bits | 0x80000000 otherwise.  A sorted NaN decodes to
+ *                 some quiet NaN (payload unspecified).
+ *              3. acc = +0, then acc = fl32(acc + s_j) for j = t .. D-t-1 in ascending order (plain adds).
+ *              4. out_i = fl32(acc / (float)(D - 2t)), correctly rounded division (as FA_LITERAL).
+ *              5. A bf16 or fp16 output is that rounded once to nearest-even, as for FA_FEDAVG.
+ *              Weights are ignored (as for FA_LITERAL).  Up to t NaN or +inf values per element are
+ *              trimmed away at the top and t values of -inf at the bottom.  t = 0 is an unweighted
+ *              mean summed in ascending order (not the FedAvg chain); t = (D-1)/2 is the median (the
+ *              middle value for odd D, fl(fl(a+b)/2) of the two middle values for even D); D = 1 is
+ *              fl(fl(+0 + x)/1).  D <= FA_TRIMMED_MAX_CLIENTS: the sort runs on one GPU in
+ *              one pass.  Added without a new FA_ABI_VERSION: fa_trimmed_device(NULL, 0, ptrs, D, 0, ...)
+ *              touches no device and answers FA_OK -- that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -55,7 +73,11 @@ extern "C" {
 typedef struct fa_ctx fa_ctx; /* opaque: device slots, streams, pinned staging */
 
 typedef enum { FA_F32 = 0, FA_BF16 = 1, FA_F16 = 2 /* IEEE binary16 */ } fa_dtype;
-typedef enum { FA_FEDAVG = 0, FA_LITERAL = 1 } fa_mode;
+typedef enum { FA_FEDAVG = 0, FA_LITERAL = 1, FA_TRIMMED = 2 /* trimmed mean / median */ } fa_mode;
+/* fa_set_trim / fa_trimmed_device: the largest valid trim, (D-1)/2 -- the coordinate-wise median. */
+#define FA_TRIM_MEDIAN (-1)
+/* Most clients of an FA_TRIMMED bucket (more: FA_ERR_ARG; a sort has no multi-pass form). */
+#define FA_TRIMMED_MAX_CLIENTS 128
 
 typedef enum {
     FA_OK = 0,
@@ -110,6 +132,18 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
                      fa_mode mode);
 /* kTrainSize_10 of aggregator.cpp:48 for FA_LITERAL buckets (default 1000). */
 int fa_set_literal_divisor(fa_ctx* ctx, int part_id, float divisor);
+/* Trim t of FA_TRIMMED buckets: FA_TRIM_MEDIAN (the default) or 0 <= t with 2t < D.  part_id as for
+ * fa_set_literal_divisor: < 0 sets the context-wide default of parts defined later (checked against D
+ * when a part is defined), else the part's own trim from its next reduction on.  FA_ERR_ARG (naming D and
+ * trim) when trim < -1 or 2 trim >= D.
+ * An FA_TRIMMED bucket: at most FA_TRIMMED_MAX_CLIENTS clients; not on an FA_SHARD_CLIENT_RS context (the
+ * rule needs every client's value of an element on one GPU); FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager
+ * (nothing is reduced before the phase end, as for FA_LITERAL); its receipts are never kept host-side
+ * (fa_submit_pinned copies them in, fa_bucket_host_read says 0); every client must have submitted before
+ * fa_finalize*.  fa_reduce_part(s) (h_weights ignored; its own launch, never in the segment table),
+ * fa_finalize*, fa_copy_output, fa_output_crc32, range shards and range pieces work as for FA_FEDAVG.
+ * fa_sync_part and fa_sync_device keep their FedAvg meaning: fa_sync_part refuses a trimmed part. */
+int fa_set_trim(fa_ctx* ctx, int part_id, int trim);
 
 /* Replaces one receipt: torch::load into the global module + the per-parameter
  * update (aggregator.cpp:63-88 / :117-142).  Copies host_src (n_elems of the
@@ -237,9 +271,18 @@ int fa_sync(fa_ctx* ctx);
  * GPUs bit-exactly).  Enqueued on hip_stream (a hipStream_t; NULL = the
  * ctx's compute stream of `gpu`); returns without synchronizing.  ctx may be
  * NULL except for a bf16 or fp16 output with D > 128 (needs ctx scratch:
- * FA_ERR_ARG without one).  A bf16 <-> f16 pair: FA_ERR_ARG. */
+ * FA_ERR_ARG without one).  A bf16 <-> f16 pair: FA_ERR_ARG.  mode FA_TRIMMED: FA_ERR_ARG (the
+ * signature has no room for a trim and d_init no meaning there; use fa_trimmed_device). */
 int fa_reduce_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const float* h_weights, int D, size_t n,
                      fa_dtype in, void* d_out, fa_dtype out, fa_mode mode, const float* d_init, void* hip_stream);
+
+/* The same for FA_TRIMMED: the trimmed mean (trim: FA_TRIM_MEDIAN or 0 <= 2 trim < D) of D client buckets
+ * resident on device `gpu` into d_out.  ctx may be NULL (then `gpu` is the HIP device).  Every argument is
+ * checked before any device call: D in 1..FA_TRIMMED_MAX_CLIENTS, trim, the dtype pair, and for n > 0 null
+ * pointers and element alignment; with n == 0 and valid arguments it returns FA_OK without touching a
+ * device.  Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
+int fa_trimmed_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, void* d_out,
+                      fa_dtype out, int trim, void* hip_stream);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

@@ -19,7 +19,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "lib", "libfa.so")
 
 F32, BF16, F16 = 0, 1, 2  # F16: IEEE binary16 (torch.float16 / np.float16)
-FEDAVG, LITERAL = 0, 1
+FEDAVG, LITERAL, TRIMMED = 0, 1, 2
+TRIM_MEDIAN = -1  # FA_TRIM_MEDIAN: the largest valid trim, (D-1)/2
+TRIMMED_MAX_CLIENTS = 128
 SHARD_RANGE, SHARD_CLIENT_RS, ACCUMULATE_ON_ARRIVAL, TEST_SHARED_DEVICE = 0x1, 0x2, 0x4, 0x100
 OK, ERR_ARG, ERR_HIP, ERR_NOMEM, ERR_STATE, ERR_NODEV, ERR_ALIGN, ERR_NCCL = 0, -1, -2, -3, -4, -5, -6, -7
 DTYPE_SIZE = {F32: 4, BF16: 2, F16: 2}
@@ -74,6 +76,8 @@ def lib():
         "fa_destroy": (None, [P]),
         "fa_bucket_define": (I, [P, I, S, I, I, I, I]),
         "fa_set_literal_divisor": (I, [P, I, F]),
+        "fa_set_trim": (I, [P, I, I]),
+        "fa_trimmed_device": (I, [P, I, P, I, S, I, P, I, I, P]),
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
         "fa_submit_gather": (I, [P, I, I, I, P, P, F]),
@@ -213,6 +217,15 @@ def reduce_device(clients, weights, n, in_dtype, out, out_dtype=F32, mode=FEDAVG
         raise ValueError("need one weight per client")
     check(lib().fa_reduce_device(ctx.handle if ctx is not None else None, gpu, arr, w.ctypes.data, D, n, in_dtype,
                                  _addr(out), out_dtype, mode, _addr(init), _stream(stream)))
+
+
+def trimmed_device(clients, n, in_dtype, out, out_dtype=F32, trim=TRIM_MEDIAN, stream=None, gpu=0, ctx=None):
+    """fa_trimmed_device: the coordinate-wise trimmed mean (trim=TRIM_MEDIAN: the median) of D device-resident
+    client buckets -> out (enqueued, not synchronized).  With n == 0 no device is touched: the feature probe."""
+    D = len(clients)
+    arr = (ctypes.c_void_p * D)(*[_addr(c) for c in clients])
+    check(lib().fa_trimmed_device(ctx.handle if ctx is not None else None, gpu, arr, D, n, in_dtype, _addr(out),
+                                  out_dtype, trim, _stream(stream)))
 
 
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
@@ -405,12 +418,18 @@ class Aggregator:
         self.handle = h
         self.parts = {}
 
-    def define(self, part_id, n, in_dtype=F32, out_dtype=F32, n_clients=1, mode=FEDAVG):
+    def define(self, part_id, n, in_dtype=F32, out_dtype=F32, n_clients=1, mode=FEDAVG, trim=None):
         check(lib().fa_bucket_define(self.handle, part_id, n, in_dtype, out_dtype, n_clients, mode))
         self.parts[part_id] = (n, in_dtype, out_dtype, n_clients, mode)
+        if trim is not None:
+            self.set_trim(trim, part_id)
 
     def set_divisor(self, divisor, part_id=-1):
         check(lib().fa_set_literal_divisor(self.handle, part_id, divisor))
+
+    def set_trim(self, trim, part_id=-1):
+        """fa_set_trim: the trim of a TRIMMED part (part_id < 0: the default of parts defined later)."""
+        check(lib().fa_set_trim(self.handle, part_id, trim))
 
     def submit(self, part_id, slot, host, weight=1.0, pinned=False):
         host = np.ascontiguousarray(host)

@@ -281,6 +281,7 @@ struct Part {
     int D = 0;
     fa_mode mode = FA_FEDAVG;
     float divisor = FA_DEFAULT_DIVISOR;
+    int trim = FA_TRIM_MEDIAN;     // FA_TRIMMED: as given to fa_set_trim (resolved against D at each reduction)
     bool rs = false;               // FA_SHARD_CLIENT_RS layout
     size_t npad = 0;               // rs: slot length (n padded to a multiple of G * 64)
     std::vector<size_t> off, cnt;  // per GPU: bucket elements held by its slots (range: its shard; rs: [0, n))
@@ -324,6 +325,7 @@ struct fa_ctx {
     int G = 1;
     int flags = 0;
     float divisor = FA_DEFAULT_DIVISOR;
+    int trim = FA_TRIM_MEDIAN;  // default of FA_TRIMMED parts defined later
     CtxTuning tuning;
     std::vector<GpuRes> gpu;
     std::map<int, Part> parts;
@@ -346,10 +348,22 @@ int ensure_scratch(fa_ctx* ctx, int g, size_t bytes) {
     return FA_OK;
 }
 
+// FA_TRIMMED: the trim a reduction over D clients uses (FA_TRIM_MEDIAN -> (D-1)/2), and its check.
+int resolved_trim(int trim, int D) { return trim == FA_TRIM_MEDIAN ? (D - 1) / 2 : trim; }
+int check_trim(int trim, int D) {
+    if (trim < -1 || (trim >= 0 && 2 * trim >= D))
+        return fail(FA_ERR_ARG, "trim %d does not fit D = %d clients (FA_TRIM_MEDIAN, or 0 <= trim with 2 trim < D)", trim, D);
+    return FA_OK;
+}
+float mode_arg(fa_mode mode, float divisor, int trim, int D) {
+    return mode == FA_TRIMMED ? (float)resolved_trim(trim, D) : divisor;
+}
+
 bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 // The device reduction for one GPU, shared by every entry: D clients (any D >= 1; more than kMaxClients
-// continue the chain from an fp32 accumulator in further passes) -> dst.
+// continue the chain from an fp32 accumulator in further passes) -> dst.  `divisor` is the mode's parameter:
+// FA_LITERAL's divisor, or FA_TRIMMED's resolved trim (mode_arg: a small integer, exact as a float).
 int reduce_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clients, const float* w, int D, size_t n,
               fa_dtype in, void* dst, fa_dtype out, fa_mode mode, float divisor, const float* init, hipStream_t s) {
     if (n == 0) return FA_OK;
@@ -369,7 +383,7 @@ int reduce_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clien
     if ((size_t)head > n) head = (int64_t)n;
     const int64_t nvec = (int64_t)(n - (size_t)head) / V;
     bool vec = true;
-    if (mode == FA_FEDAVG)
+    if (mode != FA_LITERAL)
         for (int k = 0; k < D; ++k) vec = vec && (((uintptr_t)clients[k] % 16) / si == phase);
     const size_t out_vec_bytes = (size_t)V * so;  // 16 or 32 (f32 out of 16-bit) or 8 (16-bit out of f32)
     vec = vec && ((uintptr_t)dst + (size_t)head * so) % std::min<size_t>(16, out_vec_bytes) == 0;
@@ -377,6 +391,13 @@ int reduce_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clien
 
     if (mode == FA_LITERAL) {
         FA_HIP(fa::launch_literal(clients[D - 1], in, dst, out, divisor, head, nvec, (int64_t)n, vec, tu, s));
+        return FA_OK;
+    }
+    if (mode == FA_TRIMMED) {
+        if (D > FA_TRIMMED_MAX_CLIENTS) return fail(FA_ERR_ARG, "trimmed mean of D = %d clients (at most %d)", D, FA_TRIMMED_MAX_CLIENTS);
+        fa::ClientTable t;
+        for (int k = 0; k < D; ++k) t.src[k] = clients[k];
+        FA_HIP(fa::launch_trimmed(t, D, in, out, (int)divisor, dst, head, nvec, (int64_t)n, vec, tu, s));
         return FA_OK;
     }
 
@@ -734,7 +755,9 @@ const char* device_visible(const void* ptr) {
 }
 
 bool host_read_part(const fa_ctx* ctx, const Part& p) {
-    return host_read_enabled() && ctx->G == 1 && !p.rs && !(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) &&
+    // trimmed parts are never kept host-side (fa.h): D PCIe reads per element feed a sort, not a chain
+    return host_read_enabled() && p.mode != FA_TRIMMED && ctx->G == 1 && !p.rs &&
+           !(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) &&
            p.npiece[0] == 1 && p.n > 0 && (size_t)p.D * p.n * dsize(p.in) <= kHostReadMax;
 }
 
@@ -910,7 +933,7 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
                     std::vector<const void*> ptrs;
                     for (int k = 0; k < p.D; ++k) ptrs.push_back(piece_ptr(p, g, k, j));
                     rc = reduce_on(ctx, g, ctx->tuning.tu, ptrs.data(), w, p.D, piece_cnt(p, g, j), p.in, dst, p.out,
-                                   FA_FEDAVG, p.divisor, nullptr, st);
+                                   p.mode, mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
                 }
             }
             if (rc || (rc = mark_done(ctx, p, g, st))) return rc;
@@ -1234,7 +1257,7 @@ int finalize_impl(fa_ctx* ctx, int part_id, const Gather& dst, bool pinned) {
     Part* p;
     int rc = check_part(ctx, part_id, &p);
     if (rc) return rc;
-    if (p->mode == FA_FEDAVG && p->n_submitted != p->D)
+    if (p->mode != FA_LITERAL && p->n_submitted != p->D)
         return fail(FA_ERR_STATE, "part %d: %d of %d clients submitted", part_id, p->n_submitted, p->D);
     if (p->n_submitted == 0) return fail(FA_ERR_STATE, "part %d: nothing submitted", part_id);
     if ((rc = dst.check("host destination"))) return rc;
@@ -1665,9 +1688,17 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
     if (!dvalid(in) || !dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
     FA_PAIR(in, out);
-    if (mode != FA_FEDAVG && mode != FA_LITERAL) return fail(FA_ERR_ARG, "bad mode");
+    if (mode != FA_FEDAVG && mode != FA_LITERAL && mode != FA_TRIMMED) return fail(FA_ERR_ARG, "bad mode");
     if (n_clients < 1) return fail(FA_ERR_ARG, "n_clients must be >= 1");
     const bool rs = (ctx->flags & FA_SHARD_CLIENT_RS) != 0;
+    if (mode == FA_TRIMMED) {
+        if (n_clients > FA_TRIMMED_MAX_CLIENTS)
+            return fail(FA_ERR_ARG, "a trimmed part holds at most %d clients, got %d", FA_TRIMMED_MAX_CLIENTS, n_clients);
+        if (rs)
+            return fail(FA_ERR_ARG, "a trimmed part needs every client's value of an element on one GPU: not on an "
+                                    "FA_SHARD_CLIENT_RS context (use FA_SHARD_RANGE)");
+        if (int rc = check_trim(ctx->trim, n_clients)) return rc;
+    }
     auto it = ctx->parts.find(part_id);
     if (it != ctx->parts.end()) {
         free_part(ctx, it->second);
@@ -1680,6 +1711,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     p.D = n_clients;
     p.mode = mode;
     p.divisor = ctx->divisor;
+    p.trim = ctx->trim;
     p.rs = rs;
     p.w.assign((size_t)n_clients, 0.0f);
     p.submitted.assign((size_t)n_clients, 0);
@@ -1783,6 +1815,22 @@ int fa_set_literal_divisor(fa_ctx* ctx, int part_id, float divisor) {
     return FA_OK;
 }
 
+int fa_set_trim(fa_ctx* ctx, int part_id, int trim) {
+    g_err.clear();
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (trim < -1) return fail(FA_ERR_ARG, "trim %d: FA_TRIM_MEDIAN (-1) or >= 0", trim);
+    if (part_id < 0) {
+        ctx->trim = trim;
+        return FA_OK;
+    }
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc || (rc = check_trim(trim, p->D))) return rc;
+    p->trim = trim;
+    p->ready = false;
+    return FA_OK;
+}
+
 static int submit_flat(fa_ctx* ctx, int part_id, int client_slot, const void* host_src, float weight, bool pinned) {
     Part* p;
     int rc = check_part(ctx, part_id, &p);
@@ -1863,7 +1911,8 @@ int fa_reduce_parts(fa_ctx* ctx, int n_parts, const int* part_ids, const float* 
         Part* p;
         int rc = check_part(ctx, part_ids[i], &p);
         if (rc) return rc;
-        if (p->mode == FA_FEDAVG && p->n_submitted != p->D && !(h_weights && h_weights[i]))
+        if (p->mode == FA_TRIMMED ? p->n_submitted != p->D
+                                  : p->mode == FA_FEDAVG && p->n_submitted != p->D && !(h_weights && h_weights[i]))
             return fail(FA_ERR_STATE, "part %d: %d of %d clients submitted", part_ids[i], p->n_submitted, p->D);
     }
     return reduce_parts_impl(ctx, n_parts, part_ids, h_weights, static_cast<hipStream_t>(hip_stream));
@@ -2110,6 +2159,7 @@ int fa_reduce_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const f
     if (D < 1) return fail(FA_ERR_ARG, "D must be >= 1");
     if (!dvalid(in) || !dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
     FA_PAIR(in, out);
+    if (mode == FA_TRIMMED) return fail(FA_ERR_ARG, "fa_reduce_device has no trim argument: use fa_trimmed_device");
     if (mode != FA_FEDAVG && mode != FA_LITERAL) return fail(FA_ERR_ARG, "bad mode");
     if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -2119,6 +2169,32 @@ int fa_reduce_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const f
     const CtxTuning tu = ctx ? ctx->tuning : defaults();
     return reduce_on(ctx, ctx ? gpu : 0, tu.tu, d_clients, h_weights, D, n, in, d_out, out, mode,
                      ctx ? ctx->divisor : FA_DEFAULT_DIVISOR, d_init, s);
+}
+
+int fa_trimmed_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, void* d_out,
+                      fa_dtype out, int trim, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (D < 1 || D > FA_TRIMMED_MAX_CLIENTS) return fail(FA_ERR_ARG, "D = %d: a trimmed mean takes 1..%d clients", D, FA_TRIMMED_MAX_CLIENTS);
+    if (int rc = check_trim(trim, D)) return rc;
+    if (!dvalid(in) || !dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
+    FA_PAIR(in, out);
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) return FA_OK;
+    if (!d_clients) return fail(FA_ERR_ARG, "client array is null");
+    for (int k = 0; k < D; ++k) {
+        if (!d_clients[k]) return fail(FA_ERR_ARG, "client pointer %d is null", k);
+        if (!aligned(d_clients[k], dsize(in))) return fail(FA_ERR_ALIGN, "client %d not %zu-byte aligned", k, dsize(in));
+    }
+    if (!d_out) return fail(FA_ERR_ARG, "output pointer is null");
+    if (!aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const int dev = ctx ? ctx->gpu[(size_t)gpu].dev : gpu;
+    if (!s && ctx) s = ctx->gpu[(size_t)gpu].compute;
+    DeviceGuard dg(dev);
+    const CtxTuning tu = ctx ? ctx->tuning : defaults();
+    return reduce_on(ctx, ctx ? gpu : 0, tu.tu, d_clients, nullptr, D, n, in, d_out, out, FA_TRIMMED,
+                     mode_arg(FA_TRIMMED, 0.0f, trim, D), nullptr, s);
 }
 
 int fa_sync_device(fa_ctx* ctx, int gpu, void* const* d_clients, const float* h_weights, int D, size_t n, fa_dtype dt,

@@ -89,6 +89,11 @@ struct ChainPlan {
 ChainPlan plan_chain(fa_dtype in, fa_dtype out, int64_t nvec, int nc, bool vector_ok, const Tuning& tu, int cus);
 hipError_t launch_literal(const void* x, fa_dtype in, void* dst, fa_dtype out, float divisor, int64_t head,
                           int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);
+// Coordinate-wise trimmed mean over t.src[0..nc), 1 <= nc <= FA_TRIMMED_MAX_CLIENTS, 0 <= 2 trim < nc (fa.h "FA_TRIMMED"):
+// sorted positions [trim, nc - trim) of every element, added ascending from +0, divided by nc - 2 trim.
+// Weights are not read.  fa_trimmed.hip.
+hipError_t launch_trimmed(const ClientTable& t, int nc, fa_dtype in, fa_dtype out, int trim, void* dst, int64_t head,
+                          int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, int64_t head, int64_t nvec,
                        int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);

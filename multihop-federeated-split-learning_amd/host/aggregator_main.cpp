@@ -21,7 +21,9 @@
 //
 // --mode literal reproduces the reference's arithmetic bit-for-bit
 // (fl(fl(x_last + x_last) / 1000)); --mode fedavg (default) is
-// the north star's weighted mean (weights n_k/N from --samples, else 1/D).
+// the north star's weighted mean (weights n_k/N from --samples, else 1/D);
+// --mode trimmed [--trim T] / --mode median is the coordinate-wise trimmed
+// mean (FA_TRIMMED, fa.h), which T owners sending NaN or inf do not reach.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -49,6 +51,10 @@ struct Options {
     int gpus = 1, rounds = -1, port_base = 8079, last_layers = -1;
     fa_mode mode = FA_FEDAVG;
     float divisor = 1000.0f;  // kTrainSize_10, aggregator.cpp:48
+    // --mode trimmed [--trim T] / --mode median: FA_TRIMMED, the coordinate-wise trimmed mean (fa.h); the
+    // median is its largest trim, (D-1)/2
+    int trim = FA_TRIM_MEDIAN;
+    bool trim_given = false, median = false;
     bool discover = false, pinned = true;
     bool rs = false;     // --layout rs: clients dealt to the GPUs, RCCL reduce-scatter of fp32 partials
     bool eager = false;  // --eager: accumulate on arrival (the chain advances with the in-order receipts)
@@ -73,11 +79,16 @@ struct Options {
 };
 
 void usage() {
-    std::cerr << "usage: fa_aggregator -i ID -d DATA_OWNERS -c COMPUTE_NODES [--mode fedavg|literal] [--gpus G]\n"
+    std::cerr << "usage: fa_aggregator -i ID -d DATA_OWNERS -c COMPUTE_NODES [--mode fedavg|literal|trimmed|median]\n"
+                 "       [--trim T] [--gpus G]\n"
                  "       [--rounds R] [--port-base P] [--discover] [--link-mbps M] [--samples id:n,...]\n"
                  "       [--divisor K] [--last-layers L] [--no-pinned] [--layout range|rs] [--rs-chunks C]\n"
                  "       [--eager] [--stall-report S] [--receipt-timeout S] [--rx-concurrency K]\n"
                  "       [--senders S] [--stream-min-bytes N] [--crc gpu|host] [--test-shared-device]\n"
+                 "--mode trimmed: per element the T lowest and T highest of the owners' values are dropped and the\n"
+                 "rest averaged (2T < DATA_OWNERS <= 128; without --trim, and with --mode median, the median), so up\n"
+                 "to T owners that send NaN, inf or huge values change no reply; --samples is ignored; not with\n"
+                 "--layout rs.\n"
                  "A bucket takes the dtype of its first receipt's parameters (all fp32, all bf16 or all fp16, by\n"
                  "their storage type) and is reduced and replied in it; a later receipt of another size or dtype\n"
                  "ends the process (exit 1).\n";
@@ -126,7 +137,12 @@ bool parse_args(int argc, char** argv, Options* o) {
             std::string m = val("--mode");
             if (m == "literal") o->mode = FA_LITERAL;
             else if (m == "fedavg") o->mode = FA_FEDAVG;
+            else if (m == "trimmed") o->mode = FA_TRIMMED;
+            else if (m == "median") o->mode = FA_TRIMMED, o->median = true;
             else return false;
+        } else if (a == "--trim") {
+            o->trim = std::atoi(val("--trim"));
+            o->trim_given = true;
         } else if (a == "--samples") {
             std::stringstream ss(val("--samples"));
             std::string tok;
@@ -141,6 +157,25 @@ bool parse_args(int argc, char** argv, Options* o) {
             std::cerr << "unknown argument " << a << "\n";
             return false;
         }
+    }
+    if (o->trim_given && (o->mode != FA_TRIMMED || o->median)) {
+        std::cerr << "--trim goes with --mode trimmed\n";
+        return false;
+    }
+    if (o->mode == FA_TRIMMED) {
+        if (o->rs) {
+            std::cerr << "--mode trimmed|median needs every owner's value of an element on one GPU: not with --layout rs\n";
+            return false;
+        }
+        if (o->data_owners > FA_TRIMMED_MAX_CLIENTS) {
+            std::cerr << "--mode trimmed|median takes at most " << FA_TRIMMED_MAX_CLIENTS << " data owners\n";
+            return false;
+        }
+        if (o->trim_given && (o->trim < 0 || 2 * o->trim >= o->data_owners)) {
+            std::cerr << "--trim " << o->trim << ": 0 <= 2T < " << o->data_owners << " data owners\n";
+            return false;
+        }
+        if (!o->trim_given) o->trim = o->data_owners >= 1 ? (o->data_owners - 1) / 2 : 0;
     }
     return o->data_owners >= 1 && o->stall_report_s > 0 && o->receipt_timeout_s >= 0;
 }
@@ -189,6 +224,7 @@ public:
             FA_CHECK(fa_create(&ctx_, o.gpus, flags));
         }
         FA_CHECK(fa_set_literal_divisor(ctx_, -1, o.divisor));
+        if (o.mode == FA_TRIMMED) FA_CHECK(fa_set_trim(ctx_, -1, o.trim));
         if (o.rs_chunks > 0) {
             fa_tuning t{};
             t.rs_chunks = o.rs_chunks;
@@ -643,6 +679,8 @@ int main(int argc, char** argv) {
         usage();
         return 2;
     }
+    if (o.mode == FA_TRIMMED && !o.samples.empty())
+        std::cerr << "[aggregator] warning: --samples is ignored with --mode trimmed|median (the rule has no weights)\n";
     // pinned frame buffers: receipts DMA'd from, replies DMA'd into -- small ones too (from 4 KiB): a small
     // model's receipt then goes to its slot by one DMA instead of a copy into the staging chunks first, and
     // its reply comes back the same way (BASELINE C1)
@@ -677,6 +715,9 @@ int main(int argc, char** argv) {
               << refactor.start << " end " << refactor.end << " -> " << L << " last-part layer(s)\n";
     Aggregator agg(o, &net, refactor.data_owners);
 
+    // the round line names the rule only where it is not a mean (lines of the other modes stay as they were)
+    const std::string mode_tail =
+        o.mode == FA_TRIMMED ? ",\"mode\":\"trimmed\",\"trim\":" + std::to_string(o.trim) : std::string();
     for (int round = 0; o.rounds < 0 || round < o.rounds; ++round) {
         // phase 1: model part 1 from every data owner (aggregator.cpp:59-93)
         // Receipt accounting (the reference counts raw receipts, aggregator.cpp:59-92 / :112-149): a phase
@@ -749,10 +790,11 @@ int main(int argc, char** argv) {
                "\"phase2\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,\"layers\":%d,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f,\"send_s\":%.6f},"
                "\"send_failures\":%llu,\"stale_dropped\":%llu,\"ignored\":%llu,\"replaced\":%llu,"
-               "\"clock_back\":%llu,\"streamed\":%llu,\"stream_fallbacks\":%llu,\"streamed_bytes\":%llu}\n",
+               "\"clock_back\":%llu,\"streamed\":%llu,\"stream_fallbacks\":%llu,\"streamed_bytes\":%llu%s}\n",
                round, recv1, red1, in1, s1.absorb_s, s1.finalize_s, s1.frame_s, recv2, red2, in2, L, s2.absorb_s,
                s2.finalize_s, s2.frame_s, send2, (unsigned long long)net.send_failures(), agg.stale_dropped(), agg.ignored(),
-               agg.replaced(), agg.clock_back(), agg.streamed(), agg.stream_fallbacks(), agg.streamed_bytes());
+               agg.replaced(), agg.clock_back(), agg.streamed(), agg.stream_fallbacks(), agg.streamed_bytes(),
+               mode_tail.c_str());
         fflush(stdout);
     }
     net.stop();

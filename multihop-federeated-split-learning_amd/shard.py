@@ -27,6 +27,9 @@ persistent grid (the default walk for large buckets) holds on every CU for its
 whole launch, so run these layouts with the one-shot walk:
 ``fa.set_tuning(walk=OVERLAP_WALK)`` (bench.py does; the in-process
 FA_SHARD_CLIENT_RS layout of libfa.so does the same by itself).
+
+FA_TRIMMED (the coordinate-wise trimmed mean / median) is out of scope here: this one-process-per-GPU path
+reduces FedAvg buckets only.
 """
 import numpy as np
 
