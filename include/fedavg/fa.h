@@ -45,6 +45,33 @@
  *              fl(fl(+0 + x)/1).  D <= FA_TRIMMED_MAX_CLIENTS: the sort runs on one GPU in
  *              one pass.  Added without a new FA_ABI_VERSION: fa_trimmed_device(NULL, 0, ptrs, D, 0, ...)
  *              touches no device and answers FA_OK -- that is how a caller probes for it.
+ *   Server optimizer (fa_set_server_opt, fa_server_opt_device): an element-wise update rule applied to the
+ *              round's aggregate (Reddi et al., "Adaptive Federated Optimization", Algorithm 2: FedAvgM,
+ *              FedAdagrad, FedAdam, FedYogi), specified bit for bit.  Per element, a is the part's fp32
+ *              aggregate: the ordered FMA chain for FA_FEDAVG, step 4 of the rule above for FA_TRIMMED, in
+ *              both cases before any rounding to a 16-bit output.  The state is x (the global model, an
+ *              fp32 master also for bf16 / fp16 buckets), m and v, all fp32, kept on the GPU across rounds.
+ *              The parameters are the floats lr, beta1, beta2, tau; on the host, in fp32,
+ *              c1 = fl(1 - beta1), c2 = fl(1 - beta2).  Every operation below is one IEEE fp32 operation
+ *              rounded to nearest-even; there is no fused multiply-add anywhere in the stage; division and
+ *              square root are correctly rounded; subnormals are kept.
+ *                d  = fl(a - x)
+ *                FA_OPT_MOMENTUM (FedAvgM):  m' = fl(fl(beta1 m) + d);  x' = fl(x + fl(lr m'));
+ *                                            v is not read, written or allocated
+ *                FA_OPT_ADAGRAD / ADAM / YOGI:  m' = fl(fl(beta1 m) + fl(c1 d));  q = fl(d d)
+ *                  ADAGRAD: v' = fl(v + q)
+ *                  ADAM:    v' = fl(fl(beta2 v) + fl(c2 q))
+ *                  YOGI:    u = fl(c2 q); s = fl(v - q);
+ *                           v' = fl(v - u) if s > 0, fl(v + u) if s < 0, v if s == 0, a quiet NaN if s is NaN
+ *                  x' = fl(x + fl(fl(lr m') / fl(fl(sqrt(v')) + tau)))
+ *                out = x' (a bf16 / fp16 output: x' rounded once to nearest-even, as for FA_FEDAVG)
+ *              No bias correction, as in the paper.  NaN and inf propagate (NaN payloads unspecified);
+ *              robustness comes from combining the stage with FA_TRIMMED.
+ *              Bootstrap: the first reduction of a part that has no master (none was set with
+ *              fa_server_opt_set_state and none was stepped yet) does x' = a, m' = +0, v' = +0, out = a
+ *              rounded to the out dtype; `steps` stays 0.  Every later reduction is one step and adds 1 to
+ *              `steps`.  Added without a new FA_ABI_VERSION: fa_server_opt_device with n == 0 touches no
+ *              device and answers FA_OK -- that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -283,6 +310,48 @@ int fa_reduce_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const f
  * device.  Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
 int fa_trimmed_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, void* d_out,
                       fa_dtype out, int trim, void* hip_stream);
+
+/* Server optimizer: what is done with the round's aggregate (the header comment, "Server optimizer"). */
+typedef enum { FA_OPT_NONE = 0, FA_OPT_MOMENTUM = 1, FA_OPT_ADAGRAD = 2, FA_OPT_ADAM = 3, FA_OPT_YOGI = 4 } fa_opt_rule;
+typedef struct {
+    int rule;                    /* an fa_opt_rule */
+    float lr, beta1, beta2, tau; /* beta2: FA_OPT_ADAM / FA_OPT_YOGI; tau: the adaptive rules */
+} fa_server_opt;
+/* Gives a part a server-optimizer stage (part_id >= 0), or sets the context default that FA_FEDAVG and
+ * FA_TRIMMED parts defined later take (part_id < 0; FA_LITERAL parts ignore it).  Calling again with the same
+ * rule keeps the state and changes the hyperparameters (a decaying server learning rate); a different rule
+ * keeps x and zeroes m and v (a round already reduced stays reduced: one step per round); NULL or
+ * FA_OPT_NONE removes the stage and frees its state (a part that took the context default on an
+ * FA_ACCUMULATE_ON_ARRIVAL context was defined non-eager and stays so).  The state is per
+ * GPU and covers the elements that GPU's output covers (a range shard: [off, off + cnt)): 2 or 3 fp32 arrays
+ * (plus an fp32 aggregate buffer for a 16-bit output) that live until the part or the context goes;
+ * FA_ERR_NOMEM when they cannot be allocated.  FA_ERR_ARG, naming the field: rule outside 0..4, lr not finite
+ * or < 0, beta1 outside [0, 1), beta2 outside [0, 1) (Adam, Yogi), tau not finite or <= 0 (the adaptive
+ * rules), an FA_LITERAL part, an FA_SHARD_CLIENT_RS context (its aggregate is not bit-specified).
+ * The step happens once per reducing call: fa_reduce_part, fa_reduce_parts (its own launch, never in the
+ * segment table) or the fa_finalize* that reduces the round; each reduces in fp32 (an f32 part into its
+ * output, a 16-bit part into an fp32 buffer of its own) and runs the stage on the same stream into the part's
+ * output.  On such a part fa_reduce_part needs every client submitted and marks the round reduced, so a
+ * following fa_finalize* only copies out; calling it twice takes two steps.  The part is never kept host-side
+ * (fa_bucket_host_read says 0) and FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager.  fa_sync_part keeps its
+ * meaning and takes no step; fa_copy_output, fa_output_crc32, range shards and range pieces read the part's
+ * output and work unchanged. */
+int fa_set_server_opt(fa_ctx* ctx, int part_id, const fa_server_opt* opt);
+/* The stage's state as whole-bucket host arrays of n fp32, scattered to / gathered from the GPUs' shards; any
+ * pointer may be NULL to skip that array, v is ignored for FA_OPT_MOMENTUM.  set with an x gives the part a
+ * master (no bootstrap); get waits for the part's pending work (not when only steps is asked for).  FA_ERR_STATE on a part without a stage. */
+/* The stage a part has (rule FA_OPT_NONE: none), or with part_id < 0 the context default. */
+int fa_get_server_opt(fa_ctx* ctx, int part_id, fa_server_opt* opt);
+int fa_server_opt_set_state(fa_ctx* ctx, int part_id, const float* x, const float* m, const float* v, uint64_t steps);
+int fa_server_opt_get_state(fa_ctx* ctx, int part_id, float* x, float* m, float* v, uint64_t* steps);
+/* One step on raw device pointers (no bootstrap): d_avg, d_x, d_m, d_v of n fp32 on device `gpu`; d_v may be
+ * NULL for FA_OPT_MOMENTUM; d_out (n of `out`) may be NULL (states only) or d_avg itself for FA_F32.  ctx may
+ * be NULL (then `gpu` is the HIP device).  Every argument is checked before any device call: the rule (not
+ * FA_OPT_NONE) and hyperparameters as above, the out dtype, and for n > 0 null pointers and element alignment
+ * (FA_ERR_ALIGN); with n == 0 and valid arguments it returns FA_OK without touching a device.  Async on
+ * hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
+int fa_server_opt_device(fa_ctx* ctx, int gpu, const fa_server_opt* opt, const float* d_avg, float* d_x, float* d_m,
+                         float* d_v, size_t n, void* d_out, fa_dtype out, void* hip_stream);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

@@ -22,6 +22,8 @@ F32, BF16, F16 = 0, 1, 2  # F16: IEEE binary16 (torch.float16 / np.float16)
 FEDAVG, LITERAL, TRIMMED = 0, 1, 2
 TRIM_MEDIAN = -1  # FA_TRIM_MEDIAN: the largest valid trim, (D-1)/2
 TRIMMED_MAX_CLIENTS = 128
+# fa_opt_rule: the server-optimizer stage (FedAvgM, FedAdagrad, FedAdam, FedYogi; fa.h "Server optimizer")
+OPT_NONE, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 0, 1, 2, 3, 4
 SHARD_RANGE, SHARD_CLIENT_RS, ACCUMULATE_ON_ARRIVAL, TEST_SHARED_DEVICE = 0x1, 0x2, 0x4, 0x100
 OK, ERR_ARG, ERR_HIP, ERR_NOMEM, ERR_STATE, ERR_NODEV, ERR_ALIGN, ERR_NCCL = 0, -1, -2, -3, -4, -5, -6, -7
 DTYPE_SIZE = {F32: 4, BF16: 2, F16: 2}
@@ -42,6 +44,11 @@ class _Tuning(ctypes.Structure):
                 ("load_policy", ctypes.c_int), ("store_policy", ctypes.c_int), ("slot_skew", ctypes.c_int),
                 ("walk", ctypes.c_int), ("rs_chunks", ctypes.c_int), ("piece_span_kib", ctypes.c_int),
                 ("piece_split_kib", ctypes.c_int)]
+
+
+class _ServerOpt(ctypes.Structure):
+    _fields_ = [("rule", ctypes.c_int), ("lr", ctypes.c_float), ("beta1", ctypes.c_float),
+                ("beta2", ctypes.c_float), ("tau", ctypes.c_float)]
 
 
 def build():
@@ -78,6 +85,11 @@ def lib():
         "fa_set_literal_divisor": (I, [P, I, F]),
         "fa_set_trim": (I, [P, I, I]),
         "fa_trimmed_device": (I, [P, I, P, I, S, I, P, I, I, P]),
+        "fa_set_server_opt": (I, [P, I, ctypes.POINTER(_ServerOpt)]),
+        "fa_get_server_opt": (I, [P, I, ctypes.POINTER(_ServerOpt)]),
+        "fa_server_opt_set_state": (I, [P, I, P, P, P, U64]),
+        "fa_server_opt_get_state": (I, [P, I, P, P, P, ctypes.POINTER(U64)]),
+        "fa_server_opt_device": (I, [P, I, ctypes.POINTER(_ServerOpt), P, P, P, P, S, P, I, P]),
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
         "fa_submit_gather": (I, [P, I, I, I, P, P, F]),
@@ -226,6 +238,17 @@ def trimmed_device(clients, n, in_dtype, out, out_dtype=F32, trim=TRIM_MEDIAN, s
     arr = (ctypes.c_void_p * D)(*[_addr(c) for c in clients])
     check(lib().fa_trimmed_device(ctx.handle if ctx is not None else None, gpu, arr, D, n, in_dtype, _addr(out),
                                   out_dtype, trim, _stream(stream)))
+
+
+def server_opt_device(avg, x, m, v, n, out, out_dtype=F32, rule=OPT_ADAM, lr=1.0, beta1=0.9, beta2=0.99, tau=1e-3,
+                      stream=None, gpu=0, ctx=None):
+    """fa_server_opt_device: one server-optimizer step on device-resident fp32 arrays -- the aggregate `avg` and
+    the state x, m, v (v=None for OPT_MOMENTUM) -- writing the state in place and x' to `out` in out_dtype
+    (None: states only; `avg` itself for F32).  Enqueued, not synchronized.  With n == 0 no device is touched:
+    the feature probe."""
+    opt = _ServerOpt(rule, lr, beta1, beta2, tau)
+    check(lib().fa_server_opt_device(ctx.handle if ctx is not None else None, gpu, ctypes.byref(opt), _addr(avg),
+                                     _addr(x), _addr(m), _addr(v), n, _addr(out), out_dtype, _stream(stream)))
 
 
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
@@ -430,6 +453,50 @@ class Aggregator:
     def set_trim(self, trim, part_id=-1):
         """fa_set_trim: the trim of a TRIMMED part (part_id < 0: the default of parts defined later)."""
         check(lib().fa_set_trim(self.handle, part_id, trim))
+
+    def set_server_opt(self, rule, lr=0.0, beta1=0.9, beta2=0.99, tau=1e-3, part_id=-1):
+        """fa_set_server_opt: the server-optimizer stage of a part (part_id < 0: the default of FEDAVG and
+        TRIMMED parts defined later).  The same rule again changes only the hyperparameters; another rule
+        keeps x and zeroes m and v; OPT_NONE removes the stage."""
+        opt = _ServerOpt(rule, lr, beta1, beta2, tau)
+        check(lib().fa_set_server_opt(self.handle, part_id, ctypes.byref(opt)))
+
+    def server_opt(self, part_id=-1):
+        """fa_get_server_opt: (rule, lr, beta1, beta2, tau) of the part's stage (rule OPT_NONE: none), or of
+        the context default (part_id < 0)."""
+        opt = _ServerOpt()
+        check(lib().fa_get_server_opt(self.handle, part_id, ctypes.byref(opt)))
+        return opt.rule, opt.lr, opt.beta1, opt.beta2, opt.tau
+
+    def server_opt_state(self, part_id):
+        """fa_server_opt_get_state: (x, m, v, steps) of the part's stage as whole-bucket fp32 numpy arrays
+        (v is None for OPT_MOMENTUM, which has none)."""
+        n = self.parts[part_id][0]
+        x, m = np.empty(n, np.float32), np.empty(n, np.float32)
+        v = None if self.server_opt(part_id)[0] == OPT_MOMENTUM else np.empty(n, np.float32)
+        steps = ctypes.c_uint64()
+        check(lib().fa_server_opt_get_state(self.handle, part_id, x.ctypes.data, m.ctypes.data,
+                                            None if v is None else v.ctypes.data, ctypes.byref(steps)))
+        return x, m, v, steps.value
+
+    def set_server_opt_state(self, part_id, x=None, m=None, v=None, steps=None):
+        """fa_server_opt_set_state: scatter whole-bucket fp32 arrays into the stage's state (None: leave that
+        array as it is); with an x the part has a master, so its next reduction is a step, not the bootstrap.
+        steps=None keeps the count."""
+        n = self.parts[part_id][0]
+        arrs = []
+        for a in (x, m, v):
+            if a is not None:
+                a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1))
+                if a.size != n:
+                    raise ValueError("bucket %d holds %d elements, got %d" % (part_id, n, a.size))
+            arrs.append(a)
+        if steps is None:
+            cur = ctypes.c_uint64()
+            check(lib().fa_server_opt_get_state(self.handle, part_id, None, None, None, ctypes.byref(cur)))
+            steps = cur.value
+        check(lib().fa_server_opt_set_state(self.handle, part_id, *[None if a is None else a.ctypes.data for a in arrs],
+                                            int(steps)))
 
     def submit(self, part_id, slot, host, weight=1.0, pinned=False):
         host = np.ascontiguousarray(host)

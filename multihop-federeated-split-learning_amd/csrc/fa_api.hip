@@ -317,6 +317,13 @@ struct Part {
     };
     std::vector<std::vector<HostSeg>> host_src;
     int n_host = 0;  // slots whose receipt is kept host-side this round
+    // Server-optimizer stage (fa.h "Server optimizer"; opt.rule == FA_OPT_NONE: none).  Per GPU the fp32 state
+    // over its cnt elements (ov only for the adaptive rules) and, for a 16-bit output, the fp32 buffer the
+    // round's aggregate is reduced into; each its own allocation, freed with the stage or the part.
+    fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};
+    std::vector<float*> ox, om, ov, oavg;
+    bool opt_master = false;  // x holds a model (set, or bootstrapped): the next reduction is a step
+    uint64_t opt_steps = 0;
 };
 
 }  // namespace
@@ -326,6 +333,7 @@ struct fa_ctx {
     int flags = 0;
     float divisor = FA_DEFAULT_DIVISOR;
     int trim = FA_TRIM_MEDIAN;  // default of FA_TRIMMED parts defined later
+    fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};  // default stage of FedAvg / trimmed parts defined later
     CtxTuning tuning;
     std::vector<GpuRes> gpu;
     std::map<int, Part> parts;
@@ -360,6 +368,46 @@ float mode_arg(fa_mode mode, float divisor, int trim, int D) {
 }
 
 bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
+
+// ------------------------------------------------------------------ server optimizer
+
+inline bool opt_adaptive(int rule) { return rule == FA_OPT_ADAGRAD || rule == FA_OPT_ADAM || rule == FA_OPT_YOGI; }
+inline bool finite_f(float f) { return f - f == 0.0f; }
+
+// The refusals of fa_set_server_opt / fa_server_opt_device, naming the field.
+int check_opt(const fa_server_opt& o) {
+    if (o.rule < FA_OPT_NONE || o.rule > FA_OPT_YOGI) return fail(FA_ERR_ARG, "server opt: rule %d outside 0..4", o.rule);
+    if (o.rule == FA_OPT_NONE) return FA_OK;
+    if (!finite_f(o.lr) || o.lr < 0.0f) return fail(FA_ERR_ARG, "server opt: lr %g must be finite and >= 0", (double)o.lr);
+    if (!(o.beta1 >= 0.0f && o.beta1 < 1.0f)) return fail(FA_ERR_ARG, "server opt: beta1 %g outside [0, 1)", (double)o.beta1);
+    if ((o.rule == FA_OPT_ADAM || o.rule == FA_OPT_YOGI) && !(o.beta2 >= 0.0f && o.beta2 < 1.0f))
+        return fail(FA_ERR_ARG, "server opt: beta2 %g outside [0, 1)", (double)o.beta2);
+    if (opt_adaptive(o.rule) && (!finite_f(o.tau) || !(o.tau > 0.0f)))
+        return fail(FA_ERR_ARG, "server opt: tau %g must be finite and > 0", (double)o.tau);
+    return FA_OK;
+}
+
+fa::OptHyper opt_hyper(const fa_server_opt& o) {
+    // c1, c2 in fp32 on the host (volatile: one rounded fp32 subtraction each, whatever the host's float mode)
+    volatile float c1 = 1.0f - o.beta1, c2 = 1.0f - o.beta2;
+    return fa::OptHyper{o.lr, o.beta1, o.beta2, o.tau, c1, c2};
+}
+
+// One launch of the stage on the current device: `rule` (or fa::kOptBoot) over n elements, split as reduce_on
+// splits a bucket -- the vector form where avg, the state and the output share one 16-byte phase.
+int opt_on(const fa::Tuning& tu, int rule, const fa_server_opt& o, const float* avg, float* x, float* m, float* v,
+           size_t n, void* out, fa_dtype odt, hipStream_t s) {
+    if (n == 0) return FA_OK;
+    const size_t phase = ((uintptr_t)avg % 16) / 4;
+    int64_t head = (int64_t)((4 - phase) % 4);
+    if ((size_t)head > n) head = (int64_t)n;
+    const int64_t nvec = (int64_t)(n - (size_t)head) / 4;
+    bool vec = ((uintptr_t)x % 16) / 4 == phase && ((uintptr_t)m % 16) / 4 == phase;
+    if (v) vec = vec && ((uintptr_t)v % 16) / 4 == phase;
+    if (out) vec = vec && ((uintptr_t)out + (size_t)head * dsize(odt)) % (4 * dsize(odt)) == 0;
+    FA_HIP(fa::launch_server_opt(rule, opt_hyper(o), avg, x, m, v, out, odt, head, nvec, (int64_t)n, vec, tu, s));
+    return FA_OK;
+}
 
 // The device reduction for one GPU, shared by every entry: D clients (any D >= 1; more than kMaxClients
 // continue the chain from an fp32 accumulator in further passes) -> dst.  `divisor` is the mode's parameter:
@@ -560,7 +608,24 @@ int check_part(fa_ctx* ctx, int part_id, Part** out) {
     return FA_OK;
 }
 
+// Frees the stage's arrays on every GPU (hipFree waits for the device's pending work) and forgets the master.
+void free_opt(fa_ctx* ctx, Part& p) {
+    for (size_t g = 0; g < p.ox.size(); ++g) {
+        DeviceGuard dg(ctx->gpu[g].dev);
+        for (auto* arr : {&p.ox, &p.om, &p.ov, &p.oavg})
+            if (g < arr->size() && (*arr)[g]) (void)hipFree((*arr)[g]);
+    }
+    p.ox.clear();
+    p.om.clear();
+    p.ov.clear();
+    p.oavg.clear();
+    p.opt = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};
+    p.opt_master = false;
+    p.opt_steps = 0;
+}
+
 void free_part(fa_ctx* ctx, Part& p) {
+    free_opt(ctx, p);
     for (size_t g = 0; g < p.pool.size(); ++g) {
         DeviceGuard dg(ctx->gpu[g].dev);
         if (p.pool[g]) (void)hipFree(p.pool[g]);
@@ -756,7 +821,8 @@ const char* device_visible(const void* ptr) {
 
 bool host_read_part(const fa_ctx* ctx, const Part& p) {
     // trimmed parts are never kept host-side (fa.h): D PCIe reads per element feed a sort, not a chain
-    return host_read_enabled() && p.mode != FA_TRIMMED && ctx->G == 1 && !p.rs &&
+    // nor parts with a server-optimizer stage: their round ends in a step on the device state
+    return host_read_enabled() && p.mode != FA_TRIMMED && p.opt.rule == FA_OPT_NONE && ctx->G == 1 && !p.rs &&
            !(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) &&
            p.npiece[0] == 1 && p.n > 0 && (size_t)p.D * p.n * dsize(p.in) <= kHostReadMax;
 }
@@ -925,6 +991,21 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
             if (rc) return rc;
             for (int j = 0; j < p.npiece[(size_t)g] && !rc; ++j) {  // one launch per piece, in order
                 void* dst = static_cast<char*>(p.dout[(size_t)g]) + piece_lo(p, g, j) * dsize(p.out);
+                if (p.opt.rule != FA_OPT_NONE) {
+                    // the fp32 aggregate (an f32 part: in its output, where the stage then runs in place), then
+                    // one step -- or the bootstrap of a part without a master -- on the same stream
+                    const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
+                    float* avg = p.out == FA_F32 ? static_cast<float*>(dst) : p.oavg[(size_t)g] + lo;
+                    std::vector<const void*> ptrs;
+                    for (int k = 0; k < p.D; ++k) ptrs.push_back(piece_ptr(p, g, k, j));
+                    rc = reduce_on(ctx, g, ctx->tuning.tu, ptrs.data(), w, p.D, cnt, p.in, avg, FA_F32, p.mode,
+                                   mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
+                    if (!rc)
+                        rc = opt_on(ctx->tuning.tu, p.opt_master ? p.opt.rule : fa::kOptBoot, p.opt, avg,
+                                    p.ox[(size_t)g] + lo, p.om[(size_t)g] + lo,
+                                    opt_adaptive(p.opt.rule) ? p.ov[(size_t)g] + lo : nullptr, cnt, dst, p.out, st);
+                    continue;
+                }
                 if (p.mode == FA_LITERAL) {
                     const void* last = piece_ptr(p, g, p.last_slot >= 0 ? p.last_slot : p.D - 1, j);
                     rc = reduce_on(ctx, g, ctx->tuning.tu, &last, w, 1, piece_cnt(p, g, j), p.in, dst, p.out,
@@ -939,6 +1020,10 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
             if (rc || (rc = mark_done(ctx, p, g, st))) return rc;
         }
         set_range_runs(p, G);
+        if (p.opt.rule != FA_OPT_NONE) {  // one reducing call = one step (the first one without a master: none)
+            if (p.opt_master) ++p.opt_steps;
+            p.opt_master = true;
+        }
         return FA_OK;
     }
     if (p.mode == FA_LITERAL) {  // the last client's GPU computes the whole bucket; nothing to exchange
@@ -1034,7 +1119,12 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
 // [p.reduced, j) are all submitted: one launch continues the fp32 accumulator over them (or, when j == D,
 // finishes the chain into the output), after their H2D copies.  Same bits as one chain over all D.
 int advance_prefix(fa_ctx* ctx, Part& p) {
-    if (!(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) || p.rs || p.mode != FA_FEDAVG || p.ready) return FA_OK;
+    // Whether a part is eager was settled when it was defined: it is, if it was given an accumulator.  A part
+    // that took the context's stage at its definition has none and stays non-eager when the stage goes; a part
+    // with a stage is non-eager while it has one.
+    if (!(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) || p.rs || p.mode != FA_FEDAVG || p.ready || !p.acc[0] ||
+        p.opt.rule != FA_OPT_NONE)
+        return FA_OK;
     int j = p.reduced;
     while (j < p.D && p.submitted[(size_t)j]) ++j;
     if (j == p.reduced) return FA_OK;
@@ -1250,6 +1340,81 @@ void reset_round(Part& p) {
     p.ready = false;
 }
 
+// Waits for everything that may touch the part's stage state.  A reduction may have run on a caller's stream
+// that is gone by now, so this waits for the devices, not for a stream handle (state reads, writes and rule
+// changes are rare).
+int opt_quiesce(fa_ctx* ctx) {
+    for (int g = 0; g < ctx->G; ++g) {
+        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
+        FA_HIP(hipDeviceSynchronize());
+    }
+    return FA_OK;
+}
+
+// fa_set_server_opt on a part (o checked; not FA_LITERAL, not rs).  None: the stage and its state go.  The
+// same rule: only the hyperparameters change.  Another rule (or the first one): the arrays the rule needs are
+// allocated, x is kept when the part had a stage, m and v are zeroed.
+int set_part_opt(fa_ctx* ctx, Part& p, const fa_server_opt& o) {
+    if (o.rule == FA_OPT_NONE) {
+        free_opt(ctx, p);
+        return FA_OK;
+    }
+    if (o.rule == p.opt.rule) {
+        p.opt = o;
+        return FA_OK;
+    }
+    const size_t G = (size_t)ctx->G;
+    const bool fresh = p.opt.rule == FA_OPT_NONE;
+    if (!fresh)  // the arrays about to be zeroed or freed may still be in use
+        if (int rc = opt_quiesce(ctx)) return rc;
+    if (fresh) {
+        p.ox.assign(G, nullptr);
+        p.om.assign(G, nullptr);
+        p.ov.assign(G, nullptr);
+        p.oavg.assign(G, nullptr);
+        p.opt_master = false;
+        p.opt_steps = 0;
+    }
+    for (size_t g = 0; g < G; ++g) {
+        DeviceGuard dg(ctx->gpu[g].dev);
+        const size_t bytes = std::max<size_t>(16, p.cnt[g] * 4);
+        auto need = [&](std::vector<float*>& arr, bool wanted, bool zero) -> int {
+            if (wanted && !arr[g] && hipMalloc((void**)&arr[g], bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                arr[g] = nullptr;
+                return fail(FA_ERR_NOMEM, "server opt: state alloc of %zu B failed on GPU %zu", bytes, g);
+            }
+            if (!wanted && arr[g]) {
+                (void)hipFree(arr[g]);
+                arr[g] = nullptr;
+            }
+            if (wanted && zero) FA_HIP(hipMemset(arr[g], 0, bytes));
+            return FA_OK;
+        };
+        int rc = need(p.ox, true, fresh);
+        if (!rc) rc = need(p.om, true, true);
+        if (!rc) rc = need(p.ov, opt_adaptive(o.rule), true);
+        if (!rc) rc = need(p.oavg, p.out != FA_F32, false);
+        if (rc) {
+            const std::string why = g_err;
+            free_opt(ctx, p);
+            g_err = why;
+            return rc;
+        }
+    }
+    // the zeroing ran on the null stream, which the context's non-blocking streams do not wait for
+    if (int rc = opt_quiesce(ctx)) return rc;
+    p.opt = o;
+    if (fresh) {
+        // the part is non-eager and never kept host-side from here on: what this round chained or kept so far
+        // goes back to the plain path.  A rule change leaves a round already stepped as it is: the finalize
+        // after it copies out, one step per round.
+        p.reduced = 0;
+        p.ready = false;
+    }
+    return FA_OK;
+}
+
 // The end of a phase: wait for the submits, reduce on every GPU (unless the round's reduction is done
 // already: accumulate on arrival reached D, or fa_reduce_parts), copy the result out, reset the round.
 int finalize_impl(fa_ctx* ctx, int part_id, const Gather& dst, bool pinned) {
@@ -1264,7 +1429,7 @@ int finalize_impl(fa_ctx* ctx, int part_id, const Gather& dst, bool pinned) {
     if (dst.total() != p->n * dsize(p->out))
         return fail(FA_ERR_ARG, "output of %zu bytes expected, destination holds %zu", p->n * dsize(p->out),
                     dst.total());
-    if (!p->ready && p->reduced == 0 && host_read_all(*p)) {  // the kept receipts, read where they are:
+    if (!p->ready && p->reduced == 0 && p->opt.rule == FA_OPT_NONE && host_read_all(*p)) {  // the kept receipts, read where they are:
         rc = pinned ? host_reduce(ctx, *p, p->w.data(), nullptr, &dst) : kNotHostReadable;  // into the reply,
         const bool into_reply = rc == FA_OK;
         if (rc == kNotHostReadable) {                                                      // or the output
@@ -1320,7 +1485,8 @@ int reduce_parts_impl(fa_ctx* ctx, int n_parts, const int* ids, const float* con
     std::vector<int> single;
     for (int i = 0; i < n_parts; ++i) {
         Part& p = *ps[(size_t)i];
-        bool batch = !p.rs && p.mode == FA_FEDAVG && p.D <= fa::kMaxClients && p.n_host == 0;
+        bool batch = !p.rs && p.mode == FA_FEDAVG && p.D <= fa::kMaxClients && p.n_host == 0 &&
+                     p.opt.rule == FA_OPT_NONE;  // a part with a server-optimizer stage: its own launches
         for (int g = 0; batch && g < ctx->G; ++g) {
             DeviceGuard dg(ctx->gpu[(size_t)g].dev);
             batch = p.npiece[(size_t)g] == 1 &&
@@ -1717,7 +1883,8 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     p.submitted.assign((size_t)n_clients, 0);
     p.host_src.assign((size_t)n_clients, {});
     const size_t G = (size_t)ctx->G;
-    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG;
+    const bool staged = ctx->opt.rule != FA_OPT_NONE && mode != FA_LITERAL && !rs;  // takes the context's stage
+    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged;
     if (rs) {
         const size_t unit = G * kShardUnit;
         p.npad = (n_elems + unit - 1) / unit * unit;
@@ -1796,8 +1963,114 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
             p.acc[g] = reinterpret_cast<float*>(p.pool[g] + extra_off);
         }
     }
+    if (staged) {
+        if (int rc = set_part_opt(ctx, p, ctx->opt)) {
+            const std::string why = g_err;
+            free_part(ctx, p);
+            g_err = why;
+            return rc;
+        }
+    }
     ctx->parts.emplace(part_id, std::move(p));
     return FA_OK;
+}
+
+int fa_set_server_opt(fa_ctx* ctx, int part_id, const fa_server_opt* opt) {
+    g_err.clear();
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    const fa_server_opt o = opt ? *opt : fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (int rc = check_opt(o)) return rc;
+    if (o.rule != FA_OPT_NONE && (ctx->flags & FA_SHARD_CLIENT_RS))
+        return fail(FA_ERR_ARG, "server opt: not on an FA_SHARD_CLIENT_RS context (its aggregate is not bit-specified)");
+    if (part_id < 0) {
+        ctx->opt = o;
+        return FA_OK;
+    }
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (o.rule != FA_OPT_NONE && p->mode == FA_LITERAL)
+        return fail(FA_ERR_ARG, "server opt: part %d is an FA_LITERAL part", part_id);
+    return set_part_opt(ctx, *p, o);
+}
+
+int fa_server_opt_set_state(fa_ctx* ctx, int part_id, const float* x, const float* m, const float* v, uint64_t steps) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (p->opt.rule == FA_OPT_NONE) return fail(FA_ERR_STATE, "part %d has no server-optimizer stage", part_id);
+    if ((rc = opt_quiesce(ctx))) return rc;
+    for (int g = 0; g < ctx->G; ++g) {
+        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
+        const size_t off = p->off[(size_t)g], bytes = p->cnt[(size_t)g] * 4;
+        if (!bytes) continue;
+        if (x) FA_HIP(hipMemcpy(p->ox[(size_t)g], x + off, bytes, hipMemcpyHostToDevice));
+        if (m) FA_HIP(hipMemcpy(p->om[(size_t)g], m + off, bytes, hipMemcpyHostToDevice));
+        if (v && opt_adaptive(p->opt.rule)) FA_HIP(hipMemcpy(p->ov[(size_t)g], v + off, bytes, hipMemcpyHostToDevice));
+    }
+    if ((rc = opt_quiesce(ctx))) return rc;  // the copies land before any later launch on the ctx streams
+    if (x) p->opt_master = true;
+    p->opt_steps = steps;
+    return FA_OK;
+}
+
+int fa_server_opt_get_state(fa_ctx* ctx, int part_id, float* x, float* m, float* v, uint64_t* steps) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (p->opt.rule == FA_OPT_NONE) return fail(FA_ERR_STATE, "part %d has no server-optimizer stage", part_id);
+    if (steps) *steps = p->opt_steps;
+    if (!x && !m && !v) return FA_OK;  // the step count alone is host state: no device wait
+    if ((rc = opt_quiesce(ctx))) return rc;
+    for (int g = 0; g < ctx->G; ++g) {
+        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
+        const size_t off = p->off[(size_t)g], bytes = p->cnt[(size_t)g] * 4;
+        if (!bytes) continue;
+        if (x) FA_HIP(hipMemcpy(x + off, p->ox[(size_t)g], bytes, hipMemcpyDeviceToHost));
+        if (m) FA_HIP(hipMemcpy(m + off, p->om[(size_t)g], bytes, hipMemcpyDeviceToHost));
+        if (v && opt_adaptive(p->opt.rule)) FA_HIP(hipMemcpy(v + off, p->ov[(size_t)g], bytes, hipMemcpyDeviceToHost));
+    }
+    return FA_OK;
+}
+
+int fa_get_server_opt(fa_ctx* ctx, int part_id, fa_server_opt* opt) {
+    g_err.clear();
+    if (!ctx || !opt) return fail(FA_ERR_ARG, "ctx or opt is null");
+    if (part_id < 0) {
+        *opt = ctx->opt;
+        return FA_OK;
+    }
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    *opt = p->opt;
+    return FA_OK;
+}
+
+int fa_server_opt_device(fa_ctx* ctx, int gpu, const fa_server_opt* opt, const float* d_avg, float* d_x, float* d_m,
+                         float* d_v, size_t n, void* d_out, fa_dtype out, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (!opt) return fail(FA_ERR_ARG, "server opt: opt is null");
+    if (int rc = check_opt(*opt)) return rc;
+    if (opt->rule == FA_OPT_NONE) return fail(FA_ERR_ARG, "server opt: rule FA_OPT_NONE takes no step");
+    if (!dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) return FA_OK;
+    const bool needs_v = opt_adaptive(opt->rule);
+    if (!d_avg || !d_x || !d_m || (needs_v && !d_v))
+        return fail(FA_ERR_ARG, "server opt: %s pointer is null", !d_avg ? "d_avg" : !d_x ? "d_x" : !d_m ? "d_m" : "d_v");
+    if (!aligned(d_avg, 4) || !aligned(d_x, 4) || !aligned(d_m, 4) || (needs_v && !aligned(d_v, 4)))
+        return fail(FA_ERR_ALIGN, "server opt: aggregate or state not 4-byte aligned");
+    if (d_out && !aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const int dev = ctx ? ctx->gpu[(size_t)gpu].dev : gpu;
+    if (!s && ctx) s = ctx->gpu[(size_t)gpu].compute;
+    DeviceGuard dg(dev);
+    const CtxTuning tu = ctx ? ctx->tuning : defaults();
+    return opt_on(tu.tu, opt->rule, *opt, d_avg, d_x, d_m, needs_v ? d_v : nullptr, n, d_out, out, s);
 }
 
 int fa_set_literal_divisor(fa_ctx* ctx, int part_id, float divisor) {
@@ -1911,7 +2184,7 @@ int fa_reduce_parts(fa_ctx* ctx, int n_parts, const int* part_ids, const float* 
         Part* p;
         int rc = check_part(ctx, part_ids[i], &p);
         if (rc) return rc;
-        if (p->mode == FA_TRIMMED ? p->n_submitted != p->D
+        if (p->mode == FA_TRIMMED || p->opt.rule != FA_OPT_NONE ? p->n_submitted != p->D
                                   : p->mode == FA_FEDAVG && p->n_submitted != p->D && !(h_weights && h_weights[i]))
             return fail(FA_ERR_STATE, "part %d: %d of %d clients submitted", part_ids[i], p->n_submitted, p->D);
     }
@@ -2014,7 +2287,7 @@ int fa_bucket_host_read(fa_ctx* ctx, int part_id, int* kept) {
     int rc = check_part(ctx, part_id, &p);
     if (rc) return rc;
     if (!kept) return fail(FA_ERR_ARG, "kept is null");
-    *kept = !p->ready && p->reduced == 0 && host_read_all(*p) ? 1 : 0;
+    *kept = !p->ready && p->reduced == 0 && p->opt.rule == FA_OPT_NONE && host_read_all(*p) ? 1 : 0;
     return FA_OK;
 }
 
@@ -2024,6 +2297,15 @@ int fa_reduce_part(fa_ctx* ctx, int part_id, const float* h_weights, void* hip_s
     int rc = check_part(ctx, part_id, &p);
     if (rc) return rc;
     if (hip_stream && ctx->G != 1) return fail(FA_ERR_ARG, "an explicit stream needs a single-GPU ctx");
+    if (p->opt.rule != FA_OPT_NONE) {
+        // a stage part: every reducing call is a step, so this one ends the round's reduction as
+        // fa_reduce_parts does -- a following fa_finalize* only copies out
+        if (p->n_submitted != p->D)
+            return fail(FA_ERR_STATE, "part %d: %d of %d clients submitted", part_id, p->n_submitted, p->D);
+        rc = reduce_part(ctx, *p, h_weights ? h_weights : p->w.data(), static_cast<hipStream_t>(hip_stream));
+        if (!rc) p->ready = true;
+        return rc;
+    }
     return reduce_part(ctx, *p, h_weights ? h_weights : p->w.data(), static_cast<hipStream_t>(hip_stream));
 }
 

@@ -94,6 +94,19 @@ hipError_t launch_literal(const void* x, fa_dtype in, void* dst, fa_dtype out, f
 // Weights are not read.  fa_trimmed.hip.
 hipError_t launch_trimmed(const ClientTable& t, int nc, fa_dtype in, fa_dtype out, int trim, void* dst, int64_t head,
                           int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);
+// The server-optimizer stage (fa.h "Server optimizer"), fa_server_opt.hip.  One step of `rule` (an fa_opt_rule
+// other than FA_OPT_NONE, or kOptBoot: x' = avg, m' = v' = +0, v nullable) over n elements: reads avg and the
+// fp32 state x, m, v (v null and untouched for FA_OPT_MOMENTUM), writes the state and, unless out is null, x'
+// in dtype `odt`.  out may be avg itself for FA_F32.  head / nvec / vector_ok: the split of reduce_on, with 4
+// elements per vector.
+constexpr int kOptBoot = 0;
+struct OptHyper {
+    float lr, beta1, beta2, tau;
+    float c1, c2;  // fl(1 - beta1), fl(1 - beta2), computed on the host
+};
+hipError_t launch_server_opt(int rule, const OptHyper& h, const float* avg, float* x, float* m, float* v, void* out,
+                             fa_dtype odt, int64_t head, int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu,
+                             hipStream_t s);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, int64_t head, int64_t nvec,
                        int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);

@@ -24,11 +24,17 @@
 // the north star's weighted mean (weights n_k/N from --samples, else 1/D);
 // --mode trimmed [--trim T] / --mode median is the coordinate-wise trimmed
 // mean (FA_TRIMMED, fa.h), which T owners sending NaN or inf do not reach.
+//
+// --server-opt momentum|adagrad|adam|yogi puts a server optimizer (fa.h "Server optimizer") behind the
+// aggregate of every bucket: the global model and its moments stay on the GPU in fp32 across rounds, and
+// --server-state FILE carries them across restarts.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
+#include <fstream>
 #include <iostream>
 #include <map>
 #include <set>
@@ -76,7 +82,87 @@ struct Options {
     size_t stream_min = 1u << 20;
     bool gpu_crc = true;  // --crc gpu|host: the reply records' CRC-32s from the GPU (fa_output_crc32) or the host
     std::map<int, double> samples;  // client id -> n_k
+    // --server-opt RULE --server-lr L [--server-beta1 B] [--server-beta2 B] [--server-tau T]: the server
+    // optimizer of every bucket (fa_set_server_opt on the context, before any bucket is defined);
+    // --server-state FILE: read at startup if it exists, rewritten after every round
+    fa_server_opt server{FA_OPT_NONE, 0.0f, 0.9f, 0.99f, 1e-3f};
+    bool server_lr_given = false, server_flag = false;  // server_flag: some --server-* other than --server-opt
+    std::string server_state;
 };
+
+const char* server_rule_name(int rule) {
+    return rule == FA_OPT_MOMENTUM ? "momentum" : rule == FA_OPT_ADAGRAD ? "adagrad" : rule == FA_OPT_ADAM ? "adam" : "yogi";
+}
+
+// --server-state FILE, little-endian: "FASRVOPT", u32 version = 1, u32 rule, u32 n_parts, u32 0; then per part
+// i32 part id (the protocol's model_part), u32 0, u64 n, u64 steps, x, m, v (n fp32 each; v zeros for
+// momentum).  Hyperparameters are not stored: they come from the flags.
+struct ServerStatePart {
+    uint64_t n = 0, steps = 0;
+    std::vector<float> x, m, v;
+};
+using ServerState = std::map<int, ServerStatePart>;
+constexpr char kStateMagic[8] = {'F', 'A', 'S', 'R', 'V', 'O', 'P', 'T'};
+constexpr uint32_t kStateVersion = 1;
+
+// Reads FILE into *out.  A file that does not exist is an empty state (true); a bad magic, version, rule or a
+// truncated file is an error (false, *err says which).
+bool read_server_state(const std::string& path, int rule, ServerState* out, std::string* err) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return true;
+    f.seekg(0, std::ios::end);
+    const uint64_t size = (uint64_t)f.tellg();
+    f.seekg(0);
+    char magic[8];
+    uint32_t hdr[4];
+    if (!f.read(magic, 8) || !f.read(reinterpret_cast<char*>(hdr), 16)) return *err = "shorter than its header", false;
+    if (std::memcmp(magic, kStateMagic, 8) != 0) return *err = "bad magic (not a FASRVOPT file)", false;
+    if (hdr[0] != kStateVersion) return *err = "version " + std::to_string(hdr[0]) + ", expected 1", false;
+    if ((int)hdr[1] != rule)
+        return *err = "written with rule " + std::to_string(hdr[1]) + ", --server-opt " + server_rule_name(rule) +
+                      " is rule " + std::to_string(rule), false;
+    uint64_t at = 24;
+    for (uint32_t i = 0; i < hdr[2]; ++i) {
+        int32_t id[2];
+        uint64_t ns[2];
+        if (!f.read(reinterpret_cast<char*>(id), 8) || !f.read(reinterpret_cast<char*>(ns), 16))
+            return *err = "truncated at part " + std::to_string(i), false;
+        at += 24;
+        if (ns[0] > (size - at) / 12) return *err = "part " + std::to_string(id[0]) + " runs past the end of the file", false;
+        ServerStatePart& sp = (*out)[id[0]];
+        sp.n = ns[0];
+        sp.steps = ns[1];
+        for (auto* a : {&sp.x, &sp.m, &sp.v}) {
+            a->resize((size_t)sp.n);
+            if (sp.n && !f.read(reinterpret_cast<char*>(a->data()), (std::streamsize)(sp.n * 4)))
+                return *err = "truncated in part " + std::to_string(id[0]), false;
+        }
+        at += sp.n * 12;
+    }
+    return true;
+}
+
+// Writes FILE.tmp and renames it over FILE, so a reader never sees half a state.
+bool write_server_state(const std::string& path, int rule, const ServerState& st) {
+    const std::string tmp = path + ".tmp";
+    {
+        std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
+        const uint32_t hdr[4] = {kStateVersion, (uint32_t)rule, (uint32_t)st.size(), 0};
+        f.write(kStateMagic, 8);
+        f.write(reinterpret_cast<const char*>(hdr), 16);
+        for (auto& kv : st) {
+            const int32_t id[2] = {kv.first, 0};
+            const uint64_t ns[2] = {kv.second.n, kv.second.steps};
+            f.write(reinterpret_cast<const char*>(id), 8);
+            f.write(reinterpret_cast<const char*>(ns), 16);
+            for (auto* a : {&kv.second.x, &kv.second.m, &kv.second.v})
+                f.write(reinterpret_cast<const char*>(a->data()), (std::streamsize)(kv.second.n * 4));
+        }
+        f.flush();
+        if (!f) return false;
+    }
+    return std::rename(tmp.c_str(), path.c_str()) == 0;
+}
 
 void usage() {
     std::cerr << "usage: fa_aggregator -i ID -d DATA_OWNERS -c COMPUTE_NODES [--mode fedavg|literal|trimmed|median]\n"
@@ -85,10 +171,17 @@ void usage() {
                  "       [--divisor K] [--last-layers L] [--no-pinned] [--layout range|rs] [--rs-chunks C]\n"
                  "       [--eager] [--stall-report S] [--receipt-timeout S] [--rx-concurrency K]\n"
                  "       [--senders S] [--stream-min-bytes N] [--crc gpu|host] [--test-shared-device]\n"
+                 "       [--server-opt momentum|adagrad|adam|yogi --server-lr L [--server-beta1 B] [--server-beta2 B]\n"
+                 "        [--server-tau T] [--server-state FILE]]\n"
                  "--mode trimmed: per element the T lowest and T highest of the owners' values are dropped and the\n"
                  "rest averaged (2T < DATA_OWNERS <= 128; without --trim, and with --mode median, the median), so up\n"
                  "to T owners that send NaN, inf or huge values change no reply; --samples is ignored; not with\n"
                  "--layout rs.\n"
+                 "--server-opt: a server optimizer (FedAvgM, FedAdagrad, FedAdam, FedYogi) steps the global model with\n"
+                 "the round's aggregate; the model and its moments stay on the GPU in fp32; L finite and >= 0, B in\n"
+                 "[0, 1) (defaults 0.9 and 0.99), T finite and > 0 (default 1e-3); --server-state FILE is read at startup\n"
+                 "if it exists (the initial global model, the moments of an earlier run) and rewritten after every\n"
+                 "round; not with --mode literal or --layout rs.\n"
                  "A bucket takes the dtype of its first receipt's parameters (all fp32, all bf16 or all fp16, by\n"
                  "their storage type) and is reduced and replied in it; a later receipt of another size or dtype\n"
                  "ends the process (exit 1).\n";
@@ -140,6 +233,31 @@ bool parse_args(int argc, char** argv, Options* o) {
             else if (m == "trimmed") o->mode = FA_TRIMMED;
             else if (m == "median") o->mode = FA_TRIMMED, o->median = true;
             else return false;
+        } else if (a == "--server-opt") {
+            std::string r = val("--server-opt");
+            if (r == "momentum") o->server.rule = FA_OPT_MOMENTUM;
+            else if (r == "adagrad") o->server.rule = FA_OPT_ADAGRAD;
+            else if (r == "adam") o->server.rule = FA_OPT_ADAM;
+            else if (r == "yogi") o->server.rule = FA_OPT_YOGI;
+            else {
+                std::cerr << "--server-opt " << r << ": momentum, adagrad, adam or yogi\n";
+                return false;
+            }
+        } else if (a == "--server-lr") {
+            o->server.lr = (float)std::atof(val("--server-lr"));
+            o->server_lr_given = o->server_flag = true;
+        } else if (a == "--server-beta1") {
+            o->server.beta1 = (float)std::atof(val("--server-beta1"));
+            o->server_flag = true;
+        } else if (a == "--server-beta2") {
+            o->server.beta2 = (float)std::atof(val("--server-beta2"));
+            o->server_flag = true;
+        } else if (a == "--server-tau") {
+            o->server.tau = (float)std::atof(val("--server-tau"));
+            o->server_flag = true;
+        } else if (a == "--server-state") {
+            o->server_state = val("--server-state");
+            o->server_flag = true;
         } else if (a == "--trim") {
             o->trim = std::atoi(val("--trim"));
             o->trim_given = true;
@@ -176,6 +294,42 @@ bool parse_args(int argc, char** argv, Options* o) {
             return false;
         }
         if (!o->trim_given) o->trim = o->data_owners >= 1 ? (o->data_owners - 1) / 2 : 0;
+    }
+    if (o->server.rule == FA_OPT_NONE && o->server_flag) {
+        std::cerr << "--server-lr, --server-beta1, --server-beta2, --server-tau and --server-state go with --server-opt\n";
+        return false;
+    }
+    if (o->server.rule != FA_OPT_NONE) {
+        const fa_server_opt& so = o->server;
+        const bool adaptive = so.rule != FA_OPT_MOMENTUM, second = so.rule == FA_OPT_ADAM || so.rule == FA_OPT_YOGI;
+        if (!o->server_lr_given) {
+            std::cerr << "--server-opt needs --server-lr\n";
+            return false;
+        }
+        if (o->mode == FA_LITERAL) {
+            std::cerr << "--server-opt steps a mean: not with --mode literal\n";
+            return false;
+        }
+        if (o->rs) {
+            std::cerr << "--server-opt needs a bit-specified aggregate: not with --layout rs\n";
+            return false;
+        }
+        if (!std::isfinite(so.lr) || so.lr < 0) {
+            std::cerr << "--server-lr " << so.lr << ": finite and >= 0\n";
+            return false;
+        }
+        if (!(so.beta1 >= 0 && so.beta1 < 1)) {
+            std::cerr << "--server-beta1 " << so.beta1 << ": in [0, 1)\n";
+            return false;
+        }
+        if (second && !(so.beta2 >= 0 && so.beta2 < 1)) {
+            std::cerr << "--server-beta2 " << so.beta2 << ": in [0, 1)\n";
+            return false;
+        }
+        if (adaptive && (!std::isfinite(so.tau) || !(so.tau > 0))) {
+            std::cerr << "--server-tau " << so.tau << ": finite and > 0\n";
+            return false;
+        }
     }
     return o->data_owners >= 1 && o->stall_report_s > 0 && o->receipt_timeout_s >= 0;
 }
@@ -214,7 +368,8 @@ constexpr size_t kGpuCrcMinBytes = 1u << 20;
 
 class Aggregator {
 public:
-    Aggregator(const Options& o, NetLayer* net, const std::vector<int>& owners) : o_(o), net_(net) {
+    Aggregator(const Options& o, NetLayer* net, const std::vector<int>& owners, ServerState loaded)
+        : o_(o), net_(net), loaded_(std::move(loaded)) {
         int flags = o.rs ? FA_SHARD_CLIENT_RS : o.gpus > 1 ? FA_SHARD_RANGE : 0;
         if (o.eager) flags |= FA_ACCUMULATE_ON_ARRIVAL;
         if (o.shared_device) {
@@ -225,6 +380,7 @@ public:
         }
         FA_CHECK(fa_set_literal_divisor(ctx_, -1, o.divisor));
         if (o.mode == FA_TRIMMED) FA_CHECK(fa_set_trim(ctx_, -1, o.trim));
+        if (o.server.rule != FA_OPT_NONE) FA_CHECK(fa_set_server_opt(ctx_, -1, &o.server));  // before any bucket
         if (o.rs_chunks > 0) {
             fa_tuning t{};
             t.rs_chunks = o.rs_chunks;
@@ -347,6 +503,20 @@ public:
             const fa_dtype dt = pd == ParamDtype::F32 ? FA_F32 : pd == ParamDtype::BF16 ? FA_BF16 : FA_F16;
             FA_CHECK(fa_bucket_define(ctx_, r.model_part, b.numel, dt, dt, o_.data_owners, o_.mode));
             b.defined = true;
+            auto ls = loaded_.find(r.model_part);
+            if (ls != loaded_.end()) {  // --server-state: the bucket starts from the stored model and moments
+                const ServerStatePart& sp = ls->second;
+                if (sp.n != b.numel) {
+                    std::cerr << "[aggregator] --server-state: part " << r.model_part << " holds " << sp.n
+                              << " elements, its bucket " << b.numel << "\n";
+                    // the owners are still sending this phase's other receipts: the readers take their frame
+                    // buffers from the process-wide allocator, which exit() destroys -- they finish first
+                    net_->stop();
+                    std::exit(1);
+                }
+                FA_CHECK(fa_server_opt_set_state(ctx_, r.model_part, sp.x.data(), sp.m.data(),
+                                                 o_.server.rule == FA_OPT_MOMENTUM ? nullptr : sp.v.data(), sp.steps));
+            }
         } else if ((size_t)ar.param_numel() != b.numel || pd != b.dtype) {
             std::cerr << "[aggregator] bucket " << r.model_part << " changed size or dtype\n";
             std::exit(1);
@@ -453,6 +623,33 @@ public:
     void fan_out(const std::shared_ptr<const Bytes>& f) {
         net_->send(0, f);
         for (int i = 0; i < o_.data_owners - 1; ++i) net_->send(i + o_.compute_nodes + 1, f);
+    }
+
+    // --server-state: every defined bucket's x, m, v and steps (parts read at startup and never defined in this
+    // run are carried over as read), written to FILE.tmp and renamed over FILE.  Returns the most steps a
+    // bucket has taken (the round line's server_steps).
+    unsigned long long save_server_state() {
+        unsigned long long most = 0;
+        const bool write = !o_.server_state.empty();
+        for (auto& kv : buckets_) {
+            if (!kv.second.defined) continue;
+            uint64_t steps = 0;
+            if (!write) {
+                FA_CHECK(fa_server_opt_get_state(ctx_, kv.first, nullptr, nullptr, nullptr, &steps));
+            } else {
+                ServerStatePart& sp = loaded_[kv.first];
+                sp.n = kv.second.numel;
+                for (auto* a : {&sp.x, &sp.m, &sp.v}) a->assign((size_t)sp.n, 0.0f);
+                FA_CHECK(fa_server_opt_get_state(ctx_, kv.first, sp.x.data(), sp.m.data(), sp.v.data(), &steps));
+                sp.steps = steps;
+            }
+            most = std::max<unsigned long long>(most, steps);
+        }
+        if (write && !write_server_state(o_.server_state, o_.server.rule, loaded_)) {
+            std::cerr << "[aggregator] --server-state: cannot write " << o_.server_state << "\n";
+            std::exit(1);
+        }
+        return most;
     }
 
     size_t bytes_in(int mp) { return buckets_[mp].bytes_in; }
@@ -622,6 +819,7 @@ private:
     NetLayer* net_;
     fa_ctx* ctx_ = nullptr;
     std::map<int, Bucket> buckets_;
+    ServerState loaded_;  // --server-state: as read at startup, then as last written
     std::map<int, int> slots_;  // client id -> slot
     std::vector<char> claimed_;  // slot -> an arrived client holds it
     std::vector<int> expected_;  // the data owners' ids in slot order
@@ -679,6 +877,17 @@ int main(int argc, char** argv) {
         usage();
         return 2;
     }
+    // --server-state is read before any socket or device is opened: a file of another format or rule is a
+    // mistake in the command line
+    ServerState server_state;
+    if (!o.server_state.empty()) {
+        std::string why;
+        if (!read_server_state(o.server_state, o.server.rule, &server_state, &why)) {
+            std::cerr << "--server-state " << o.server_state << ": " << why << "\n";
+            usage();
+            return 2;
+        }
+    }
     if (o.mode == FA_TRIMMED && !o.samples.empty())
         std::cerr << "[aggregator] warning: --samples is ignored with --mode trimmed|median (the rule has no weights)\n";
     // pinned frame buffers: receipts DMA'd from, replies DMA'd into -- small ones too (from 4 KiB): a small
@@ -713,7 +922,7 @@ int main(int argc, char** argv) {
     const int L = o.last_layers > 0 ? o.last_layers : last_part_layers(refactor.model_name, refactor.start);
     std::cerr << "[aggregator] refactor: model " << refactor.model_name << "/" << refactor.model_type << " start "
               << refactor.start << " end " << refactor.end << " -> " << L << " last-part layer(s)\n";
-    Aggregator agg(o, &net, refactor.data_owners);
+    Aggregator agg(o, &net, refactor.data_owners, std::move(server_state));
 
     // the round line names the rule only where it is not a mean (lines of the other modes stay as they were)
     const std::string mode_tail =
@@ -785,16 +994,24 @@ int main(int argc, char** argv) {
         for (auto& f : replies) agg.fan_out(f);  // :153-166, in layer order
         net.flush();
         const double send2 = secs_since(t4);
+        // the replies are with the senders: the state is read back and stored off the reply path
+        std::string server_tail;
+        if (o.server.rule != FA_OPT_NONE) {
+            char buf[128];
+            snprintf(buf, sizeof buf, ",\"server_opt\":\"%s\",\"server_lr\":%g,\"server_steps\":%llu",
+                     server_rule_name(o.server.rule), (double)o.server.lr, agg.save_server_state());
+            server_tail = buf;
+        }
         printf("{\"round\":%d,\"phase1\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f},"
                "\"phase2\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,\"layers\":%d,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f,\"send_s\":%.6f},"
                "\"send_failures\":%llu,\"stale_dropped\":%llu,\"ignored\":%llu,\"replaced\":%llu,"
-               "\"clock_back\":%llu,\"streamed\":%llu,\"stream_fallbacks\":%llu,\"streamed_bytes\":%llu%s}\n",
+               "\"clock_back\":%llu,\"streamed\":%llu,\"stream_fallbacks\":%llu,\"streamed_bytes\":%llu%s%s}\n",
                round, recv1, red1, in1, s1.absorb_s, s1.finalize_s, s1.frame_s, recv2, red2, in2, L, s2.absorb_s,
                s2.finalize_s, s2.frame_s, send2, (unsigned long long)net.send_failures(), agg.stale_dropped(), agg.ignored(),
                agg.replaced(), agg.clock_back(), agg.streamed(), agg.stream_fallbacks(), agg.streamed_bytes(),
-               mode_tail.c_str());
+               mode_tail.c_str(), server_tail.c_str());
         fflush(stdout);
     }
     net.stop();
