@@ -72,6 +72,41 @@
  *              rounded to the out dtype; `steps` stays 0.  Every later reduction is one step and adds 1 to
  *              `steps`.  Added without a new FA_ABI_VERSION: fa_server_opt_device with n == 0 touches no
  *              device and answers FA_OK -- that is how a caller probes for it.
+ *   Clip stage (fa_set_clip): per-client L2 norm clipping of the updates of an FA_FEDAVG part (norm-bounded
+ *              FedAvg: Sun et al., "Can You Really Backdoor Federated Learning?"; the deterministic half of
+ *              DP-FedAvg).  Part-level state: g, an fp32 "reference" of n elements -- the global model the
+ *              owners last received -- and whether it exists.  Per round, with weights w_k and the fp32
+ *              C = max_norm > 0:
+ *              1. Squared distance.  For every client k: x_{k,i} is widened to fp32 exactly,
+ *                 d = fl32(x_{k,i} - g_i), q = (double)d * (double)d (exact in fp64), Q_k = sum_i q.  The
+ *                 summation order is NOT specified: every partial sum is an fp64 add of non-negative terms, so
+ *                 whatever the order |Q_k - exact| <= n * 2^-53 * exact.  No floating-point atomics: for one
+ *                 layout (GPU count, tuning, n, D) the result is the same bits on every run.  On range shards
+ *                 and range pieces the per-shard / per-piece sums are added on the host in fp64, in GPU order
+ *                 and then piece order.
+ *              2. Scale (fa_clip_scale, pure host arithmetic).  N = sqrt(Q_k) in fp64, correctly rounded.  If N
+ *                 is NaN or +inf, client k is EXCLUDED this round; else if N <= (double)C, s_k = 1.0f; else
+ *                 s_k = (float)((double)C / N).
+ *              3. Weights.  w'_k = fl32(w_k * s_k) for the included clients.  In fp64, in client order,
+ *                 W = the sum over all D of (double)w_k and W' = the sum over the included clients of
+ *                 (double)w'_k; c0 = (float)(W - W').
+ *              4. Aggregate.  acc = +0; if c0 != 0, acc = fmaf(c0, g_i, acc); then acc = fmaf(w'_k, x_{k,i}, acc)
+ *                 for the included k in ascending order: the FA_FEDAVG chain with g as an extra first term,
+ *                 since sum_k w_k s_k (x_k - g) + W g = sum_k (w_k s_k) x_k + (W - sum_k w_k s_k) g.  The mass
+ *                 taken from clipped or excluded owners stays on the reference.  If no owner is clipped or
+ *                 excluded, c0 == 0 and the result is bit for bit the plain FA_FEDAVG aggregate.  With zero
+ *                 included clients the aggregate is that first term alone (+0 when c0 == 0).
+ *              5. The aggregate is the part's fp32 aggregate a: it feeds the server-optimizer stage if the part
+ *                 has one, otherwise it is rounded once to the out dtype as for FA_FEDAVG.
+ *              6. Reference update.  After the round g becomes the part's output widened to fp32 (for a 16-bit
+ *                 out dtype the rounded values): exactly what the owners receive, with or without a server
+ *                 optimizer.
+ *              7. Bootstrap.  A round on a part that has no reference does no clipping: the plain aggregate,
+ *                 all s_k = 1, nothing excluded, Q_k reported as 0.  The reference is then set from its output.
+ *              A reducing call of such a part enqueues the norm pass on every GPU, waits for the D sums (one
+ *              stream round trip more than a plain round) and then enqueues the chain.  Added without a new
+ *              FA_ABI_VERSION: fa_clip_sumsq_device with n == 0 touches no device and answers FA_OK -- that is
+ *              how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -352,6 +387,41 @@ int fa_server_opt_get_state(fa_ctx* ctx, int part_id, float* x, float* m, float*
  * hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
 int fa_server_opt_device(fa_ctx* ctx, int gpu, const fa_server_opt* opt, const float* d_avg, float* d_x, float* d_m,
                          float* d_v, size_t n, void* d_out, fa_dtype out, void* hip_stream);
+
+/* Clip stage: per-client L2 norm clipping of an FA_FEDAVG part's updates (the header comment, "Clip stage").
+ * Gives a part the stage with bound max_norm > 0 (part_id >= 0; calling again changes the bound and keeps the
+ * reference), or sets the context default that FA_FEDAVG parts defined later take (part_id < 0).  max_norm == 0
+ * removes the stage and frees its arrays (per GPU: the fp32 reference over the elements that GPU's output
+ * covers, plus an fp32 buffer of that size for a 16-bit input).  FA_ERR_ARG, naming the cause: max_norm not
+ * finite or < 0, an FA_LITERAL or FA_TRIMMED part, an FA_SHARD_CLIENT_RS context.  FA_ERR_NOMEM when the arrays
+ * cannot be allocated.  Like a part with a server optimizer (the two compose, in either call order), a clipped
+ * part is never kept host-side (fa_bucket_host_read says 0), FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager, it
+ * gets its own launches in fa_reduce_parts (never the segment table), and a reducing call (fa_reduce_part,
+ * fa_reduce_parts, the fa_finalize* that reduces the round) needs every client submitted; fa_reduce_part marks
+ * the round reduced, so a following fa_finalize* only copies out.  Such a call waits on the host for the norm
+ * pass before it enqueues the chain: one stream round trip.  Range shards and range pieces work. */
+int fa_set_clip(fa_ctx* ctx, int part_id, float max_norm);
+/* The reference as a whole-bucket host array of n fp32, scattered to / gathered from the GPUs' shards.  set with
+ * g == NULL drops the reference: the next round bootstraps.  FA_ERR_STATE on a part without the stage, and from
+ * get on a part without a reference.  Both wait for the part's pending work. */
+int fa_clip_set_reference(fa_ctx* ctx, int part_id, const float* g);
+int fa_clip_get_reference(fa_ctx* ctx, int part_id, float* g);
+/* What the part's last reducing call did: sumsq[k] = Q_k, scales[k] = s_k (0 for an excluded client),
+ * included[k] = 0 / 1, *n_clipped = the included clients with s_k < 1.  Each array holds D entries; any pointer
+ * may be NULL.  After a bootstrap round: Q_k = 0, s_k = 1, all included.  FA_ERR_STATE on a part without the
+ * stage or never reduced with it. */
+int fa_clip_get_round(fa_ctx* ctx, int part_id, double* sumsq, float* scales, int* included, int* n_clipped);
+/* Rule 2 of the stage, pure host arithmetic: the scale of a client whose squared distance is sumsq under the
+ * bound max_norm; *excluded (nullable) = 1 and the result 0 when sqrt(sumsq) is NaN or +inf. */
+float fa_clip_scale(double sumsq, float max_norm, int* excluded);
+/* Rule 1 on raw device pointers: h_sumsq[k] = Q_k of the D client buckets (n elements of `in`) against d_ref (n
+ * fp32) on device `gpu`, any D >= 1.  ctx may be NULL (then `gpu` is the HIP device).  Every argument is checked
+ * before any device call: D, the dtype, h_sumsq, and for n > 0 null pointers and element alignment
+ * (FA_ERR_ALIGN); with n == 0 and valid arguments it touches no device, writes D zeros and answers FA_OK.
+ * Otherwise it enqueues on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream), waits for
+ * it and returns the D sums. */
+int fa_clip_sumsq_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in,
+                         const float* d_ref, double* h_sumsq, void* hip_stream);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

@@ -90,6 +90,12 @@ def lib():
         "fa_server_opt_set_state": (I, [P, I, P, P, P, U64]),
         "fa_server_opt_get_state": (I, [P, I, P, P, P, ctypes.POINTER(U64)]),
         "fa_server_opt_device": (I, [P, I, ctypes.POINTER(_ServerOpt), P, P, P, P, S, P, I, P]),
+        "fa_set_clip": (I, [P, I, F]),
+        "fa_clip_set_reference": (I, [P, I, P]),
+        "fa_clip_get_reference": (I, [P, I, P]),
+        "fa_clip_get_round": (I, [P, I, P, P, P, ctypes.POINTER(I)]),
+        "fa_clip_scale": (F, [ctypes.c_double, F, ctypes.POINTER(I)]),
+        "fa_clip_sumsq_device": (I, [P, I, P, I, S, I, P, P, P]),
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
         "fa_submit_gather": (I, [P, I, I, I, P, P, F]),
@@ -249,6 +255,26 @@ def server_opt_device(avg, x, m, v, n, out, out_dtype=F32, rule=OPT_ADAM, lr=1.0
     opt = _ServerOpt(rule, lr, beta1, beta2, tau)
     check(lib().fa_server_opt_device(ctx.handle if ctx is not None else None, gpu, ctypes.byref(opt), _addr(avg),
                                      _addr(x), _addr(m), _addr(v), n, _addr(out), out_dtype, _stream(stream)))
+
+
+def clip_sumsq_device(clients, n, in_dtype, ref, stream=None, gpu=0, ctx=None):
+    """fa_clip_sumsq_device: the squared L2 distances Q_k (np.float64, one per client) of D device-resident client
+    buckets to the fp32 device reference `ref` (fa.h "Clip stage", rule 1).  Enqueued on `stream` and waited for.
+    With n == 0 no device is touched and the sums are zeros: the feature probe."""
+    D = len(clients)
+    arr = (ctypes.c_void_p * D)(*[_addr(c) for c in clients])
+    q = np.empty(D, np.float64)
+    check(lib().fa_clip_sumsq_device(ctx.handle if ctx is not None else None, gpu, arr, D, n, in_dtype, _addr(ref),
+                                     q.ctypes.data, _stream(stream)))
+    return q
+
+
+def clip_scale(sumsq, max_norm):
+    """fa_clip_scale (host arithmetic, rule 2): (scale as np.float32, excluded) of a client whose squared
+    distance is `sumsq` under the bound `max_norm`; an excluded client (NaN or infinite norm) has scale 0."""
+    ex = ctypes.c_int(0)
+    s = lib().fa_clip_scale(float(sumsq), float(max_norm), ctypes.byref(ex))
+    return np.float32(s), bool(ex.value)
 
 
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
@@ -497,6 +523,36 @@ class Aggregator:
             steps = cur.value
         check(lib().fa_server_opt_set_state(self.handle, part_id, *[None if a is None else a.ctypes.data for a in arrs],
                                             int(steps)))
+
+    def set_clip(self, max_norm, part_id=-1):
+        """fa_set_clip: per-client L2 norm clipping of a FEDAVG part's updates to `max_norm` (part_id < 0: the
+        default of FEDAVG parts defined later); 0 removes the stage."""
+        check(lib().fa_set_clip(self.handle, part_id, float(max_norm)))
+
+    def clip_round(self, part_id):
+        """fa_clip_get_round: (sumsq float64[D], scales float32[D], included bool[D], n_clipped) of the part's
+        last reducing call; an excluded client has scale 0."""
+        D = self.parts[part_id][3]
+        q, s, inc = np.empty(D, np.float64), np.empty(D, np.float32), np.empty(D, np.intc)
+        nc = ctypes.c_int()
+        check(lib().fa_clip_get_round(self.handle, part_id, q.ctypes.data, s.ctypes.data, inc.ctypes.data,
+                                      ctypes.byref(nc)))
+        return q, s, inc.astype(bool), nc.value
+
+    def clip_reference(self, part_id):
+        """fa_clip_get_reference: the part's reference g as a whole-bucket fp32 numpy array."""
+        g = np.empty(self.parts[part_id][0], np.float32)
+        check(lib().fa_clip_get_reference(self.handle, part_id, g.ctypes.data))
+        return g
+
+    def set_clip_reference(self, part_id, g):
+        """fa_clip_set_reference: scatter a whole-bucket fp32 array into the part's reference; None drops the
+        reference, so the next round bootstraps."""
+        if g is not None:
+            g = np.ascontiguousarray(np.asarray(g, np.float32).reshape(-1))
+            if g.size != self.parts[part_id][0]:
+                raise ValueError("bucket %d holds %d elements, got %d" % (part_id, self.parts[part_id][0], g.size))
+        check(lib().fa_clip_set_reference(self.handle, part_id, None if g is None else g.ctypes.data))
 
     def submit(self, part_id, slot, host, weight=1.0, pinned=False):
         host = np.ascontiguousarray(host)

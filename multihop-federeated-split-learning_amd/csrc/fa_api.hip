@@ -21,6 +21,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -248,6 +249,11 @@ struct GpuRes {
     std::map<hipStream_t, uint64_t> waited;  // per stream: the copy batch it last waited for
     hipEvent_t step_ev = nullptr;  // orders the rs exchange of a piece after its reduction
     void* scratch = nullptr;       // fp32 chain accumulator for a 16-bit output, D > kMaxClients
+    // clip stage: the norm pass's device scratch (the sums, then the per-workgroup partials) and the pinned
+    // array the sums are read back into, grown on use (ensure_clip_scratch)
+    double* clip_dev = nullptr;
+    double* clip_host = nullptr;
+    size_t clip_sums = 0;          // sums either array has room for
     // fa_output_crc32: the piece table (pinned staging + device copy) and the per-piece results, grown on use
     char* crc_host = nullptr;
     char* crc_dev = nullptr;
@@ -324,7 +330,22 @@ struct Part {
     std::vector<float*> ox, om, ov, oavg;
     bool opt_master = false;  // x holds a model (set, or bootstrapped): the next reduction is a step
     uint64_t opt_steps = 0;
+    // Clip stage (fa.h "Clip stage"; clip == 0: none).  Per GPU the fp32 reference over its cnt elements and,
+    // for a 16-bit input, the fp32 buffer the chain's first term fmaf(c0, g, +0) is written into; each its own
+    // allocation, freed with the stage or the part.
+    float clip = 0.0f;
+    std::vector<float*> cref, cinit;
+    bool clip_has_ref = false;  // g holds a model (set, or left by a round): the next reduction clips
+    bool clip_reported = false; // a reducing call ran with the stage: the arrays below describe it
+    std::vector<double> clip_q;
+    std::vector<float> clip_s;
+    std::vector<int> clip_in;
+    int clip_n = 0;
 };
+
+// A part whose reducing calls are rounds of their own (a server-optimizer or clip stage): never batched,
+// eager or host-read, every client submitted before each.
+inline bool staged(const Part& p) { return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f; }
 
 }  // namespace
 
@@ -334,6 +355,7 @@ struct fa_ctx {
     float divisor = FA_DEFAULT_DIVISOR;
     int trim = FA_TRIM_MEDIAN;  // default of FA_TRIMMED parts defined later
     fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};  // default stage of FedAvg / trimmed parts defined later
+    float clip = 0.0f;          // default clip bound of FedAvg parts defined later (0: none)
     CtxTuning tuning;
     std::vector<GpuRes> gpu;
     std::map<int, Part> parts;
@@ -521,6 +543,65 @@ int sync_on(fa_ctx* ctx, int g, const fa::Tuning& tu, void* const* slots, const 
     return FA_OK;
 }
 
+// ------------------------------------------------------------------ clip stage
+
+// Rule 2 of fa.h "Clip stage": volatile keeps each step one rounded fp64 / fp32 operation.
+float clip_scale(double sumsq, float max_norm, int* excluded) {
+    volatile double nrm = std::sqrt(sumsq);
+    const double N = nrm;
+    const bool out = N != N || N == HUGE_VAL;
+    if (excluded) *excluded = out ? 1 : 0;
+    if (out) return 0.0f;
+    if (N <= (double)max_norm) return 1.0f;
+    volatile double q = (double)max_norm / N;
+    return (float)q;
+}
+
+// Room on GPU g (the current device) for the norm pass of `sums` (client, piece) sums.
+int ensure_clip_scratch(GpuRes& r, size_t sums) {
+    if (r.clip_sums >= sums) return FA_OK;
+    if (r.clip_dev) (void)hipFree(r.clip_dev);
+    if (r.clip_host) (void)hipHostFree(r.clip_host);
+    r.clip_dev = r.clip_host = nullptr;
+    r.clip_sums = 0;
+    const size_t cap = std::max<size_t>(sums, 256);
+    const size_t dev_bytes = (cap + (size_t)fa::kMaxClients * (size_t)fa::kClipMaxPartials) * sizeof(double);
+    if (hipMalloc((void**)&r.clip_dev, dev_bytes) != hipSuccess ||
+        hipHostMalloc((void**)&r.clip_host, cap * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        if (r.clip_dev) (void)hipFree(r.clip_dev);
+        r.clip_dev = nullptr;
+        return fail(FA_ERR_NOMEM, "clip: norm-pass scratch of %zu B failed", dev_bytes);
+    }
+    r.clip_sums = cap;
+    return FA_OK;
+}
+
+// Enqueues the norm pass on the current device: d_sums[k] = Q_k of clients[k] (n elements of `in`) against ref,
+// k < D, in passes of kMaxClients clients; d_part: kMaxClients * kClipMaxPartials doubles of scratch.  The
+// vector form where every client and ref share one 16-byte phase (the split of reduce_on).
+int clip_sumsq_on(const fa::Tuning& tu, const void* const* clients, int D, size_t n, fa_dtype in, const float* ref,
+                  double* d_part, double* d_sums, hipStream_t s) {
+    const size_t si = dsize(in);
+    const int V = (int)(16 / si);
+    const size_t phase = ((uintptr_t)clients[0] % 16) / si;
+    int64_t head = (int64_t)((V - phase) % V);
+    if ((size_t)head > n) head = (int64_t)n;
+    const int64_t nvec = (int64_t)(n - (size_t)head) / V;
+    bool vec = ((uintptr_t)ref + (size_t)head * 4) % 16 == 0;
+    for (int k = 0; k < D; ++k) vec = vec && (((uintptr_t)clients[k] % 16) / si == phase);
+    for (int k0 = 0; k0 < D; k0 += fa::kMaxClients) {
+        fa::ClientTable t;
+        const int nc = std::min(fa::kMaxClients, D - k0);
+        for (int k = 0; k < nc; ++k) {
+            t.src[k] = clients[k0 + k];
+            t.w[k] = 0.0f;
+        }
+        FA_HIP(fa::launch_clip_sumsq(t, nc, in, ref, head, nvec, (int64_t)n, vec, d_part, d_sums + k0, tu, s));
+    }
+    return FA_OK;
+}
+
 // ------------------------------------------------------------------ layouts
 
 // [c0, c1) of the D client slots held by GPU g of G under the rs layout (contiguous, balanced; chain
@@ -624,8 +705,23 @@ void free_opt(fa_ctx* ctx, Part& p) {
     p.opt_steps = 0;
 }
 
+// The same for the clip stage: its arrays go, the reference is forgotten.
+void free_clip(fa_ctx* ctx, Part& p) {
+    for (size_t g = 0; g < p.cref.size(); ++g) {
+        DeviceGuard dg(ctx->gpu[g].dev);
+        for (auto* arr : {&p.cref, &p.cinit})
+            if (g < arr->size() && (*arr)[g]) (void)hipFree((*arr)[g]);
+    }
+    p.cref.clear();
+    p.cinit.clear();
+    p.clip = 0.0f;
+    p.clip_has_ref = false;
+    p.clip_reported = false;
+}
+
 void free_part(fa_ctx* ctx, Part& p) {
     free_opt(ctx, p);
+    free_clip(ctx, p);
     for (size_t g = 0; g < p.pool.size(); ++g) {
         DeviceGuard dg(ctx->gpu[g].dev);
         if (p.pool[g]) (void)hipFree(p.pool[g]);
@@ -821,8 +917,8 @@ const char* device_visible(const void* ptr) {
 
 bool host_read_part(const fa_ctx* ctx, const Part& p) {
     // trimmed parts are never kept host-side (fa.h): D PCIe reads per element feed a sort, not a chain
-    // nor parts with a server-optimizer stage: their round ends in a step on the device state
-    return host_read_enabled() && p.mode != FA_TRIMMED && p.opt.rule == FA_OPT_NONE && ctx->G == 1 && !p.rs &&
+    // nor parts with a server-optimizer or clip stage: their round reads or ends in device state
+    return host_read_enabled() && p.mode != FA_TRIMMED && !staged(p) && ctx->G == 1 && !p.rs &&
            !(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) &&
            p.npiece[0] == 1 && p.n > 0 && (size_t)p.D * p.n * dsize(p.in) <= kHostReadMax;
 }
@@ -973,6 +1069,114 @@ int host_reduce(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, const Gathe
     return FA_OK;
 }
 
+// What the clip stage makes of a round's weights (fa.h "Clip stage", rules 1-3): the included clients in
+// ascending order, their weights w'_k, and the reference's weight c0.
+struct ClipPlan {
+    std::vector<int> inc;
+    std::vector<float> w;
+    float c0 = 0.0f;
+};
+
+// Rules 1-3 for part p (range layout, a reference present): the norm pass of every piece on every GPU, one wait
+// per GPU for its sums, then the host arithmetic.  The per-shard and per-piece sums are added in fp64 in GPU
+// order, then piece order.  Leaves the round's report in the part.
+int clip_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, ClipPlan* plan) {
+    const size_t D = (size_t)p.D;
+    std::vector<const void*> ptrs(D);
+    for (int g = 0; g < ctx->G; ++g) {
+        if (p.cnt[(size_t)g] == 0) continue;
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        hipStream_t st = s ? s : r.compute;
+        int rc = wait_copies(ctx, g, st);
+        const size_t sums = (size_t)p.npiece[(size_t)g] * D;
+        if (rc || (rc = ensure_clip_scratch(r, sums))) return rc;
+        for (int j = 0; j < p.npiece[(size_t)g]; ++j) {
+            for (size_t k = 0; k < D; ++k) ptrs[k] = piece_ptr(p, g, (int)k, j);
+            rc = clip_sumsq_on(ctx->tuning.tu, ptrs.data(), p.D, piece_cnt(p, g, j), p.in,
+                               p.cref[(size_t)g] + piece_lo(p, g, j), r.clip_dev + r.clip_sums,
+                               r.clip_dev + (size_t)j * D, st);
+            if (rc) return rc;
+        }
+        FA_HIP(hipMemcpyAsync(r.clip_host, r.clip_dev, sums * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    std::fill(p.clip_q.begin(), p.clip_q.end(), 0.0);
+    for (int g = 0; g < ctx->G; ++g) {
+        if (p.cnt[(size_t)g] == 0) continue;
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        FA_HIP(hipStreamSynchronize(s ? s : r.compute));
+        for (int j = 0; j < p.npiece[(size_t)g]; ++j)
+            for (size_t k = 0; k < D; ++k) {
+                volatile double q = p.clip_q[k] + r.clip_host[(size_t)j * D + k];
+                p.clip_q[k] = q;
+            }
+    }
+    double W = 0.0, Wp = 0.0;
+    p.clip_n = 0;
+    for (size_t k = 0; k < D; ++k) {
+        int ex = 0;
+        const float sc = clip_scale(p.clip_q[k], p.clip, &ex);
+        p.clip_s[k] = sc;
+        p.clip_in[k] = ex ? 0 : 1;
+        W += (double)w[k];
+        if (ex) continue;
+        if (sc < 1.0f) ++p.clip_n;
+        volatile float prod = w[k] * sc;  // one rounded fp32 product
+        const float wk = prod;
+        Wp += (double)wk;
+        plan->inc.push_back((int)k);
+        plan->w.push_back(wk);
+    }
+    volatile double rest = W - Wp;
+    plan->c0 = (float)rest;
+    return FA_OK;
+}
+
+// Rule 4 for piece j of GPU g (the current device): the chain over the included clients with the reference as
+// its first term, into dst (dtype odt).  An f32 part passes g as the chain's first client with weight c0; a
+// 16-bit part first writes fmaf(c0, g, +0) into its fp32 buffer (a one-client f32 chain) and continues from it.
+int clip_chain(fa_ctx* ctx, Part& p, int g, int j, const ClipPlan& plan, void* dst, fa_dtype odt, hipStream_t st) {
+    const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
+    if (cnt == 0) return FA_OK;
+    const fa::Tuning& tu = ctx->tuning.tu;
+    const void* ref = p.cref[(size_t)g] + lo;
+    const bool lead = plan.c0 != 0.0f;
+    if (plan.inc.empty()) {  // the first term alone, +0 without one
+        if (lead) return reduce_on(ctx, g, tu, &ref, &plan.c0, 1, cnt, FA_F32, dst, odt, FA_FEDAVG, 0.0f, nullptr, st);
+        FA_HIP(hipMemsetAsync(dst, 0, cnt * dsize(odt), st));
+        return FA_OK;
+    }
+    std::vector<const void*> ptrs;
+    std::vector<float> ws;
+    const float* init = nullptr;
+    if (lead && p.in == FA_F32) {
+        ptrs.push_back(ref);
+        ws.push_back(plan.c0);
+    } else if (lead) {
+        float* first = p.cinit[(size_t)g] + lo;
+        if (int rc = reduce_on(ctx, g, tu, &ref, &plan.c0, 1, cnt, FA_F32, first, FA_F32, FA_FEDAVG, 0.0f, nullptr, st))
+            return rc;
+        init = first;
+    }
+    for (size_t i = 0; i < plan.inc.size(); ++i) {
+        ptrs.push_back(piece_ptr(p, g, plan.inc[i], j));
+        ws.push_back(plan.w[i]);
+    }
+    return reduce_on(ctx, g, tu, ptrs.data(), ws.data(), (int)ptrs.size(), cnt, p.in, dst, odt, FA_FEDAVG, 0.0f, init, st);
+}
+
+// Rule 6 for the same piece: the reference := the output just written, widened to fp32.
+int clip_take_reference(Part& p, int g, int j, hipStream_t st) {
+    const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
+    if (cnt == 0) return FA_OK;
+    const char* out = static_cast<const char*>(p.dout[(size_t)g]) + lo * dsize(p.out);
+    float* ref = p.cref[(size_t)g] + lo;
+    if (p.out == FA_F32) FA_HIP(hipMemcpyAsync(ref, out, cnt * 4, hipMemcpyDeviceToDevice, st));
+    else FA_HIP(fa::launch_clip_widen(out, p.out, ref, (int64_t)cnt, st));
+    return FA_OK;
+}
+
 // Enqueue the full reduction of part p on every GPU (the ctx's streams, or `s` for a one-GPU ctx):
 // range -> each GPU's shard; rs -> the clients' fp32 partials, piece by piece, each piece's RCCL
 // reduce-scatter (ring over xGMI) overlapping the reduction of the next.
@@ -983,6 +1187,19 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
     // caller keeps them until then); a reduction before it takes them into the slots first
     if (int rc = host_flush(ctx, p)) return rc;
     if (!p.rs) {
+        // a clip stage with a reference: the norm pass and the host's wait for its sums come first (without a
+        // reference the round is the bootstrap: the plain aggregate, reported as unclipped)
+        const bool clip = p.clip > 0.0f, clipping = clip && p.clip_has_ref;
+        ClipPlan plan;
+        if (clip) {
+            p.clip_q.assign((size_t)p.D, 0.0);
+            p.clip_s.assign((size_t)p.D, 1.0f);
+            p.clip_in.assign((size_t)p.D, 1);
+            p.clip_n = 0;
+            p.clip_reported = true;
+            if (clipping)
+                if (int rc = clip_plan(ctx, p, w, s, &plan)) return rc;
+        }
         for (int g = 0; g < G; ++g) {
             GpuRes& r = ctx->gpu[(size_t)g];
             DeviceGuard dg(r.dev);
@@ -991,19 +1208,28 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
             if (rc) return rc;
             for (int j = 0; j < p.npiece[(size_t)g] && !rc; ++j) {  // one launch per piece, in order
                 void* dst = static_cast<char*>(p.dout[(size_t)g]) + piece_lo(p, g, j) * dsize(p.out);
-                if (p.opt.rule != FA_OPT_NONE) {
-                    // the fp32 aggregate (an f32 part: in its output, where the stage then runs in place), then
-                    // one step -- or the bootstrap of a part without a master -- on the same stream
+                if (staged(p)) {
+                    // the aggregate -- clipped, if the part has a reference; with a server optimizer in fp32 (an
+                    // f32 part: in its output, where the stage then runs in place), followed by one step or the
+                    // bootstrap of a part without a master -- then the new reference, all on the same stream
                     const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
-                    float* avg = p.out == FA_F32 ? static_cast<float*>(dst) : p.oavg[(size_t)g] + lo;
-                    std::vector<const void*> ptrs;
-                    for (int k = 0; k < p.D; ++k) ptrs.push_back(piece_ptr(p, g, k, j));
-                    rc = reduce_on(ctx, g, ctx->tuning.tu, ptrs.data(), w, p.D, cnt, p.in, avg, FA_F32, p.mode,
-                                   mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
-                    if (!rc)
+                    const bool opt = p.opt.rule != FA_OPT_NONE;
+                    float* avg = !opt ? nullptr : p.out == FA_F32 ? static_cast<float*>(dst) : p.oavg[(size_t)g] + lo;
+                    void* adst = opt ? (void*)avg : dst;
+                    const fa_dtype adt = opt ? FA_F32 : p.out;
+                    if (clipping) {
+                        rc = clip_chain(ctx, p, g, j, plan, adst, adt, st);
+                    } else {
+                        std::vector<const void*> ptrs;
+                        for (int k = 0; k < p.D; ++k) ptrs.push_back(piece_ptr(p, g, k, j));
+                        rc = reduce_on(ctx, g, ctx->tuning.tu, ptrs.data(), w, p.D, cnt, p.in, adst, adt, p.mode,
+                                       mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
+                    }
+                    if (!rc && opt)
                         rc = opt_on(ctx->tuning.tu, p.opt_master ? p.opt.rule : fa::kOptBoot, p.opt, avg,
                                     p.ox[(size_t)g] + lo, p.om[(size_t)g] + lo,
                                     opt_adaptive(p.opt.rule) ? p.ov[(size_t)g] + lo : nullptr, cnt, dst, p.out, st);
+                    if (!rc && clip) rc = clip_take_reference(p, g, j, st);
                     continue;
                 }
                 if (p.mode == FA_LITERAL) {
@@ -1024,6 +1250,7 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
             if (p.opt_master) ++p.opt_steps;
             p.opt_master = true;
         }
+        if (clip) p.clip_has_ref = true;  // what this round sent out
         return FA_OK;
     }
     if (p.mode == FA_LITERAL) {  // the last client's GPU computes the whole bucket; nothing to exchange
@@ -1123,7 +1350,7 @@ int advance_prefix(fa_ctx* ctx, Part& p) {
     // that took the context's stage at its definition has none and stays non-eager when the stage goes; a part
     // with a stage is non-eager while it has one.
     if (!(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) || p.rs || p.mode != FA_FEDAVG || p.ready || !p.acc[0] ||
-        p.opt.rule != FA_OPT_NONE)
+        staged(p))
         return FA_OK;
     int j = p.reduced;
     while (j < p.D && p.submitted[(size_t)j]) ++j;
@@ -1415,6 +1642,43 @@ int set_part_opt(fa_ctx* ctx, Part& p, const fa_server_opt& o) {
     return FA_OK;
 }
 
+// fa_set_clip on a part (max_norm checked; an FA_FEDAVG part, not rs).  0: the stage and its arrays go.  A part
+// that has the stage: only the bound changes.  Else the reference (and a 16-bit part's first-term buffer) is
+// allocated; the part has no reference until a round or fa_clip_set_reference gives it one.
+int set_part_clip(fa_ctx* ctx, Part& p, float max_norm) {
+    if (max_norm == 0.0f) {
+        if (p.clip > 0.0f)  // the arrays may still be in use
+            if (int rc = opt_quiesce(ctx)) return rc;
+        free_clip(ctx, p);
+        return FA_OK;
+    }
+    if (p.clip > 0.0f) {
+        p.clip = max_norm;
+        return FA_OK;
+    }
+    const size_t G = (size_t)ctx->G;
+    p.cref.assign(G, nullptr);
+    p.cinit.assign(G, nullptr);
+    for (size_t g = 0; g < G; ++g) {
+        DeviceGuard dg(ctx->gpu[g].dev);
+        const size_t bytes = std::max<size_t>(16, p.cnt[g] * 4);
+        if (hipMalloc((void**)&p.cref[g], bytes) != hipSuccess ||
+            (p.in != FA_F32 && hipMalloc((void**)&p.cinit[g], bytes) != hipSuccess)) {
+            (void)hipGetLastError();
+            free_clip(ctx, p);
+            return fail(FA_ERR_NOMEM, "clip: reference alloc of %zu B failed on GPU %zu", bytes, g);
+        }
+    }
+    p.clip = max_norm;
+    p.clip_has_ref = false;
+    p.clip_reported = false;
+    // non-eager and never kept host-side from here on: what this round chained or kept so far goes back to
+    // the plain path (as for a server-optimizer stage)
+    p.reduced = 0;
+    p.ready = false;
+    return FA_OK;
+}
+
 // The end of a phase: wait for the submits, reduce on every GPU (unless the round's reduction is done
 // already: accumulate on arrival reached D, or fa_reduce_parts), copy the result out, reset the round.
 int finalize_impl(fa_ctx* ctx, int part_id, const Gather& dst, bool pinned) {
@@ -1429,7 +1693,7 @@ int finalize_impl(fa_ctx* ctx, int part_id, const Gather& dst, bool pinned) {
     if (dst.total() != p->n * dsize(p->out))
         return fail(FA_ERR_ARG, "output of %zu bytes expected, destination holds %zu", p->n * dsize(p->out),
                     dst.total());
-    if (!p->ready && p->reduced == 0 && p->opt.rule == FA_OPT_NONE && host_read_all(*p)) {  // the kept receipts, read where they are:
+    if (!p->ready && p->reduced == 0 && !staged(*p) && host_read_all(*p)) {  // the kept receipts, read where they are:
         rc = pinned ? host_reduce(ctx, *p, p->w.data(), nullptr, &dst) : kNotHostReadable;  // into the reply,
         const bool into_reply = rc == FA_OK;
         if (rc == kNotHostReadable) {                                                      // or the output
@@ -1486,7 +1750,7 @@ int reduce_parts_impl(fa_ctx* ctx, int n_parts, const int* ids, const float* con
     for (int i = 0; i < n_parts; ++i) {
         Part& p = *ps[(size_t)i];
         bool batch = !p.rs && p.mode == FA_FEDAVG && p.D <= fa::kMaxClients && p.n_host == 0 &&
-                     p.opt.rule == FA_OPT_NONE;  // a part with a server-optimizer stage: its own launches
+                     !staged(p);  // a part with a server-optimizer or clip stage: its own launches
         for (int g = 0; batch && g < ctx->G; ++g) {
             DeviceGuard dg(ctx->gpu[(size_t)g].dev);
             batch = p.npiece[(size_t)g] == 1 &&
@@ -1835,6 +2099,8 @@ void fa_destroy(fa_ctx* ctx) {
         for (hipEvent_t e : {r.copy_ev, r.step_ev})
             if (e) (void)hipEventDestroy(e);
         if (r.scratch) (void)hipFree(r.scratch);
+        if (r.clip_dev) (void)hipFree(r.clip_dev);
+        if (r.clip_host) (void)hipHostFree(r.clip_host);
         if (r.crc_host) (void)hipHostFree(r.crc_host);
         if (r.crc_dev) (void)hipFree(r.crc_dev);
         for (hipStream_t s : {r.compute, r.copy, r.comm})
@@ -1884,7 +2150,8 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     p.host_src.assign((size_t)n_clients, {});
     const size_t G = (size_t)ctx->G;
     const bool staged = ctx->opt.rule != FA_OPT_NONE && mode != FA_LITERAL && !rs;  // takes the context's stage
-    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged;
+    const bool clipped = ctx->clip > 0.0f && mode == FA_FEDAVG && !rs;  // takes the context's clip bound
+    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged && !clipped;
     if (rs) {
         const size_t unit = G * kShardUnit;
         p.npad = (n_elems + unit - 1) / unit * unit;
@@ -1965,6 +2232,14 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     }
     if (staged) {
         if (int rc = set_part_opt(ctx, p, ctx->opt)) {
+            const std::string why = g_err;
+            free_part(ctx, p);
+            g_err = why;
+            return rc;
+        }
+    }
+    if (clipped) {
+        if (int rc = set_part_clip(ctx, p, ctx->clip)) {
             const std::string why = g_err;
             free_part(ctx, p);
             g_err = why;
@@ -2071,6 +2346,120 @@ int fa_server_opt_device(fa_ctx* ctx, int gpu, const fa_server_opt* opt, const f
     DeviceGuard dg(dev);
     const CtxTuning tu = ctx ? ctx->tuning : defaults();
     return opt_on(tu.tu, opt->rule, *opt, d_avg, d_x, d_m, needs_v ? d_v : nullptr, n, d_out, out, s);
+}
+
+int fa_set_clip(fa_ctx* ctx, int part_id, float max_norm) {
+    g_err.clear();
+    if (!finite_f(max_norm) || max_norm < 0.0f)
+        return fail(FA_ERR_ARG, "clip: max_norm %g must be finite and >= 0", (double)max_norm);
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (max_norm > 0.0f && (ctx->flags & FA_SHARD_CLIENT_RS))
+        return fail(FA_ERR_ARG, "clip: not on an FA_SHARD_CLIENT_RS context (its aggregate is not bit-specified; use "
+                                "FA_SHARD_RANGE)");
+    if (part_id < 0) {
+        ctx->clip = max_norm;
+        return FA_OK;
+    }
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (max_norm > 0.0f && p->mode != FA_FEDAVG)
+        return fail(FA_ERR_ARG, "clip: part %d is an %s part (the stage clips FA_FEDAVG updates)", part_id,
+                    p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_TRIMMED");
+    return set_part_clip(ctx, *p, max_norm);
+}
+
+int fa_clip_set_reference(fa_ctx* ctx, int part_id, const float* g) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (!(p->clip > 0.0f)) return fail(FA_ERR_STATE, "part %d has no clip stage", part_id);
+    if ((rc = opt_quiesce(ctx))) return rc;
+    for (int gi = 0; g && gi < ctx->G; ++gi) {
+        DeviceGuard dg(ctx->gpu[(size_t)gi].dev);
+        const size_t bytes = p->cnt[(size_t)gi] * 4;
+        if (bytes) FA_HIP(hipMemcpy(p->cref[(size_t)gi], g + p->off[(size_t)gi], bytes, hipMemcpyHostToDevice));
+    }
+    if (g && (rc = opt_quiesce(ctx))) return rc;  // the copies land before any later launch on the ctx streams
+    p->clip_has_ref = g != nullptr;
+    return FA_OK;
+}
+
+int fa_clip_get_reference(fa_ctx* ctx, int part_id, float* g) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (!(p->clip > 0.0f)) return fail(FA_ERR_STATE, "part %d has no clip stage", part_id);
+    if (!p->clip_has_ref) return fail(FA_ERR_STATE, "part %d has no clip reference yet", part_id);
+    if (!g && p->n) return fail(FA_ERR_ARG, "g is null");
+    if ((rc = opt_quiesce(ctx))) return rc;
+    for (int gi = 0; gi < ctx->G; ++gi) {
+        DeviceGuard dg(ctx->gpu[(size_t)gi].dev);
+        const size_t bytes = p->cnt[(size_t)gi] * 4;
+        if (bytes) FA_HIP(hipMemcpy(g + p->off[(size_t)gi], p->cref[(size_t)gi], bytes, hipMemcpyDeviceToHost));
+    }
+    return FA_OK;
+}
+
+int fa_clip_get_round(fa_ctx* ctx, int part_id, double* sumsq, float* scales, int* included, int* n_clipped) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (!(p->clip > 0.0f)) return fail(FA_ERR_STATE, "part %d has no clip stage", part_id);
+    if (!p->clip_reported) return fail(FA_ERR_STATE, "part %d: no round reduced with the clip stage yet", part_id);
+    for (size_t k = 0; k < (size_t)p->D; ++k) {
+        if (sumsq) sumsq[k] = p->clip_q[k];
+        if (scales) scales[k] = p->clip_in[k] ? p->clip_s[k] : 0.0f;
+        if (included) included[k] = p->clip_in[k];
+    }
+    if (n_clipped) *n_clipped = p->clip_n;
+    return FA_OK;
+}
+
+float fa_clip_scale(double sumsq, float max_norm, int* excluded) { return clip_scale(sumsq, max_norm, excluded); }
+
+int fa_clip_sumsq_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in,
+                         const float* d_ref, double* h_sumsq, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (D < 1) return fail(FA_ERR_ARG, "clip: D must be >= 1");
+    if (!dvalid(in)) return fail(FA_ERR_ARG, "bad dtype");
+    if (!h_sumsq) return fail(FA_ERR_ARG, "clip: h_sumsq is null");
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) {
+        std::fill(h_sumsq, h_sumsq + D, 0.0);
+        return FA_OK;
+    }
+    if (!d_clients) return fail(FA_ERR_ARG, "client array is null");
+    for (int k = 0; k < D; ++k) {
+        if (!d_clients[k]) return fail(FA_ERR_ARG, "client pointer %d is null", k);
+        if (!aligned(d_clients[k], dsize(in))) return fail(FA_ERR_ALIGN, "client %d not %zu-byte aligned", k, dsize(in));
+    }
+    if (!d_ref) return fail(FA_ERR_ARG, "clip: d_ref is null");
+    if (!aligned(d_ref, 4)) return fail(FA_ERR_ALIGN, "clip: reference not 4-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const int dev = ctx ? ctx->gpu[(size_t)gpu].dev : gpu;
+    if (!s && ctx) s = ctx->gpu[(size_t)gpu].compute;
+    DeviceGuard dg(dev);
+    const CtxTuning tu = ctx ? ctx->tuning : defaults();
+    GpuRes own;  // a context-less call brings its scratch and frees it before it returns
+    GpuRes& r = ctx ? ctx->gpu[(size_t)gpu] : own;
+    int rc = ensure_clip_scratch(r, (size_t)D);
+    if (!rc) rc = clip_sumsq_on(tu.tu, d_clients, D, n, in, d_ref, r.clip_dev + r.clip_sums, r.clip_dev, s);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(r.clip_host, r.clip_dev, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
+    if (!rc && e == hipSuccess) std::copy(r.clip_host, r.clip_host + D, h_sumsq);
+    if (!ctx) {
+        if (own.clip_dev) (void)hipFree(own.clip_dev);
+        if (own.clip_host) (void)hipHostFree(own.clip_host);
+    }
+    if (rc) return rc;
+    FA_HIP(e);
+    return FA_OK;
 }
 
 int fa_set_literal_divisor(fa_ctx* ctx, int part_id, float divisor) {
@@ -2184,7 +2573,7 @@ int fa_reduce_parts(fa_ctx* ctx, int n_parts, const int* part_ids, const float* 
         Part* p;
         int rc = check_part(ctx, part_ids[i], &p);
         if (rc) return rc;
-        if (p->mode == FA_TRIMMED || p->opt.rule != FA_OPT_NONE ? p->n_submitted != p->D
+        if (p->mode == FA_TRIMMED || staged(*p) ? p->n_submitted != p->D
                                   : p->mode == FA_FEDAVG && p->n_submitted != p->D && !(h_weights && h_weights[i]))
             return fail(FA_ERR_STATE, "part %d: %d of %d clients submitted", part_ids[i], p->n_submitted, p->D);
     }
@@ -2287,7 +2676,7 @@ int fa_bucket_host_read(fa_ctx* ctx, int part_id, int* kept) {
     int rc = check_part(ctx, part_id, &p);
     if (rc) return rc;
     if (!kept) return fail(FA_ERR_ARG, "kept is null");
-    *kept = !p->ready && p->reduced == 0 && p->opt.rule == FA_OPT_NONE && host_read_all(*p) ? 1 : 0;
+    *kept = !p->ready && p->reduced == 0 && !staged(*p) && host_read_all(*p) ? 1 : 0;
     return FA_OK;
 }
 
@@ -2297,8 +2686,8 @@ int fa_reduce_part(fa_ctx* ctx, int part_id, const float* h_weights, void* hip_s
     int rc = check_part(ctx, part_id, &p);
     if (rc) return rc;
     if (hip_stream && ctx->G != 1) return fail(FA_ERR_ARG, "an explicit stream needs a single-GPU ctx");
-    if (p->opt.rule != FA_OPT_NONE) {
-        // a stage part: every reducing call is a step, so this one ends the round's reduction as
+    if (staged(*p)) {
+        // a stage part: every reducing call is a step (or a clipped round), so this one ends the round's reduction as
         // fa_reduce_parts does -- a following fa_finalize* only copies out
         if (p->n_submitted != p->D)
             return fail(FA_ERR_STATE, "part %d: %d of %d clients submitted", part_id, p->n_submitted, p->D);

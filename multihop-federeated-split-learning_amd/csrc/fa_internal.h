@@ -107,6 +107,17 @@ struct OptHyper {
 hipError_t launch_server_opt(int rule, const OptHyper& h, const float* avg, float* x, float* m, float* v, void* out,
                              fa_dtype odt, int64_t head, int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu,
                              hipStream_t s);
+// The clip stage's norm pass (fa.h "Clip stage"), fa_clip.hip.  sums[k] = sum_i ((double)fl32(x_{k,i} - ref_i))^2
+// over the n elements of clients t.src[0..nc), 1 <= nc <= kMaxClients (weights not read): one launch over all
+// clients writes one fp64 partial per (client, workgroup) into `partials` (room for nc * kClipMaxPartials
+// doubles), a second one adds each client's partials in a fixed order.  No atomics.  head / nvec / vector_ok:
+// the split of reduce_on, ref sharing the clients' 16-byte phase.
+constexpr int64_t kClipMaxBlocks = 2048;  // 8 workgroups per CU on 256 CUs; tiles beyond it are strided
+constexpr int64_t kClipMaxPartials = kClipMaxBlocks + 1;  // per client: the grid's, plus one for head and tail
+hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const float* ref, int64_t head, int64_t nvec,
+                             int64_t n, bool vector_ok, double* partials, double* sums, const Tuning& tu, hipStream_t s);
+// dst[i] = src[i] widened to fp32 exactly (the part's output into its reference; signed zeros kept).
+hipError_t launch_clip_widen(const void* src, fa_dtype dt, float* dst, int64_t n, hipStream_t s);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, int64_t head, int64_t nvec,
                        int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);

@@ -28,6 +28,8 @@
 // --server-opt momentum|adagrad|adam|yogi puts a server optimizer (fa.h "Server optimizer") behind the
 // aggregate of every bucket: the global model and its moments stay on the GPU in fp32 across rounds, and
 // --server-state FILE carries them across restarts.
+// --clip-norm C bounds every owner's update (its receipt minus the global model it was last sent) to an L2
+// norm of C before the FedAvg chain (fa.h "Clip stage"); --clip-state FILE carries that model across restarts.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -88,6 +90,11 @@ struct Options {
     fa_server_opt server{FA_OPT_NONE, 0.0f, 0.9f, 0.99f, 1e-3f};
     bool server_lr_given = false, server_flag = false;  // server_flag: some --server-* other than --server-opt
     std::string server_state;
+    // --clip-norm C: the clip stage of every bucket (fa_set_clip on the context, before any bucket is defined);
+    // --clip-state FILE: the buckets' references, read at startup if it exists, rewritten after every round
+    float clip_norm = 0.0f;
+    bool clip_given = false;
+    std::string clip_state;
 };
 
 const char* server_rule_name(int rule) {
@@ -164,6 +171,62 @@ bool write_server_state(const std::string& path, int rule, const ServerState& st
     return std::rename(tmp.c_str(), path.c_str()) == 0;
 }
 
+// --clip-state FILE, little-endian: "FACLIPRF", u32 version = 1, u32 n_parts; then per part i32 part id (the
+// protocol's model_part), u32 0, u64 n, and the reference (n fp32).
+using ClipState = std::map<int, std::vector<float>>;
+constexpr char kClipMagic[8] = {'F', 'A', 'C', 'L', 'I', 'P', 'R', 'F'};
+
+// Reads FILE into *out.  A file that does not exist is an empty state (true); a bad magic or version or a
+// truncated file is an error (false, *err says which).
+bool read_clip_state(const std::string& path, ClipState* out, std::string* err) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return true;
+    f.seekg(0, std::ios::end);
+    const uint64_t size = (uint64_t)f.tellg();
+    f.seekg(0);
+    char magic[8];
+    uint32_t hdr[2];
+    if (!f.read(magic, 8) || !f.read(reinterpret_cast<char*>(hdr), 8)) return *err = "shorter than its header", false;
+    if (std::memcmp(magic, kClipMagic, 8) != 0) return *err = "bad magic (not a FACLIPRF file)", false;
+    if (hdr[0] != 1) return *err = "version " + std::to_string(hdr[0]) + ", expected 1", false;
+    uint64_t at = 16;
+    for (uint32_t i = 0; i < hdr[1]; ++i) {
+        int32_t id[2];
+        uint64_t n;
+        if (!f.read(reinterpret_cast<char*>(id), 8) || !f.read(reinterpret_cast<char*>(&n), 8))
+            return *err = "truncated at part " + std::to_string(i), false;
+        at += 16;
+        if (n > (size - at) / 4) return *err = "part " + std::to_string(id[0]) + " runs past the end of the file", false;
+        std::vector<float>& g = (*out)[id[0]];
+        g.resize((size_t)n);
+        if (n && !f.read(reinterpret_cast<char*>(g.data()), (std::streamsize)(n * 4)))
+            return *err = "truncated in part " + std::to_string(id[0]), false;
+        at += n * 4;
+    }
+    return true;
+}
+
+// Writes FILE.tmp and renames it over FILE, so a reader never sees half a state.
+bool write_clip_state(const std::string& path, const ClipState& st) {
+    const std::string tmp = path + ".tmp";
+    {
+        std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
+        const uint32_t hdr[2] = {1, (uint32_t)st.size()};
+        f.write(kClipMagic, 8);
+        f.write(reinterpret_cast<const char*>(hdr), 8);
+        for (auto& kv : st) {
+            const int32_t id[2] = {kv.first, 0};
+            const uint64_t n = kv.second.size();
+            f.write(reinterpret_cast<const char*>(id), 8);
+            f.write(reinterpret_cast<const char*>(&n), 8);
+            f.write(reinterpret_cast<const char*>(kv.second.data()), (std::streamsize)(n * 4));
+        }
+        f.flush();
+        if (!f) return false;
+    }
+    return std::rename(tmp.c_str(), path.c_str()) == 0;
+}
+
 void usage() {
     std::cerr << "usage: fa_aggregator -i ID -d DATA_OWNERS -c COMPUTE_NODES [--mode fedavg|literal|trimmed|median]\n"
                  "       [--trim T] [--gpus G]\n"
@@ -173,6 +236,7 @@ void usage() {
                  "       [--senders S] [--stream-min-bytes N] [--crc gpu|host] [--test-shared-device]\n"
                  "       [--server-opt momentum|adagrad|adam|yogi --server-lr L [--server-beta1 B] [--server-beta2 B]\n"
                  "        [--server-tau T] [--server-state FILE]]\n"
+                 "       [--clip-norm C [--clip-state FILE]]\n"
                  "--mode trimmed: per element the T lowest and T highest of the owners' values are dropped and the\n"
                  "rest averaged (2T < DATA_OWNERS <= 128; without --trim, and with --mode median, the median), so up\n"
                  "to T owners that send NaN, inf or huge values change no reply; --samples is ignored; not with\n"
@@ -182,6 +246,11 @@ void usage() {
                  "[0, 1) (defaults 0.9 and 0.99), T finite and > 0 (default 1e-3); --server-state FILE is read at startup\n"
                  "if it exists (the initial global model, the moments of an earlier run) and rewritten after every\n"
                  "round; not with --mode literal or --layout rs.\n"
+                 "--clip-norm C: every owner's update (its receipt minus the global model it was last sent) is scaled\n"
+                 "down to an L2 norm of at most C (finite and > 0) before the weighted average, and an owner whose\n"
+                 "update holds a NaN or an inf is left out of the round; the first round of a bucket without a stored\n"
+                 "model clips nothing; --clip-state FILE is read at startup if it exists (the model last sent) and\n"
+                 "rewritten after every round; not with --mode literal|trimmed|median or --layout rs.\n"
                  "A bucket takes the dtype of its first receipt's parameters (all fp32, all bf16 or all fp16, by\n"
                  "their storage type) and is reduced and replied in it; a later receipt of another size or dtype\n"
                  "ends the process (exit 1).\n";
@@ -258,6 +327,11 @@ bool parse_args(int argc, char** argv, Options* o) {
         } else if (a == "--server-state") {
             o->server_state = val("--server-state");
             o->server_flag = true;
+        } else if (a == "--clip-norm") {
+            o->clip_norm = (float)std::atof(val("--clip-norm"));
+            o->clip_given = true;
+        } else if (a == "--clip-state") {
+            o->clip_state = val("--clip-state");
         } else if (a == "--trim") {
             o->trim = std::atoi(val("--trim"));
             o->trim_given = true;
@@ -331,6 +405,25 @@ bool parse_args(int argc, char** argv, Options* o) {
             return false;
         }
     }
+    if (!o->clip_given && !o->clip_state.empty()) {
+        std::cerr << "--clip-state goes with --clip-norm\n";
+        return false;
+    }
+    if (o->clip_given) {
+        if (o->mode != FA_FEDAVG) {
+            std::cerr << "--clip-norm clips the updates of a weighted average: not with --mode "
+                      << (o->mode == FA_LITERAL ? "literal" : o->median ? "median" : "trimmed") << "\n";
+            return false;
+        }
+        if (o->rs) {
+            std::cerr << "--clip-norm needs a bit-specified aggregate: not with --layout rs\n";
+            return false;
+        }
+        if (!std::isfinite(o->clip_norm) || !(o->clip_norm > 0)) {
+            std::cerr << "--clip-norm " << o->clip_norm << ": finite and > 0\n";
+            return false;
+        }
+    }
     return o->data_owners >= 1 && o->stall_report_s > 0 && o->receipt_timeout_s >= 0;
 }
 
@@ -368,8 +461,8 @@ constexpr size_t kGpuCrcMinBytes = 1u << 20;
 
 class Aggregator {
 public:
-    Aggregator(const Options& o, NetLayer* net, const std::vector<int>& owners, ServerState loaded)
-        : o_(o), net_(net), loaded_(std::move(loaded)) {
+    Aggregator(const Options& o, NetLayer* net, const std::vector<int>& owners, ServerState loaded, ClipState clip_loaded)
+        : o_(o), net_(net), loaded_(std::move(loaded)), clip_loaded_(std::move(clip_loaded)) {
         int flags = o.rs ? FA_SHARD_CLIENT_RS : o.gpus > 1 ? FA_SHARD_RANGE : 0;
         if (o.eager) flags |= FA_ACCUMULATE_ON_ARRIVAL;
         if (o.shared_device) {
@@ -381,6 +474,7 @@ public:
         FA_CHECK(fa_set_literal_divisor(ctx_, -1, o.divisor));
         if (o.mode == FA_TRIMMED) FA_CHECK(fa_set_trim(ctx_, -1, o.trim));
         if (o.server.rule != FA_OPT_NONE) FA_CHECK(fa_set_server_opt(ctx_, -1, &o.server));  // before any bucket
+        if (o.clip_given) FA_CHECK(fa_set_clip(ctx_, -1, o.clip_norm));
         if (o.rs_chunks > 0) {
             fa_tuning t{};
             t.rs_chunks = o.rs_chunks;
@@ -517,6 +611,16 @@ public:
                 FA_CHECK(fa_server_opt_set_state(ctx_, r.model_part, sp.x.data(), sp.m.data(),
                                                  o_.server.rule == FA_OPT_MOMENTUM ? nullptr : sp.v.data(), sp.steps));
             }
+            auto lc = clip_loaded_.find(r.model_part);
+            if (lc != clip_loaded_.end()) {  // --clip-state: the model this bucket's owners were last sent
+                if (lc->second.size() != b.numel) {
+                    std::cerr << "[aggregator] --clip-state: part " << r.model_part << " holds " << lc->second.size()
+                              << " elements, its bucket " << b.numel << "\n";
+                    net_->stop();  // as for --server-state above
+                    std::exit(1);
+                }
+                FA_CHECK(fa_clip_set_reference(ctx_, r.model_part, lc->second.data()));
+            }
         } else if ((size_t)ar.param_numel() != b.numel || pd != b.dtype) {
             std::cerr << "[aggregator] bucket " << r.model_part << " changed size or dtype\n";
             std::exit(1);
@@ -611,6 +715,15 @@ public:
                 std::exit(1);
             }
         }
+        if (o_.clip_given) {  // what the clip stage did to this bucket's receipts, for the round line
+            std::vector<double>& q = clip_q_[mp];
+            q.assign((size_t)o_.data_owners, 0.0);
+            std::vector<int> inc((size_t)o_.data_owners, 1);
+            int clipped = 0;
+            FA_CHECK(fa_clip_get_round(ctx_, mp, q.data(), nullptr, inc.data(), &clipped));
+            clip_clipped_ += (unsigned long long)clipped;
+            for (int i : inc) clip_excluded_ += i ? 0 : 1;
+        }
         b.held.clear();
         b.arrived.clear();
         b.bytes_in = 0;
@@ -650,6 +763,44 @@ public:
             std::exit(1);
         }
         return most;
+    }
+
+    // --clip-norm: the round line's tail -- the receipts scaled down and left out this round and every
+    // bucket's squared distances in slot order (17 significant digits: they read back to the same doubles) --
+    // and, with --clip-state, every defined bucket's reference written to FILE.tmp and renamed over FILE (parts
+    // read at startup and never defined in this run are carried over as read).
+    std::string clip_tail() {
+        std::ostringstream os;
+        os << ",\"clip_norm\":" << o_.clip_norm << ",\"clipped\":" << clip_clipped_ << ",\"excluded\":" << clip_excluded_
+           << ",\"clip_sumsq\":{";
+        bool first = true;
+        for (auto& kv : clip_q_) {
+            os << (first ? "" : ",") << "\"" << kv.first << "\":[";
+            first = false;
+            for (size_t k = 0; k < kv.second.size(); ++k) {
+                char buf[40];
+                if (std::isfinite(kv.second[k])) snprintf(buf, sizeof buf, "%.17g", kv.second[k]);
+                else snprintf(buf, sizeof buf, "\"%s\"", std::isnan(kv.second[k]) ? "nan" : "inf");
+                os << (k ? "," : "") << buf;
+            }
+            os << "]";
+        }
+        os << "}";
+        clip_clipped_ = clip_excluded_ = 0;
+        clip_q_.clear();
+        if (!o_.clip_state.empty()) {
+            for (auto& kv : buckets_) {
+                if (!kv.second.defined) continue;
+                std::vector<float>& g = clip_loaded_[kv.first];
+                g.assign(kv.second.numel, 0.0f);
+                FA_CHECK(fa_clip_get_reference(ctx_, kv.first, g.data()));
+            }
+            if (!write_clip_state(o_.clip_state, clip_loaded_)) {
+                std::cerr << "[aggregator] --clip-state: cannot write " << o_.clip_state << "\n";
+                std::exit(1);
+            }
+        }
+        return os.str();
     }
 
     size_t bytes_in(int mp) { return buckets_[mp].bytes_in; }
@@ -820,6 +971,10 @@ private:
     fa_ctx* ctx_ = nullptr;
     std::map<int, Bucket> buckets_;
     ServerState loaded_;  // --server-state: as read at startup, then as last written
+    ClipState clip_loaded_;  // --clip-state: likewise
+    // --clip-norm: this round's clipped and excluded receipts and each bucket's squared distances (clip_tail)
+    unsigned long long clip_clipped_ = 0, clip_excluded_ = 0;
+    std::map<int, std::vector<double>> clip_q_;
     std::map<int, int> slots_;  // client id -> slot
     std::vector<char> claimed_;  // slot -> an arrived client holds it
     std::vector<int> expected_;  // the data owners' ids in slot order
@@ -888,6 +1043,15 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    ClipState clip_state;  // likewise
+    if (!o.clip_state.empty()) {
+        std::string why;
+        if (!read_clip_state(o.clip_state, &clip_state, &why)) {
+            std::cerr << "--clip-state " << o.clip_state << ": " << why << "\n";
+            usage();
+            return 2;
+        }
+    }
     if (o.mode == FA_TRIMMED && !o.samples.empty())
         std::cerr << "[aggregator] warning: --samples is ignored with --mode trimmed|median (the rule has no weights)\n";
     // pinned frame buffers: receipts DMA'd from, replies DMA'd into -- small ones too (from 4 KiB): a small
@@ -922,7 +1086,7 @@ int main(int argc, char** argv) {
     const int L = o.last_layers > 0 ? o.last_layers : last_part_layers(refactor.model_name, refactor.start);
     std::cerr << "[aggregator] refactor: model " << refactor.model_name << "/" << refactor.model_type << " start "
               << refactor.start << " end " << refactor.end << " -> " << L << " last-part layer(s)\n";
-    Aggregator agg(o, &net, refactor.data_owners, std::move(server_state));
+    Aggregator agg(o, &net, refactor.data_owners, std::move(server_state), std::move(clip_state));
 
     // the round line names the rule only where it is not a mean (lines of the other modes stay as they were)
     const std::string mode_tail =
@@ -1002,16 +1166,17 @@ int main(int argc, char** argv) {
                      server_rule_name(o.server.rule), (double)o.server.lr, agg.save_server_state());
             server_tail = buf;
         }
+        const std::string clip_tail = o.clip_given ? agg.clip_tail() : std::string();
         printf("{\"round\":%d,\"phase1\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f},"
                "\"phase2\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,\"layers\":%d,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f,\"send_s\":%.6f},"
                "\"send_failures\":%llu,\"stale_dropped\":%llu,\"ignored\":%llu,\"replaced\":%llu,"
-               "\"clock_back\":%llu,\"streamed\":%llu,\"stream_fallbacks\":%llu,\"streamed_bytes\":%llu%s%s}\n",
+               "\"clock_back\":%llu,\"streamed\":%llu,\"stream_fallbacks\":%llu,\"streamed_bytes\":%llu%s%s%s}\n",
                round, recv1, red1, in1, s1.absorb_s, s1.finalize_s, s1.frame_s, recv2, red2, in2, L, s2.absorb_s,
                s2.finalize_s, s2.frame_s, send2, (unsigned long long)net.send_failures(), agg.stale_dropped(), agg.ignored(),
                agg.replaced(), agg.clock_back(), agg.streamed(), agg.stream_fallbacks(), agg.streamed_bytes(),
-               mode_tail.c_str(), server_tail.c_str());
+               mode_tail.c_str(), server_tail.c_str(), clip_tail.c_str());
         fflush(stdout);
     }
     net.stop();
