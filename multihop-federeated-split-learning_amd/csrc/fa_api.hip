@@ -365,6 +365,20 @@ struct fa_ctx {
 
 namespace {
 
+// What a fa_*_device entry runs on (gpu checked against ctx->G before): the ctx's GPU `gpu`, hip_stream or that
+// GPU's compute stream, the ctx's tuning; without a ctx HIP device `gpu`, the defaults, g = 0.  No device call.
+struct DeviceCall {
+    int dev, g;
+    hipStream_t s;
+    fa::Tuning tu;
+};
+DeviceCall device_call(fa_ctx* ctx, int gpu, void* hip_stream) {
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (!ctx) return DeviceCall{gpu, 0, s, defaults().tu};
+    const GpuRes& r = ctx->gpu[(size_t)gpu];
+    return DeviceCall{r.dev, gpu, s ? s : r.compute, ctx->tuning.tu};
+}
+
 // Scratch of at least `bytes` on GPU g (only used by a 16-bit output with D > kMaxClients).
 int ensure_scratch(fa_ctx* ctx, int g, size_t bytes) {
     GpuRes& r = ctx->gpu[g];
@@ -391,6 +405,25 @@ float mode_arg(fa_mode mode, float divisor, int trim, int D) {
 
 bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
+// A client pointer array (`what`: "client", "client slot"): there, every entry non-null and aligned to its element.
+int check_clients(const void* const* ptrs, int D, size_t elem, const char* what) {
+    if (!ptrs) return fail(FA_ERR_ARG, "client array is null");
+    for (int k = 0; k < D; ++k) {
+        if (!ptrs[k]) return fail(FA_ERR_ARG, "%s pointer %d is null", what, k);
+        if (!aligned(ptrs[k], elem)) return fail(FA_ERR_ALIGN, "%s %d not %zu-byte aligned", what, k, elem);
+    }
+    return FA_OK;
+}
+// Clients [k0, k0 + nc) of ptrs with their weights (w null: 0.0f, for the launches that read none).
+fa::ClientTable client_table(const void* const* ptrs, const float* w, int k0, int nc) {
+    fa::ClientTable t;
+    for (int k = 0; k < nc; ++k) {
+        t.src[k] = ptrs[k0 + k];
+        t.w[k] = w ? w[k0 + k] : 0.0f;
+    }
+    return t;
+}
+
 // ------------------------------------------------------------------ server optimizer
 
 inline bool opt_adaptive(int rule) { return rule == FA_OPT_ADAGRAD || rule == FA_OPT_ADAM || rule == FA_OPT_YOGI; }
@@ -415,19 +448,17 @@ fa::OptHyper opt_hyper(const fa_server_opt& o) {
     return fa::OptHyper{o.lr, o.beta1, o.beta2, o.tau, c1, c2};
 }
 
-// One launch of the stage on the current device: `rule` (or fa::kOptBoot) over n elements, split as reduce_on
-// splits a bucket -- the vector form where avg, the state and the output share one 16-byte phase.
+// One launch of the stage on the current device: `rule` (or fa::kOptBoot) over n elements, split (fa_split.h)
+// with avg in the lead -- the vector form where the state and the output allow it too.
 int opt_on(const fa::Tuning& tu, int rule, const fa_server_opt& o, const float* avg, float* x, float* m, float* v,
            size_t n, void* out, fa_dtype odt, hipStream_t s) {
     if (n == 0) return FA_OK;
-    const size_t phase = ((uintptr_t)avg % 16) / 4;
-    int64_t head = (int64_t)((4 - phase) % 4);
-    if ((size_t)head > n) head = (int64_t)n;
-    const int64_t nvec = (int64_t)(n - (size_t)head) / 4;
-    bool vec = ((uintptr_t)x % 16) / 4 == phase && ((uintptr_t)m % 16) / 4 == phase;
-    if (v) vec = vec && ((uintptr_t)v % 16) / 4 == phase;
-    if (out) vec = vec && ((uintptr_t)out + (size_t)head * dsize(odt)) % (4 * dsize(odt)) == 0;
-    FA_HIP(fa::launch_server_opt(rule, opt_hyper(o), avg, x, m, v, out, odt, head, nvec, (int64_t)n, vec, tu, s));
+    fa::Split sp = fa::split_at(avg, 4, n);
+    sp.require_input(x);
+    sp.require_input(m);
+    if (v) sp.require_input(v);
+    if (out) sp.require(out, dsize(odt));
+    FA_HIP(fa::launch_server_opt(rule, opt_hyper(o), avg, x, m, v, out, odt, sp, tu, s));
     return FA_OK;
 }
 
@@ -438,36 +469,26 @@ int reduce_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clien
               fa_dtype in, void* dst, fa_dtype out, fa_mode mode, float divisor, const float* init, hipStream_t s) {
     if (n == 0) return FA_OK;
     const size_t si = dsize(in), so = dsize(out);
-    const int V = (int)(16 / si);
-    for (int k = 0; k < D; ++k)
-        if (!clients[k]) return fail(FA_ERR_ARG, "client pointer %d is null", k);
+    if (int rc = check_clients(clients, D, si, "client")) return rc;
     if (!dst) return fail(FA_ERR_ARG, "output pointer is null");
-    for (int k = 0; k < D; ++k)
-        if (!aligned(clients[k], si)) return fail(FA_ERR_ALIGN, "client %d not %zu-byte aligned", k, si);
     if (!aligned(dst, so)) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", so);
     if (init && !aligned(init, 4)) return fail(FA_ERR_ALIGN, "init not 4-byte aligned");
 
-    // Vector path: every input shares one 16-byte phase; head elements bring it to 0.
-    const size_t phase = ((uintptr_t)clients[mode == FA_LITERAL ? D - 1 : 0] % 16) / si;
-    int64_t head = (int64_t)((V - phase) % V);
-    if ((size_t)head > n) head = (int64_t)n;
-    const int64_t nvec = (int64_t)(n - (size_t)head) / V;
-    bool vec = true;
+    // The split (fa_split.h): FA_LITERAL reads its last client alone, every other mode all of them.
+    fa::Split sp = fa::split_at(clients[mode == FA_LITERAL ? D - 1 : 0], si, n);
     if (mode != FA_LITERAL)
-        for (int k = 0; k < D; ++k) vec = vec && (((uintptr_t)clients[k] % 16) / si == phase);
-    const size_t out_vec_bytes = (size_t)V * so;  // 16 or 32 (f32 out of 16-bit) or 8 (16-bit out of f32)
-    vec = vec && ((uintptr_t)dst + (size_t)head * so) % std::min<size_t>(16, out_vec_bytes) == 0;
-    if (init) vec = vec && ((uintptr_t)init + (size_t)head * 4) % 16 == 0;
+        for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
+    sp.require(dst, so);
+    if (init) sp.require(init, 4);
 
     if (mode == FA_LITERAL) {
-        FA_HIP(fa::launch_literal(clients[D - 1], in, dst, out, divisor, head, nvec, (int64_t)n, vec, tu, s));
+        FA_HIP(fa::launch_literal(clients[D - 1], in, dst, out, divisor, sp, tu, s));
         return FA_OK;
     }
     if (mode == FA_TRIMMED) {
         if (D > FA_TRIMMED_MAX_CLIENTS) return fail(FA_ERR_ARG, "trimmed mean of D = %d clients (at most %d)", D, FA_TRIMMED_MAX_CLIENTS);
-        fa::ClientTable t;
-        for (int k = 0; k < D; ++k) t.src[k] = clients[k];
-        FA_HIP(fa::launch_trimmed(t, D, in, out, (int)divisor, dst, head, nvec, (int64_t)n, vec, tu, s));
+        const fa::ClientTable t = client_table(clients, nullptr, 0, D);
+        FA_HIP(fa::launch_trimmed(t, D, in, out, (int)divisor, dst, sp, tu, s));
         return FA_OK;
     }
 
@@ -481,20 +502,16 @@ int reduce_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clien
             int rc = ensure_scratch(ctx, g, n * 4);
             if (rc) return rc;
             acc = static_cast<float*>(ctx->gpu[g].scratch);
-            vec = vec && ((uintptr_t)acc + (size_t)head * 4) % 16 == 0;
+            sp.require(acc, 4);
         }
     }
     for (int p = 0; p < passes; ++p) {
-        fa::ClientTable t;
         const int k0 = p * fa::kMaxClients, nc = std::min(fa::kMaxClients, D - k0);
-        for (int k = 0; k < nc; ++k) {
-            t.src[k] = clients[k0 + k];
-            t.w[k] = w[k0 + k];
-        }
+        const fa::ClientTable t = client_table(clients, w, k0, nc);
         const float* pin = p == 0 ? init : acc;
         const bool last = p == passes - 1;
         void* pdst = last ? dst : acc;
-        FA_HIP(fa::launch_chain(t, nc, in, last ? out : FA_F32, pin, pdst, head, nvec, (int64_t)n, vec, tu, s));
+        FA_HIP(fa::launch_chain(t, nc, in, last ? out : FA_F32, pin, pdst, sp, tu, s));
     }
     return FA_OK;
 }
@@ -504,42 +521,26 @@ int reduce_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clien
 int sync_on(fa_ctx* ctx, int g, const fa::Tuning& tu, void* const* slots, const float* w, int D, size_t n,
             fa_dtype dt, hipStream_t s) {
     if (n == 0) return FA_OK;
-    const size_t si = dsize(dt);
-    const int V = (int)(16 / si);
-    for (int k = 0; k < D; ++k) {
-        if (!slots[k]) return fail(FA_ERR_ARG, "client slot pointer %d is null", k);
-        if (!aligned(slots[k], si)) return fail(FA_ERR_ALIGN, "client slot %d not %zu-byte aligned", k, si);
-    }
+    const void* const* srcs = (const void* const*)slots;
+    if (int rc = check_clients(srcs, D, dsize(dt), "client slot")) return rc;
     if (D > fa::kMaxClients) {
         if (!ctx) return fail(FA_ERR_ARG, "state sync of more than %d slots needs a ctx for scratch", fa::kMaxClients);
         int rc = ensure_scratch(ctx, g, n * 4);
         if (rc) return rc;
         float* acc = static_cast<float*>(ctx->gpu[g].scratch);
-        rc = reduce_on(ctx, g, tu, (const void* const*)slots, w, D, n, dt, acc, FA_F32, FA_FEDAVG, 0.0f, nullptr, s);
+        rc = reduce_on(ctx, g, tu, srcs, w, D, n, dt, acc, FA_F32, FA_FEDAVG, 0.0f, nullptr, s);
         if (rc) return rc;
         for (int k0 = 0; k0 < D; k0 += fa::kMaxClients) {
-            fa::ClientTable t;
             const int nc = std::min(fa::kMaxClients, D - k0);
-            for (int k = 0; k < nc; ++k) {
-                t.src[k] = slots[k0 + k];
-                t.w[k] = 0.0f;
-            }
+            const fa::ClientTable t = client_table(srcs, nullptr, k0, nc);
             FA_HIP(fa::launch_broadcast(t, nc, dt, acc, (int64_t)n, tu, s));
         }
         return FA_OK;
     }
-    const size_t phase = ((uintptr_t)slots[0] % 16) / si;
-    int64_t head = (int64_t)((V - phase) % V);
-    if ((size_t)head > n) head = (int64_t)n;
-    const int64_t nvec = (int64_t)(n - (size_t)head) / V;
-    bool vec = true;
-    for (int k = 0; k < D; ++k) vec = vec && (((uintptr_t)slots[k] % 16) / si == phase);
-    fa::ClientTable t;
-    for (int k = 0; k < D; ++k) {
-        t.src[k] = slots[k];
-        t.w[k] = w[k];
-    }
-    FA_HIP(fa::launch_sync(t, D, dt, nullptr, head, nvec, (int64_t)n, vec, tu, s));
+    fa::Split sp = fa::split_at(slots[0], dsize(dt), n);
+    for (int k = 0; k < D; ++k) sp.require_input(slots[k]);
+    const fa::ClientTable t = client_table(srcs, w, 0, D);
+    FA_HIP(fa::launch_sync(t, D, dt, nullptr, sp, tu, s));
     return FA_OK;
 }
 
@@ -579,25 +580,16 @@ int ensure_clip_scratch(GpuRes& r, size_t sums) {
 
 // Enqueues the norm pass on the current device: d_sums[k] = Q_k of clients[k] (n elements of `in`) against ref,
 // k < D, in passes of kMaxClients clients; d_part: kMaxClients * kClipMaxPartials doubles of scratch.  The
-// vector form where every client and ref share one 16-byte phase (the split of reduce_on).
+// vector form where every client and ref allow it (fa_split.h).
 int clip_sumsq_on(const fa::Tuning& tu, const void* const* clients, int D, size_t n, fa_dtype in, const float* ref,
                   double* d_part, double* d_sums, hipStream_t s) {
-    const size_t si = dsize(in);
-    const int V = (int)(16 / si);
-    const size_t phase = ((uintptr_t)clients[0] % 16) / si;
-    int64_t head = (int64_t)((V - phase) % V);
-    if ((size_t)head > n) head = (int64_t)n;
-    const int64_t nvec = (int64_t)(n - (size_t)head) / V;
-    bool vec = ((uintptr_t)ref + (size_t)head * 4) % 16 == 0;
-    for (int k = 0; k < D; ++k) vec = vec && (((uintptr_t)clients[k] % 16) / si == phase);
+    fa::Split sp = fa::split_at(clients[0], dsize(in), n);
+    for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
+    sp.require(ref, 4);
     for (int k0 = 0; k0 < D; k0 += fa::kMaxClients) {
-        fa::ClientTable t;
         const int nc = std::min(fa::kMaxClients, D - k0);
-        for (int k = 0; k < nc; ++k) {
-            t.src[k] = clients[k0 + k];
-            t.w[k] = 0.0f;
-        }
-        FA_HIP(fa::launch_clip_sumsq(t, nc, in, ref, head, nvec, (int64_t)n, vec, d_part, d_sums + k0, tu, s));
+        const fa::ClientTable t = client_table(clients, nullptr, k0, nc);
+        FA_HIP(fa::launch_clip_sumsq(t, nc, in, ref, sp, d_part, d_sums + k0, tu, s));
     }
     return FA_OK;
 }
@@ -680,6 +672,13 @@ inline char* piece_ptr(const Part& p, int g, int k, int j) {
     return p.pool[(size_t)g] + ((size_t)j * held + (size_t)(k - p.c0[(size_t)g])) * p.stride[(size_t)g];
 }
 inline char* slot_ptr(const Part& p, int g, int k) { return piece_ptr(p, g, k, 0); }  // one-piece parts
+// The pointer list of piece j of GPU g over clients [k0, k1), in a vector the caller keeps across pieces.
+template <typename P>
+P* const* piece_ptrs(const Part& p, int g, int j, int k0, int k1, std::vector<P*>& out) {
+    out.resize((size_t)(k1 - k0));
+    for (int k = k0; k < k1; ++k) out[(size_t)(k - k0)] = piece_ptr(p, g, k, j);
+    return out.data();
+}
 
 int check_part(fa_ctx* ctx, int part_id, Part** out) {
     if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
@@ -778,23 +777,19 @@ void set_rs_runs(Part& p, int G, int chunks) {
 // Notes the stream the part's reduction on GPU g ran on; the copy-out orders itself after it
 // (copy_output records p.done there at copy time, which covers everything enqueued so far, and waits
 // only when that stream is not its own).  Nothing is recorded in the reduction's path.
-int mark_done(fa_ctx*, Part& p, int g, hipStream_t s) {
-    p.done_stream[(size_t)g] = s;
-    return FA_OK;
-}
+void mark_done(Part& p, int g, hipStream_t s) { p.done_stream[(size_t)g] = s; }
 
 // Range layout: enqueue the ordered chain over clients [k0, k1) of part p on GPU g, continuing the
 // fp32 accumulator when k0 > 0 (accumulate on arrival) and writing the output dtype when k1 == D.
 int chain_range(fa_ctx* ctx, Part& p, int g, int k0, int k1, const float* w, hipStream_t st) {
     const bool last = k1 == p.D;
+    std::vector<const void*> ptrs;
     for (int j = 0; j < p.npiece[(size_t)g]; ++j) {
         const size_t lo = piece_lo(p, g, j);
-        std::vector<const void*> ptrs;
-        for (int k = k0; k < k1; ++k) ptrs.push_back(piece_ptr(p, g, k, j));
         const float* init = k0 > 0 ? p.acc[(size_t)g] + lo : nullptr;
         void* dst = last ? static_cast<char*>(p.dout[(size_t)g]) + lo * dsize(p.out) : (void*)(p.acc[(size_t)g] + lo);
-        int rc = reduce_on(ctx, g, ctx->tuning.tu, ptrs.data(), w + k0, k1 - k0, piece_cnt(p, g, j), p.in, dst,
-                           last ? p.out : FA_F32, FA_FEDAVG, p.divisor, init, st);
+        int rc = reduce_on(ctx, g, ctx->tuning.tu, piece_ptrs(p, g, j, k0, k1, ptrs), w + k0, k1 - k0,
+                           piece_cnt(p, g, j), p.in, dst, last ? p.out : FA_F32, FA_FEDAVG, p.divisor, init, st);
         if (rc) return rc;
     }
     return FA_OK;
@@ -1063,8 +1058,7 @@ int host_reduce(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, const Gathe
         FA_HIP(hipStreamSynchronize(st));
         return FA_OK;
     }
-    int rc = mark_done(ctx, p, 0, st);
-    if (rc) return rc;
+    mark_done(p, 0, st);
     set_range_runs(p, 1);
     return FA_OK;
 }
@@ -1082,7 +1076,7 @@ struct ClipPlan {
 // order, then piece order.  Leaves the round's report in the part.
 int clip_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, ClipPlan* plan) {
     const size_t D = (size_t)p.D;
-    std::vector<const void*> ptrs(D);
+    std::vector<const void*> ptrs;
     for (int g = 0; g < ctx->G; ++g) {
         if (p.cnt[(size_t)g] == 0) continue;
         GpuRes& r = ctx->gpu[(size_t)g];
@@ -1092,8 +1086,7 @@ int clip_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, ClipPlan* pla
         const size_t sums = (size_t)p.npiece[(size_t)g] * D;
         if (rc || (rc = ensure_clip_scratch(r, sums))) return rc;
         for (int j = 0; j < p.npiece[(size_t)g]; ++j) {
-            for (size_t k = 0; k < D; ++k) ptrs[k] = piece_ptr(p, g, (int)k, j);
-            rc = clip_sumsq_on(ctx->tuning.tu, ptrs.data(), p.D, piece_cnt(p, g, j), p.in,
+            rc = clip_sumsq_on(ctx->tuning.tu, piece_ptrs(p, g, j, 0, p.D, ptrs), p.D, piece_cnt(p, g, j), p.in,
                                p.cref[(size_t)g] + piece_lo(p, g, j), r.clip_dev + r.clip_sums,
                                r.clip_dev + (size_t)j * D, st);
             if (rc) return rc;
@@ -1200,50 +1193,40 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
             if (clipping)
                 if (int rc = clip_plan(ctx, p, w, s, &plan)) return rc;
         }
+        std::vector<const void*> ptrs;
         for (int g = 0; g < G; ++g) {
             GpuRes& r = ctx->gpu[(size_t)g];
             DeviceGuard dg(r.dev);
             hipStream_t st = s ? s : r.compute;
             int rc = wait_copies(ctx, g, st);
             if (rc) return rc;
-            for (int j = 0; j < p.npiece[(size_t)g] && !rc; ++j) {  // one launch per piece, in order
-                void* dst = static_cast<char*>(p.dout[(size_t)g]) + piece_lo(p, g, j) * dsize(p.out);
-                if (staged(p)) {
-                    // the aggregate -- clipped, if the part has a reference; with a server optimizer in fp32 (an
-                    // f32 part: in its output, where the stage then runs in place), followed by one step or the
-                    // bootstrap of a part without a master -- then the new reference, all on the same stream
-                    const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
-                    const bool opt = p.opt.rule != FA_OPT_NONE;
-                    float* avg = !opt ? nullptr : p.out == FA_F32 ? static_cast<float*>(dst) : p.oavg[(size_t)g] + lo;
-                    void* adst = opt ? (void*)avg : dst;
-                    const fa_dtype adt = opt ? FA_F32 : p.out;
-                    if (clipping) {
-                        rc = clip_chain(ctx, p, g, j, plan, adst, adt, st);
-                    } else {
-                        std::vector<const void*> ptrs;
-                        for (int k = 0; k < p.D; ++k) ptrs.push_back(piece_ptr(p, g, k, j));
-                        rc = reduce_on(ctx, g, ctx->tuning.tu, ptrs.data(), w, p.D, cnt, p.in, adst, adt, p.mode,
-                                       mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
-                    }
-                    if (!rc && opt)
-                        rc = opt_on(ctx->tuning.tu, p.opt_master ? p.opt.rule : fa::kOptBoot, p.opt, avg,
-                                    p.ox[(size_t)g] + lo, p.om[(size_t)g] + lo,
-                                    opt_adaptive(p.opt.rule) ? p.ov[(size_t)g] + lo : nullptr, cnt, dst, p.out, st);
-                    if (!rc && clip) rc = clip_take_reference(p, g, j, st);
-                    continue;
-                }
+            const fa::Tuning& tu = ctx->tuning.tu;
+            for (int j = 0; j < p.npiece[(size_t)g]; ++j) {  // one launch per piece, in order
+                const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
+                void* dst = static_cast<char*>(p.dout[(size_t)g]) + lo * dsize(p.out);
+                // the aggregate into adst (dst without a stage; FA_LITERAL never has one) -- clipped, if the part has a
+                // reference; with a server optimizer in fp32 (an f32 part: in its output, where the stage then runs in
+                // place), then one step or the bootstrap of a part without a master -- then the new reference
+                const bool opt = p.opt.rule != FA_OPT_NONE;
+                float* avg = !opt ? nullptr : p.out == FA_F32 ? static_cast<float*>(dst) : p.oavg[(size_t)g] + lo;
+                void* adst = opt ? (void*)avg : dst;
+                const fa_dtype adt = opt ? FA_F32 : p.out;
                 if (p.mode == FA_LITERAL) {
                     const void* last = piece_ptr(p, g, p.last_slot >= 0 ? p.last_slot : p.D - 1, j);
-                    rc = reduce_on(ctx, g, ctx->tuning.tu, &last, w, 1, piece_cnt(p, g, j), p.in, dst, p.out,
-                                   FA_LITERAL, p.divisor, nullptr, st);
-                } else {
-                    std::vector<const void*> ptrs;
-                    for (int k = 0; k < p.D; ++k) ptrs.push_back(piece_ptr(p, g, k, j));
-                    rc = reduce_on(ctx, g, ctx->tuning.tu, ptrs.data(), w, p.D, piece_cnt(p, g, j), p.in, dst, p.out,
-                                   p.mode, mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
-                }
+                    rc = reduce_on(ctx, g, tu, &last, w, 1, cnt, p.in, dst, p.out, FA_LITERAL, p.divisor, nullptr, st);
+                } else if (clipping)
+                    rc = clip_chain(ctx, p, g, j, plan, adst, adt, st);
+                else
+                    rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
+                                   mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
+                if (!rc && opt)
+                    rc = opt_on(tu, p.opt_master ? p.opt.rule : fa::kOptBoot, p.opt, avg, p.ox[(size_t)g] + lo,
+                                p.om[(size_t)g] + lo, opt_adaptive(p.opt.rule) ? p.ov[(size_t)g] + lo : nullptr, cnt,
+                                dst, p.out, st);
+                if (!rc && clip) rc = clip_take_reference(p, g, j, st);
+                if (rc) return rc;
             }
-            if (rc || (rc = mark_done(ctx, p, g, st))) return rc;
+            mark_done(p, g, st);
         }
         set_range_runs(p, G);
         if (p.opt.rule != FA_OPT_NONE) {  // one reducing call = one step (the first one without a master: none)
@@ -1265,7 +1248,7 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
         if (rc || (rc = reduce_on(ctx, o, ctx->tuning.tu, &last, w, 1, p.n, p.in, p.partial[(size_t)o], p.out,
                                   FA_LITERAL, p.divisor, nullptr, st)))
             return rc;
-        if ((rc = mark_done(ctx, p, o, st))) return rc;
+        mark_done(p, o, st);
         for (int g = 0; g < G; ++g) p.runs[(size_t)g].clear();
         p.runs[(size_t)o] = {Run{0, 0, p.n}};
         p.run_src[(size_t)o] = p.partial[(size_t)o];
@@ -1333,10 +1316,7 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
             if (rc) return rc;
         }
     }
-    for (int g = 0; g < G; ++g) {
-        int rc = mark_done(ctx, p, g, ctx->gpu[(size_t)g].comm);
-        if (rc) return rc;
-    }
+    for (int g = 0; g < G; ++g) mark_done(p, g, ctx->gpu[(size_t)g].comm);
     set_rs_runs(p, G, ctx->tuning.rs_chunks);
     return FA_OK;
 }
@@ -1361,7 +1341,7 @@ int advance_prefix(fa_ctx* ctx, Part& p) {
         DeviceGuard dg(r.dev);
         int rc = wait_copies(ctx, g, r.compute);
         if (rc || (rc = chain_range(ctx, p, g, p.reduced, j, p.w.data(), r.compute))) return rc;
-        if (j == p.D && (rc = mark_done(ctx, p, g, r.compute))) return rc;
+        if (j == p.D) mark_done(p, g, r.compute);
     }
     p.reduced = j;
     if (j == p.D) {
@@ -1717,7 +1697,7 @@ int finalize_impl(fa_ctx* ctx, int part_id, const Gather& dst, bool pinned) {
                 DeviceGuard dg(r.dev);
                 if ((rc = wait_copies(ctx, g, r.compute))) return rc;
                 if ((rc = chain_range(ctx, *p, g, p->reduced, p->D, p->w.data(), r.compute))) return rc;
-                if ((rc = mark_done(ctx, *p, g, r.compute))) return rc;
+                mark_done(*p, g, r.compute);
             }
             set_range_runs(*p, ctx->G);
         } else if ((rc = reduce_part(ctx, *p, p->w.data(), nullptr))) {
@@ -1872,8 +1852,7 @@ int reduce_parts_impl(fa_ctx* ctx, int n_parts, const int* ids, const float* con
                     r.seg[ti].stream = st;
                     r.seg_last = ti;
                 }
-                for (size_t m = m0; m < m1; ++m)
-                    if ((rc = mark_done(ctx, *ps[(size_t)members[m]], g, st))) return rc;
+                for (size_t m = m0; m < m1; ++m) mark_done(*ps[(size_t)members[m]], g, st);
             }
             for (size_t m = m0; m < m1; ++m) {
                 Part& p = *ps[(size_t)members[m]];
@@ -2340,12 +2319,9 @@ int fa_server_opt_device(fa_ctx* ctx, int gpu, const fa_server_opt* opt, const f
     if (!aligned(d_avg, 4) || !aligned(d_x, 4) || !aligned(d_m, 4) || (needs_v && !aligned(d_v, 4)))
         return fail(FA_ERR_ALIGN, "server opt: aggregate or state not 4-byte aligned");
     if (d_out && !aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int dev = ctx ? ctx->gpu[(size_t)gpu].dev : gpu;
-    if (!s && ctx) s = ctx->gpu[(size_t)gpu].compute;
-    DeviceGuard dg(dev);
-    const CtxTuning tu = ctx ? ctx->tuning : defaults();
-    return opt_on(tu.tu, opt->rule, *opt, d_avg, d_x, d_m, needs_v ? d_v : nullptr, n, d_out, out, s);
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    return opt_on(c.tu, opt->rule, *opt, d_avg, d_x, d_m, needs_v ? d_v : nullptr, n, d_out, out, c.s);
 }
 
 int fa_set_clip(fa_ctx* ctx, int part_id, float max_norm) {
@@ -2433,25 +2409,18 @@ int fa_clip_sumsq_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int
         std::fill(h_sumsq, h_sumsq + D, 0.0);
         return FA_OK;
     }
-    if (!d_clients) return fail(FA_ERR_ARG, "client array is null");
-    for (int k = 0; k < D; ++k) {
-        if (!d_clients[k]) return fail(FA_ERR_ARG, "client pointer %d is null", k);
-        if (!aligned(d_clients[k], dsize(in))) return fail(FA_ERR_ALIGN, "client %d not %zu-byte aligned", k, dsize(in));
-    }
+    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
     if (!d_ref) return fail(FA_ERR_ARG, "clip: d_ref is null");
     if (!aligned(d_ref, 4)) return fail(FA_ERR_ALIGN, "clip: reference not 4-byte aligned");
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int dev = ctx ? ctx->gpu[(size_t)gpu].dev : gpu;
-    if (!s && ctx) s = ctx->gpu[(size_t)gpu].compute;
-    DeviceGuard dg(dev);
-    const CtxTuning tu = ctx ? ctx->tuning : defaults();
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
     GpuRes own;  // a context-less call brings its scratch and frees it before it returns
     GpuRes& r = ctx ? ctx->gpu[(size_t)gpu] : own;
     int rc = ensure_clip_scratch(r, (size_t)D);
-    if (!rc) rc = clip_sumsq_on(tu.tu, d_clients, D, n, in, d_ref, r.clip_dev + r.clip_sums, r.clip_dev, s);
+    if (!rc) rc = clip_sumsq_on(c.tu, d_clients, D, n, in, d_ref, r.clip_dev + r.clip_sums, r.clip_dev, c.s);
     hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(r.clip_host, r.clip_dev, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
+    if (!rc) e = hipMemcpyAsync(r.clip_host, r.clip_dev, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, c.s);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c.s);
     if (!rc && e == hipSuccess) std::copy(r.clip_host, r.clip_host + D, h_sumsq);
     if (!ctx) {
         if (own.clip_dev) (void)hipFree(own.clip_dev);
@@ -2833,13 +2802,10 @@ int fa_reduce_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const f
     if (mode == FA_TRIMMED) return fail(FA_ERR_ARG, "fa_reduce_device has no trim argument: use fa_trimmed_device");
     if (mode != FA_FEDAVG && mode != FA_LITERAL) return fail(FA_ERR_ARG, "bad mode");
     if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int dev = ctx ? ctx->gpu[(size_t)gpu].dev : gpu;
-    if (!s && ctx) s = ctx->gpu[(size_t)gpu].compute;
-    DeviceGuard dg(dev);
-    const CtxTuning tu = ctx ? ctx->tuning : defaults();
-    return reduce_on(ctx, ctx ? gpu : 0, tu.tu, d_clients, h_weights, D, n, in, d_out, out, mode,
-                     ctx ? ctx->divisor : FA_DEFAULT_DIVISOR, d_init, s);
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    return reduce_on(ctx, c.g, c.tu, d_clients, h_weights, D, n, in, d_out, out, mode,
+                     ctx ? ctx->divisor : FA_DEFAULT_DIVISOR, d_init, c.s);
 }
 
 int fa_trimmed_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, void* d_out,
@@ -2852,20 +2818,13 @@ int fa_trimmed_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D,
     FA_PAIR(in, out);
     if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
     if (n == 0) return FA_OK;
-    if (!d_clients) return fail(FA_ERR_ARG, "client array is null");
-    for (int k = 0; k < D; ++k) {
-        if (!d_clients[k]) return fail(FA_ERR_ARG, "client pointer %d is null", k);
-        if (!aligned(d_clients[k], dsize(in))) return fail(FA_ERR_ALIGN, "client %d not %zu-byte aligned", k, dsize(in));
-    }
+    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
     if (!d_out) return fail(FA_ERR_ARG, "output pointer is null");
     if (!aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int dev = ctx ? ctx->gpu[(size_t)gpu].dev : gpu;
-    if (!s && ctx) s = ctx->gpu[(size_t)gpu].compute;
-    DeviceGuard dg(dev);
-    const CtxTuning tu = ctx ? ctx->tuning : defaults();
-    return reduce_on(ctx, ctx ? gpu : 0, tu.tu, d_clients, nullptr, D, n, in, d_out, out, FA_TRIMMED,
-                     mode_arg(FA_TRIMMED, 0.0f, trim, D), nullptr, s);
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    return reduce_on(ctx, c.g, c.tu, d_clients, nullptr, D, n, in, d_out, out, FA_TRIMMED,
+                     mode_arg(FA_TRIMMED, 0.0f, trim, D), nullptr, c.s);
 }
 
 int fa_sync_device(fa_ctx* ctx, int gpu, void* const* d_clients, const float* h_weights, int D, size_t n, fa_dtype dt,
@@ -2875,14 +2834,9 @@ int fa_sync_device(fa_ctx* ctx, int gpu, void* const* d_clients, const float* h_
     if (D < 1) return fail(FA_ERR_ARG, "D must be >= 1");
     if (!dvalid(dt)) return fail(FA_ERR_ARG, "bad dtype");
     if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (!s && ctx) s = ctx->gpu[(size_t)gpu].compute;
-    if (ctx) {
-        DeviceGuard dg(ctx->gpu[(size_t)gpu].dev);
-        return sync_on(ctx, gpu, ctx->tuning.tu, d_clients, h_weights, D, n, dt, s);
-    }
-    const CtxTuning tu = defaults();
-    return sync_on(nullptr, gpu, tu.tu, d_clients, h_weights, D, n, dt, s);
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(ctx ? c.dev : -1);  // without a ctx: the caller's current device, whatever `gpu` says
+    return sync_on(ctx, c.g, c.tu, d_clients, h_weights, D, n, dt, c.s);
 }
 
 int fa_sync_part(fa_ctx* ctx, int part_id, const float* h_weights, void* hip_stream) {
@@ -2895,15 +2849,16 @@ int fa_sync_part(fa_ctx* ctx, int part_id, const float* h_weights, void* hip_str
     if (hip_stream && ctx->G != 1) return fail(FA_ERR_ARG, "an explicit stream needs a single-GPU ctx");
     const float* w = h_weights ? h_weights : p->w.data();
     if ((rc = host_flush(ctx, *p))) return rc;  // the sync works on the slots
-    std::vector<void*> ptrs((size_t)p->D);
+    std::vector<void*> ptrs;
     for (int g = 0; g < ctx->G; ++g) {
         GpuRes& r = ctx->gpu[(size_t)g];
         DeviceGuard dg(r.dev);
         hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : r.compute;
         if ((rc = wait_copies(ctx, g, st))) return rc;  // the slots' submits land first
         for (int j = 0; j < p->npiece[(size_t)g]; ++j) {
-            for (int k = 0; k < p->D; ++k) ptrs[(size_t)k] = piece_ptr(*p, g, k, j);
-            if ((rc = sync_on(ctx, g, ctx->tuning.tu, ptrs.data(), w, p->D, piece_cnt(*p, g, j), p->in, st))) return rc;
+            void* const* slots = piece_ptrs(*p, g, j, 0, p->D, ptrs);
+            rc = sync_on(ctx, g, ctx->tuning.tu, slots, w, p->D, piece_cnt(*p, g, j), p->in, st);
+            if (rc) return rc;
         }
     }
     return FA_OK;

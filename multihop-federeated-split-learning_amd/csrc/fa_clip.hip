@@ -195,28 +195,27 @@ int64_t blocks_of(int64_t tiles, const Tuning& tu) {
 struct ClipGrid {
     int64_t vec_blocks, elem_blocks;
 };
-ClipGrid clip_grid(fa_dtype in, int64_t head, int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu) {
-    const int64_t V = in == FA_F32 ? 4 : 8;
-    if (vector_ok && nvec > 0) {
-        const int64_t tile_vecs = kClipTile / V, edges = head + (n - (head + nvec * V));
-        return ClipGrid{blocks_of((nvec + tile_vecs - 1) / tile_vecs, tu), edges > 0 ? 1 : 0};
+ClipGrid clip_grid(const Split& sp, const Tuning& tu) {
+    if (sp.vec && sp.nvec > 0) {
+        const int64_t tile_vecs = kClipTile / sp.V;
+        return ClipGrid{blocks_of((sp.nvec + tile_vecs - 1) / tile_vecs, tu), sp.edges() > 0 ? 1 : 0};
     }
-    return ClipGrid{0, blocks_of((n + kClipTile - 1) / kClipTile, tu)};
+    return ClipGrid{0, blocks_of((sp.n + kClipTile - 1) / kClipTile, tu)};
 }
 
 template <typename T>
-hipError_t launch_sumsq_t(const ClientTable& t, int nc, const float* ref, int64_t head, int64_t nvec, int64_t n,
-                          const ClipGrid& gr, double* partials, double* sums, hipStream_t s) {
+hipError_t launch_sumsq_t(const ClientTable& t, int nc, const float* ref, const Split& sp, const ClipGrid& gr,
+                          double* partials, double* sums, hipStream_t s) {
     const int64_t np = gr.vec_blocks + gr.elem_blocks;
     if (gr.vec_blocks > 0) {
         hipLaunchKernelGGL((clip_sumsq_vec_kernel<T>), dim3((unsigned)gr.vec_blocks), dim3(kClipThreads), 0, s, t, nc, ref,
-                           head, nvec, partials, np);
+                           sp.head, sp.nvec, partials, np);
         if (gr.elem_blocks > 0)
-            hipLaunchKernelGGL((clip_sumsq_elem_kernel<T>), dim3(1), dim3(kClipThreads), 0, s, t, nc, ref, head,
-                               head + nvec * In<T>::kVec, n, partials, np, gr.vec_blocks);
+            hipLaunchKernelGGL((clip_sumsq_elem_kernel<T>), dim3(1), dim3(kClipThreads), 0, s, t, nc, ref, sp.head,
+                               sp.tail0(), sp.n, partials, np, gr.vec_blocks);
     } else {
         hipLaunchKernelGGL((clip_sumsq_elem_kernel<T>), dim3((unsigned)gr.elem_blocks), dim3(kClipThreads), 0, s, t, nc,
-                           ref, n, n, n, partials, np, (int64_t)0);
+                           ref, sp.n, sp.n, sp.n, partials, np, (int64_t)0);
     }
     hipLaunchKernelGGL(clip_finish_kernel, dim3((unsigned)nc), dim3(64), 0, s, partials, np, np, sums);
     return hipGetLastError();
@@ -224,16 +223,15 @@ hipError_t launch_sumsq_t(const ClientTable& t, int nc, const float* ref, int64_
 
 }  // namespace
 
-hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const float* ref, int64_t head, int64_t nvec,
-                             int64_t n, bool vector_ok, double* partials, double* sums, const Tuning& tu, hipStream_t s) {
-    if (nc < 1 || nc > kMaxClients || n <= 0 || !ref || !partials || !sums) return hipErrorInvalidValue;
-    const int64_t V = in == FA_F32 ? 4 : 8;
-    if (head < 0 || nvec < 0 || head + nvec * V > n) return hipErrorInvalidValue;
-    const ClipGrid gr = clip_grid(in, head, nvec, n, vector_ok, tu);
+hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const float* ref, const Split& sp,
+                             double* partials, double* sums, const Tuning& tu, hipStream_t s) {
+    if (!sp.valid() || sp.V != (in == FA_F32 ? 4 : 8)) return hipErrorInvalidValue;
+    if (nc < 1 || nc > kMaxClients || sp.n <= 0 || !ref || !partials || !sums) return hipErrorInvalidValue;
+    const ClipGrid gr = clip_grid(sp, tu);
     switch (in) {
-        case FA_F32: return launch_sumsq_t<float>(t, nc, ref, head, nvec, n, gr, partials, sums, s);
-        case FA_BF16: return launch_sumsq_t<uint16_t>(t, nc, ref, head, nvec, n, gr, partials, sums, s);
-        case FA_F16: return launch_sumsq_t<_Float16>(t, nc, ref, head, nvec, n, gr, partials, sums, s);
+        case FA_F32: return launch_sumsq_t<float>(t, nc, ref, sp, gr, partials, sums, s);
+        case FA_BF16: return launch_sumsq_t<uint16_t>(t, nc, ref, sp, gr, partials, sums, s);
+        case FA_F16: return launch_sumsq_t<_Float16>(t, nc, ref, sp, gr, partials, sums, s);
     }
     return hipErrorInvalidValue;
 }

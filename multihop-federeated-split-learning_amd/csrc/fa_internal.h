@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fa_split.h"
 #include "fedavg/fa.h"
 
 namespace fa {
@@ -66,7 +67,7 @@ uint32_t crc32_mulmod(uint32_t a, uint32_t b);
 uint32_t crc32_x8n(uint64_t n);
 
 hipError_t launch_chain(const ClientTable& t, int nc, fa_dtype in, fa_dtype out, const float* init, void* dst,
-                        int64_t head, int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);
+                        const Split& sp, const Tuning& tu, hipStream_t s);
 // Meetings of the phased kernel on device `dev` that gave up waiting (the grid was not co-resident).
 hipError_t phased_timeouts(int dev, uint64_t* count);
 // FA_TIMELINE=1 diagnostic: copies the last phased launch's per-workgroup timeline (8 words each) on device
@@ -87,40 +88,39 @@ struct ChainPlan {
 };
 // cus: the device's CU count (0 = no phased kernel).
 ChainPlan plan_chain(fa_dtype in, fa_dtype out, int64_t nvec, int nc, bool vector_ok, const Tuning& tu, int cus);
-hipError_t launch_literal(const void* x, fa_dtype in, void* dst, fa_dtype out, float divisor, int64_t head,
-                          int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);
+hipError_t launch_literal(const void* x, fa_dtype in, void* dst, fa_dtype out, float divisor,
+                          const Split& sp, const Tuning& tu, hipStream_t s);
 // Coordinate-wise trimmed mean over t.src[0..nc), 1 <= nc <= FA_TRIMMED_MAX_CLIENTS, 0 <= 2 trim < nc (fa.h "FA_TRIMMED"):
 // sorted positions [trim, nc - trim) of every element, added ascending from +0, divided by nc - 2 trim.
 // Weights are not read.  fa_trimmed.hip.
-hipError_t launch_trimmed(const ClientTable& t, int nc, fa_dtype in, fa_dtype out, int trim, void* dst, int64_t head,
-                          int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);
+hipError_t launch_trimmed(const ClientTable& t, int nc, fa_dtype in, fa_dtype out, int trim, void* dst,
+                          const Split& sp, const Tuning& tu, hipStream_t s);
 // The server-optimizer stage (fa.h "Server optimizer"), fa_server_opt.hip.  One step of `rule` (an fa_opt_rule
 // other than FA_OPT_NONE, or kOptBoot: x' = avg, m' = v' = +0, v nullable) over n elements: reads avg and the
 // fp32 state x, m, v (v null and untouched for FA_OPT_MOMENTUM), writes the state and, unless out is null, x'
-// in dtype `odt`.  out may be avg itself for FA_F32.  head / nvec / vector_ok: the split of reduce_on, with 4
-// elements per vector.
+// in dtype `odt`.  out may be avg itself for FA_F32.  sp: the Split (fa_split.h) led by avg, 4 elements per
+// vector.
 constexpr int kOptBoot = 0;
 struct OptHyper {
     float lr, beta1, beta2, tau;
     float c1, c2;  // fl(1 - beta1), fl(1 - beta2), computed on the host
 };
 hipError_t launch_server_opt(int rule, const OptHyper& h, const float* avg, float* x, float* m, float* v, void* out,
-                             fa_dtype odt, int64_t head, int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu,
-                             hipStream_t s);
+                             fa_dtype odt, const Split& sp, const Tuning& tu, hipStream_t s);
 // The clip stage's norm pass (fa.h "Clip stage"), fa_clip.hip.  sums[k] = sum_i ((double)fl32(x_{k,i} - ref_i))^2
 // over the n elements of clients t.src[0..nc), 1 <= nc <= kMaxClients (weights not read): one launch over all
 // clients writes one fp64 partial per (client, workgroup) into `partials` (room for nc * kClipMaxPartials
-// doubles), a second one adds each client's partials in a fixed order.  No atomics.  head / nvec / vector_ok:
-// the split of reduce_on, ref sharing the clients' 16-byte phase.
+// doubles), a second one adds each client's partials in a fixed order.  No atomics.  sp: the Split
+// (fa_split.h) led by the first client, ref required as well.
 constexpr int64_t kClipMaxBlocks = 2048;  // 8 workgroups per CU on 256 CUs; tiles beyond it are strided
 constexpr int64_t kClipMaxPartials = kClipMaxBlocks + 1;  // per client: the grid's, plus one for head and tail
-hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const float* ref, int64_t head, int64_t nvec,
-                             int64_t n, bool vector_ok, double* partials, double* sums, const Tuning& tu, hipStream_t s);
+hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const float* ref, const Split& sp,
+                             double* partials, double* sums, const Tuning& tu, hipStream_t s);
 // dst[i] = src[i] widened to fp32 exactly (the part's output into its reference; signed zeros kept).
 hipError_t launch_clip_widen(const void* src, fa_dtype dt, float* dst, int64_t n, hipStream_t s);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
-hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, int64_t head, int64_t nvec,
-                       int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s);
+hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
+                       const Tuning& tu, hipStream_t s);
 // slots t.src[0..nc) := acc (rounded to dt).
 hipError_t launch_broadcast(const ClientTable& t, int nc, fa_dtype dt, const float* acc, int64_t n,
                             const Tuning& tu, hipStream_t s);

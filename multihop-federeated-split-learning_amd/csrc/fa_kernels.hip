@@ -663,42 +663,42 @@ constexpr int64_t kScalarMaxBlocks = 1 << 16;
 inline int64_t grid_scalar(int64_t n, const Tuning& tu) { return std::min(grid_for(n, tu), kScalarMaxBlocks); }
 
 template <typename IN, typename OUT, int U, bool LNT, int SP>
-hipError_t launch_chain_u(const ClientTable& t, int nc, const float* init, void* out, int64_t head, int64_t nvec,
-                          int64_t n, const Tuning& tu, hipStream_t s) {
-    int64_t g = grid_for(nvec > 0 ? nvec : 1, tu);
+hipError_t launch_chain_u(const ClientTable& t, int nc, const float* init, void* out, const Split& sp,
+                          const Tuning& tu, hipStream_t s) {
+    int64_t g = grid_for(sp.nvec > 0 ? sp.nvec : 1, tu);
     // the XCD walks need the one-shot grid (one vector per lane), rounded up to whole eighths
-    const int walk = (tu.walk && tu.max_blocks <= 0 && nvec >= 8 * (int64_t)tu.block) ? tu.walk : 0;
+    const int walk = (tu.walk && tu.max_blocks <= 0 && sp.nvec >= 8 * (int64_t)tu.block) ? tu.walk : 0;
     if (walk) g = (g + 7) / 8 * 8;
     if (init)
         hipLaunchKernelGGL((fedavg_chain_kernel<IN, OUT, U, LNT, SP, true>), dim3((unsigned)g), dim3(tu.block), 0, s,
-                           t, nc, init, out, head, nvec, n, walk);
+                           t, nc, init, out, sp.head, sp.nvec, sp.n, walk);
     else
         hipLaunchKernelGGL((fedavg_chain_kernel<IN, OUT, U, LNT, SP, false>), dim3((unsigned)g), dim3(tu.block), 0,
-                           s, t, nc, init, out, head, nvec, n, walk);
+                           s, t, nc, init, out, sp.head, sp.nvec, sp.n, walk);
     return hipGetLastError();
 }
 
 template <typename IN, typename OUT, bool LNT, int SP>
-hipError_t launch_chain_sp(const ClientTable& t, int nc, const float* init, void* out, int64_t head, int64_t nvec,
-                           int64_t n, const Tuning& tu, hipStream_t s) {
+hipError_t launch_chain_sp(const ClientTable& t, int nc, const float* init, void* out, const Split& sp,
+                           const Tuning& tu, hipStream_t s) {
     // D <= 8 never fills a 16-wide group: the 8-wide body (loads and FMAs interleaved by the
     // compiler) is ~2% faster there than the guarded tail group (tools/sweep.py c2, profiles/).
     const int unroll = (nc <= 8 && tu.unroll == 16) ? 8 : tu.unroll;
     switch (unroll) {
-        case 4: return launch_chain_u<IN, OUT, 4, LNT, SP>(t, nc, init, out, head, nvec, n, tu, s);
-        case 16: return launch_chain_u<IN, OUT, 16, LNT, SP>(t, nc, init, out, head, nvec, n, tu, s);
-        default: return launch_chain_u<IN, OUT, 8, LNT, SP>(t, nc, init, out, head, nvec, n, tu, s);
+        case 4: return launch_chain_u<IN, OUT, 4, LNT, SP>(t, nc, init, out, sp, tu, s);
+        case 16: return launch_chain_u<IN, OUT, 16, LNT, SP>(t, nc, init, out, sp, tu, s);
+        default: return launch_chain_u<IN, OUT, 8, LNT, SP>(t, nc, init, out, sp, tu, s);
     }
 }
 
 template <typename IN, typename OUT, bool LNT>
-hipError_t launch_chain_lnt(const ClientTable& t, int nc, const float* init, void* out, int64_t head, int64_t nvec,
-                            int64_t n, const Tuning& tu, hipStream_t s) {
+hipError_t launch_chain_lnt(const ClientTable& t, int nc, const float* init, void* out, const Split& sp,
+                            const Tuning& tu, hipStream_t s) {
     switch (tu.store_policy) {
-        case kStNt: return launch_chain_sp<IN, OUT, LNT, kStNt>(t, nc, init, out, head, nvec, n, tu, s);
-        case kStSc1: return launch_chain_sp<IN, OUT, LNT, kStSc1>(t, nc, init, out, head, nvec, n, tu, s);
-        case kStSc01: return launch_chain_sp<IN, OUT, LNT, kStSc01>(t, nc, init, out, head, nvec, n, tu, s);
-        default: return launch_chain_sp<IN, OUT, LNT, kStPlain>(t, nc, init, out, head, nvec, n, tu, s);
+        case kStNt: return launch_chain_sp<IN, OUT, LNT, kStNt>(t, nc, init, out, sp, tu, s);
+        case kStSc1: return launch_chain_sp<IN, OUT, LNT, kStSc1>(t, nc, init, out, sp, tu, s);
+        case kStSc01: return launch_chain_sp<IN, OUT, LNT, kStSc01>(t, nc, init, out, sp, tu, s);
+        default: return launch_chain_sp<IN, OUT, LNT, kStPlain>(t, nc, init, out, sp, tu, s);
     }
 }
 
@@ -796,7 +796,8 @@ int phased_skew(int RL) { return RL >= 40 ? std::min(RL / 10, RL / 2 - 1) : 0; }
 // Enqueue one phased launch on stream s, on the stream's counter slot.
 template <typename Kern>
 hipError_t phased_enqueue(PhasedDevice* d, Kern kern, int th, int RL, int RR, hipStream_t s, const ClientTable& t,
-                          int nc, const float* init, void* out, int64_t head, int64_t nvec, int64_t n) {
+                          int nc, const float* init, void* out, const Split& sp) {
+    const int64_t nvec = sp.nvec;
     bool own = false;
     const int slot = d->slot_of(s, &own);
     const int slack = d->cus / 32;  // the write part starts once all but ~3% of the workgroups have arrived
@@ -814,7 +815,7 @@ hipError_t phased_enqueue(PhasedDevice* d, Kern kern, int th, int RL, int RR, hi
     constexpr int last_meet = 0;
     // FA_TIMELINE: a launch without meetings leaves their stamps alone, so clear the previous launch's
     if (d->tl) (void)hipMemsetAsync(d->tl, 0, sizeof(unsigned long long) * 8 * d->cus, s);
-    hipLaunchKernelGGL(kern, dim3((unsigned)d->cus), dim3(th), 0, s, t, nc, init, out, head, nvec, n,
+    hipLaunchKernelGGL(kern, dim3((unsigned)d->cus), dim3(th), 0, s, t, nc, init, out, sp.head, nvec, sp.n,
                        d->sync + slot * kSyncStride, slack, rl_last, skew, skew_last, last_meet, d->tl);
     return hipGetLastError();
 }
@@ -834,13 +835,13 @@ bool phased_fits(std::atomic<int>& occ, Kern kern, int th) {
 // workgroup per CU, all co-resident -- hipErrorNotSupported if not even one fits (the caller then takes the
 // one-shot grid).
 template <typename IN, typename OUT, int REGS, int TH>
-hipError_t launch_phased_r(PhasedDevice* d, const ClientTable& t, int nc, const float* init, void* out, int64_t head,
-                           int64_t nvec, int64_t n, hipStream_t s) {
+hipError_t launch_phased_r(PhasedDevice* d, const ClientTable& t, int nc, const float* init, void* out,
+                           const Split& sp, hipStream_t s) {
     constexpr int RL = Phased<IN, REGS, TH, OUT>::RL, RR = Phased<IN, REGS, TH, OUT>::RR;
     static std::atomic<int> occ[2] = {-1, -1};  // per INIT variant
     auto kern = init ? fedavg_phased_kernel<IN, OUT, true, REGS, false, TH> : fedavg_phased_kernel<IN, OUT, false, REGS, false, TH>;
     if (!phased_fits(occ[init ? 1 : 0], kern, TH)) return hipErrorNotSupported;
-    return phased_enqueue(d, kern, TH, RL, RR, s, t, nc, init, out, head, nvec, n);
+    return phased_enqueue(d, kern, TH, RL, RR, s, t, nc, init, out, sp);
 }
 
 // Clients from which a bucket smaller than one phase takes a phase sized to it (plan_chain); fewer
@@ -879,23 +880,23 @@ hipError_t with_types(fa_dtype in, fa_dtype out, F&& f) {
 // and of bf16 / fp16 inputs (96, and 64 / 32 for their sized phases), and walk 4's 128-register form.
 template <typename IN, typename OUT>
 hipError_t launch_phased_plan(PhasedDevice* d, const ChainPlan& pl, const ClientTable& t, int nc, const float* init,
-                              void* out, int64_t head, int64_t nvec, int64_t n, hipStream_t s) {
+                              void* out, const Split& sp, hipStream_t s) {
     constexpr bool h16 = sizeof(IN) == 2;  // bf16 or fp16 input
     switch (pl.threads * 1000 + pl.regs) {
-        case 256128: return launch_phased_r<IN, OUT, 128, 256>(d, t, nc, init, out, head, nvec, n, s);
-        case 512096: return launch_phased_r<IN, OUT, 96, 512>(d, t, nc, init, out, head, nvec, n, s);
+        case 256128: return launch_phased_r<IN, OUT, 128, 256>(d, t, nc, init, out, sp, s);
+        case 512096: return launch_phased_r<IN, OUT, 96, 512>(d, t, nc, init, out, sp, s);
         default: break;
     }
     if constexpr (!h16) {
         switch (pl.threads * 1000 + pl.regs) {
-            case 256192: return launch_phased_r<IN, OUT, 192, 256>(d, t, nc, init, out, head, nvec, n, s);
-            case 256032: return launch_phased_r<IN, OUT, 32, 256>(d, t, nc, init, out, head, nvec, n, s);
+            case 256192: return launch_phased_r<IN, OUT, 192, 256>(d, t, nc, init, out, sp, s);
+            case 256032: return launch_phased_r<IN, OUT, 32, 256>(d, t, nc, init, out, sp, s);
             default: break;
         }
     } else {
         switch (pl.threads * 1000 + pl.regs) {
-            case 512064: return launch_phased_r<IN, OUT, 64, 512>(d, t, nc, init, out, head, nvec, n, s);
-            case 512032: return launch_phased_r<IN, OUT, 32, 512>(d, t, nc, init, out, head, nvec, n, s);
+            case 512064: return launch_phased_r<IN, OUT, 64, 512>(d, t, nc, init, out, sp, s);
+            case 512032: return launch_phased_r<IN, OUT, 32, 512>(d, t, nc, init, out, sp, s);
             default: break;
         }
     }
@@ -903,26 +904,26 @@ hipError_t launch_phased_plan(PhasedDevice* d, const ChainPlan& pl, const Client
 }
 
 template <typename IN, typename OUT>
-hipError_t launch_chain_t(const ClientTable& t, int nc, const float* init, void* out, int64_t head, int64_t nvec,
-                          int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
-    PhasedDevice* d = vector_ok && tu.walk >= 3 && tu.walk <= 5 ? phased_device() : nullptr;
-    const ChainPlan pl = plan_chain(dtype_of<IN>(), dtype_of<OUT>(), nvec, nc, vector_ok, tu, d ? d->cus : 0);
+hipError_t launch_chain_t(const ClientTable& t, int nc, const float* init, void* out, const Split& sp,
+                          const Tuning& tu, hipStream_t s) {
+    PhasedDevice* d = sp.vec && tu.walk >= 3 && tu.walk <= 5 ? phased_device() : nullptr;
+    const ChainPlan pl = plan_chain(dtype_of<IN>(), dtype_of<OUT>(), sp.nvec, nc, sp.vec, tu, d ? d->cus : 0);
     if (pl.kind == kPlanPhased) {
-        const hipError_t e = launch_phased_plan<IN, OUT>(d, pl, t, nc, init, out, head, nvec, n, s);
+        const hipError_t e = launch_phased_plan<IN, OUT>(d, pl, t, nc, init, out, sp, s);
         if (e != hipErrorNotSupported) return e;
     }
     if (pl.kind == kPlanScalar) {
-        const int64_t g = grid_scalar(n, tu);
+        const int64_t g = grid_scalar(sp.n, tu);
         if (init)
             hipLaunchKernelGGL((fedavg_chain_scalar_kernel<IN, OUT, true>), dim3((unsigned)g), dim3(tu.block), 0, s,
-                               t, nc, init, out, n);
+                               t, nc, init, out, sp.n);
         else
             hipLaunchKernelGGL((fedavg_chain_scalar_kernel<IN, OUT, false>), dim3((unsigned)g), dim3(tu.block), 0,
-                               s, t, nc, init, out, n);
+                               s, t, nc, init, out, sp.n);
         return hipGetLastError();
     }
-    if (tu.load_nt) return launch_chain_lnt<IN, OUT, true>(t, nc, init, out, head, nvec, n, tu, s);
-    return launch_chain_lnt<IN, OUT, false>(t, nc, init, out, head, nvec, n, tu, s);
+    if (tu.load_nt) return launch_chain_lnt<IN, OUT, true>(t, nc, init, out, sp, tu, s);
+    return launch_chain_lnt<IN, OUT, false>(t, nc, init, out, sp, tu, s);
 }
 
 }  // namespace
@@ -1014,99 +1015,98 @@ int phased_slot(int dev, hipStream_t s, bool* own) {
 int phased_owned_slots(int dev) { return dev >= 0 && dev < kMaxDevices ? g_phased[dev].taken_count() : -1; }
 
 hipError_t launch_chain(const ClientTable& t, int nc, fa_dtype in, fa_dtype outdt, const float* init, void* out,
-                        int64_t head, int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
+                        const Split& sp, const Tuning& tu, hipStream_t s) {
+    if (!sp.valid()) return hipErrorInvalidValue;
     return with_types(in, outdt, [&](auto i, auto o) {
-        return launch_chain_t<typename decltype(i)::type, typename decltype(o)::type>(t, nc, init, out, head, nvec, n,
-                                                                                      vector_ok, tu, s);
+        return launch_chain_t<typename decltype(i)::type, typename decltype(o)::type>(t, nc, init, out, sp, tu, s);
     });
 }
 
 namespace {
 template <typename IN, typename OUT>
-hipError_t launch_literal_t(const void* x, void* out, float divisor, int64_t head, int64_t nvec, int64_t n,
-                            bool vector_ok, const Tuning& tu, hipStream_t s) {
-    if (!vector_ok) {
-        hipLaunchKernelGGL((literal_scalar_kernel<IN, OUT>), dim3((unsigned)grid_scalar(n, tu)), dim3(tu.block), 0, s,
-                           x, out, divisor, n);
+hipError_t launch_literal_t(const void* x, void* out, float divisor, const Split& sp, const Tuning& tu,
+                            hipStream_t s) {
+    if (!sp.vec) {
+        hipLaunchKernelGGL((literal_scalar_kernel<IN, OUT>), dim3((unsigned)grid_scalar(sp.n, tu)), dim3(tu.block), 0,
+                           s, x, out, divisor, sp.n);
     } else {  // two streams only: nt loads, write-through stores
-        hipLaunchKernelGGL((literal_kernel<IN, OUT, true, kStSc1>), dim3((unsigned)grid_for(nvec > 0 ? nvec : 1, tu)),
-                           dim3(tu.block), 0, s, x, out, divisor, head, nvec, n);
+        hipLaunchKernelGGL((literal_kernel<IN, OUT, true, kStSc1>),
+                           dim3((unsigned)grid_for(sp.nvec > 0 ? sp.nvec : 1, tu)), dim3(tu.block), 0, s, x, out,
+                           divisor, sp.head, sp.nvec, sp.n);
     }
     return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_literal(const void* x, fa_dtype in, void* out, fa_dtype outdt, float divisor, int64_t head,
-                          int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
+hipError_t launch_literal(const void* x, fa_dtype in, void* out, fa_dtype outdt, float divisor, const Split& sp,
+                          const Tuning& tu, hipStream_t s) {
+    if (!sp.valid()) return hipErrorInvalidValue;
     return with_types(in, outdt, [&](auto i, auto o) {
-        return launch_literal_t<typename decltype(i)::type, typename decltype(o)::type>(x, out, divisor, head, nvec, n,
-                                                                                        vector_ok, tu, s);
+        return launch_literal_t<typename decltype(i)::type, typename decltype(o)::type>(x, out, divisor, sp, tu, s);
     });
 }
 
 namespace {
 template <typename T, int SP>
-hipError_t launch_sync_sp(const ClientTable& t, int nc, const float* init, int64_t head, int64_t nvec, int64_t n,
-                          const Tuning& tu, hipStream_t s) {
-    const int64_t g = grid_for(nvec > 0 ? nvec : 1, tu);
+hipError_t launch_sync_sp(const ClientTable& t, int nc, const float* init, const Split& sp, const Tuning& tu,
+                          hipStream_t s) {
+    const int64_t g = grid_for(sp.nvec > 0 ? sp.nvec : 1, tu);
     if (init)
         hipLaunchKernelGGL((fedavg_sync_kernel<T, 8, SP, true>), dim3((unsigned)g), dim3(tu.block), 0, s, t, nc, init,
-                           head, nvec, n);
+                           sp.head, sp.nvec, sp.n);
     else
         hipLaunchKernelGGL((fedavg_sync_kernel<T, 8, SP, false>), dim3((unsigned)g), dim3(tu.block), 0, s, t, nc,
-                           init, head, nvec, n);
+                           init, sp.head, sp.nvec, sp.n);
     return hipGetLastError();
 }
 
 // The phased kernel in state-sync form (no init: sync_on chains more than kMaxClients slots into
 // scratch and broadcasts instead).
 template <typename T, int REGS, int TH>
-hipError_t launch_sync_phased_r(const ClientTable& t, int nc, int64_t head, int64_t nvec, int64_t n, hipStream_t s) {
+hipError_t launch_sync_phased_r(const ClientTable& t, int nc, const Split& sp, hipStream_t s) {
     PhasedDevice* d = phased_device();
     if (!d) return hipErrorNotSupported;
     constexpr int RL = Phased<T, REGS, TH, T>::RL, RR = Phased<T, REGS, TH, T>::RR;
     const int64_t per_phase = (int64_t)d->cus * TH * (RL + RR);
-    if (nvec < per_phase) return hipErrorNotSupported;
+    if (sp.nvec < per_phase) return hipErrorNotSupported;
     static std::atomic<int> occ{-1};
     auto kern = fedavg_phased_kernel<T, T, false, REGS, true, TH>;
     if (!phased_fits(occ, kern, TH)) return hipErrorNotSupported;
-    return phased_enqueue(d, kern, TH, RL, RR, s, t, nc,
-                          (const float*)nullptr, (void*)nullptr, head, nvec, n);
+    return phased_enqueue(d, kern, TH, RL, RR, s, t, nc, (const float*)nullptr, (void*)nullptr, sp);
 }
 
 template <typename T>
-hipError_t launch_sync_t(const ClientTable& t, int nc, const float* init, int64_t head, int64_t nvec, int64_t n,
-                         bool vector_ok, const Tuning& tu, hipStream_t s) {
-    if (vector_ok && !init && tu.walk >= 3 && tu.walk <= 5) {
-        const hipError_t e = tu.walk == 3   ? launch_sync_phased_r<T, 128, 256>(t, nc, head, nvec, n, s)
-                             : tu.walk == 4 ? launch_sync_phased_r<T, 192, 256>(t, nc, head, nvec, n, s)
-                                            : launch_sync_phased_r<T, 96, 512>(t, nc, head, nvec, n, s);
+hipError_t launch_sync_t(const ClientTable& t, int nc, const float* init, const Split& sp, const Tuning& tu,
+                         hipStream_t s) {
+    if (sp.vec && !init && tu.walk >= 3 && tu.walk <= 5) {
+        const hipError_t e = tu.walk == 3   ? launch_sync_phased_r<T, 128, 256>(t, nc, sp, s)
+                             : tu.walk == 4 ? launch_sync_phased_r<T, 192, 256>(t, nc, sp, s)
+                                            : launch_sync_phased_r<T, 96, 512>(t, nc, sp, s);
         if (e != hipErrorNotSupported) return e;
     }
-    if (!vector_ok) {
-        const int64_t g = grid_scalar(n, tu);
+    if (!sp.vec) {
+        const int64_t g = grid_scalar(sp.n, tu);
         if (init)
             hipLaunchKernelGGL((fedavg_sync_scalar_kernel<T, true>), dim3((unsigned)g), dim3(tu.block), 0, s, t, nc,
-                               init, n);
+                               init, sp.n);
         else
             hipLaunchKernelGGL((fedavg_sync_scalar_kernel<T, false>), dim3((unsigned)g), dim3(tu.block), 0, s, t, nc,
-                               init, n);
+                               init, sp.n);
         return hipGetLastError();
     }
     switch (tu.store_policy) {
-        case kStNt: return launch_sync_sp<T, kStNt>(t, nc, init, head, nvec, n, tu, s);
-        case kStSc1: return launch_sync_sp<T, kStSc1>(t, nc, init, head, nvec, n, tu, s);
-        case kStSc01: return launch_sync_sp<T, kStSc01>(t, nc, init, head, nvec, n, tu, s);
-        default: return launch_sync_sp<T, kStPlain>(t, nc, init, head, nvec, n, tu, s);
+        case kStNt: return launch_sync_sp<T, kStNt>(t, nc, init, sp, tu, s);
+        case kStSc1: return launch_sync_sp<T, kStSc1>(t, nc, init, sp, tu, s);
+        case kStSc01: return launch_sync_sp<T, kStSc01>(t, nc, init, sp, tu, s);
+        default: return launch_sync_sp<T, kStPlain>(t, nc, init, sp, tu, s);
     }
 }
 }  // namespace
 
-hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, int64_t head, int64_t nvec,
-                       int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
-    return with_type(dt, [&](auto e) {
-        return launch_sync_t<typename decltype(e)::type>(t, nc, init, head, nvec, n, vector_ok, tu, s);
-    });
+hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
+                       const Tuning& tu, hipStream_t s) {
+    if (!sp.valid()) return hipErrorInvalidValue;
+    return with_type(dt, [&](auto e) { return launch_sync_t<typename decltype(e)::type>(t, nc, init, sp, tu, s); });
 }
 
 hipError_t launch_broadcast(const ClientTable& t, int nc, fa_dtype dt, const float* acc, int64_t n,
@@ -1197,7 +1197,8 @@ hipError_t launch_read_probe(const ClientTable& t, int nc, int64_t nvec, float* 
     if (d) {
         const ChainPlan pl = plan_chain(FA_F32, FA_F32, nvec, nc, true, tu, d->cus);
         if (pl.kind == kPlanPhased) {
-            const hipError_t e = launch_phased_plan<float, float>(d, pl, t, nc, nullptr, nullptr, 0, nvec, nvec * 4, s);
+            const hipError_t e = launch_phased_plan<float, float>(d, pl, t, nc, nullptr, nullptr,
+                                                                  split_at(nullptr, 4, (size_t)nvec * 4), s);
             if (e != hipErrorNotSupported) return e;
         }
     }

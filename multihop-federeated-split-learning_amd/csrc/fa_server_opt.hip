@@ -144,31 +144,30 @@ int64_t blocks_for(int64_t work, const Tuning& tu, int64_t cap) {
 }
 
 template <int RULE, typename OUT>
-hipError_t launch_opt_t(const OptHyper& h, const float* avg, float* x, float* m, float* v, void* out, int64_t head,
-                        int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
-    if (vector_ok && nvec > 0) {
+hipError_t launch_opt_t(const OptHyper& h, const float* avg, float* x, float* m, float* v, void* out, const Split& sp,
+                        const Tuning& tu, hipStream_t s) {
+    if (sp.vec && sp.nvec > 0) {
         hipLaunchKernelGGL((server_opt_vec_kernel<RULE, OUT, kStSc1>),
-                           dim3((unsigned)blocks_for(nvec, tu, (int64_t)1 << 30)), dim3(tu.block), 0, s, h, avg, x, m, v,
-                           out, head, nvec);
-        const int64_t tail0 = head + nvec * 4, edges = head + (n - tail0);
-        if (edges > 0)
-            hipLaunchKernelGGL((server_opt_elem_kernel<RULE, OUT>), dim3(1), dim3(64), 0, s, h, avg, x, m, v, out, head,
-                               tail0, n);
+                           dim3((unsigned)blocks_for(sp.nvec, tu, (int64_t)1 << 30)), dim3(tu.block), 0, s, h, avg, x,
+                           m, v, out, sp.head, sp.nvec);
+        if (sp.edges() > 0)
+            hipLaunchKernelGGL((server_opt_elem_kernel<RULE, OUT>), dim3(1), dim3(64), 0, s, h, avg, x, m, v, out,
+                               sp.head, sp.tail0(), sp.n);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((server_opt_elem_kernel<RULE, OUT>), dim3((unsigned)blocks_for(n, tu, kElemMaxBlocks)),
-                       dim3(tu.block), 0, s, h, avg, x, m, v, out, n, n, n);
+    hipLaunchKernelGGL((server_opt_elem_kernel<RULE, OUT>), dim3((unsigned)blocks_for(sp.n, tu, kElemMaxBlocks)),
+                       dim3(tu.block), 0, s, h, avg, x, m, v, out, sp.n, sp.n, sp.n);
     return hipGetLastError();
 }
 
 template <int RULE>
 hipError_t launch_opt_r(const OptHyper& h, const float* avg, float* x, float* m, float* v, void* out, fa_dtype odt,
-                        int64_t head, int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
-    if (!out) return launch_opt_t<RULE, NoOut>(h, avg, x, m, v, out, head, nvec, n, vector_ok, tu, s);
+                        const Split& sp, const Tuning& tu, hipStream_t s) {
+    if (!out) return launch_opt_t<RULE, NoOut>(h, avg, x, m, v, out, sp, tu, s);
     switch (odt) {
-        case FA_F32: return launch_opt_t<RULE, float>(h, avg, x, m, v, out, head, nvec, n, vector_ok, tu, s);
-        case FA_BF16: return launch_opt_t<RULE, uint16_t>(h, avg, x, m, v, out, head, nvec, n, vector_ok, tu, s);
-        case FA_F16: return launch_opt_t<RULE, _Float16>(h, avg, x, m, v, out, head, nvec, n, vector_ok, tu, s);
+        case FA_F32: return launch_opt_t<RULE, float>(h, avg, x, m, v, out, sp, tu, s);
+        case FA_BF16: return launch_opt_t<RULE, uint16_t>(h, avg, x, m, v, out, sp, tu, s);
+        case FA_F16: return launch_opt_t<RULE, _Float16>(h, avg, x, m, v, out, sp, tu, s);
     }
     return hipErrorInvalidValue;
 }
@@ -176,13 +175,12 @@ hipError_t launch_opt_r(const OptHyper& h, const float* avg, float* x, float* m,
 }  // namespace
 
 hipError_t launch_server_opt(int rule, const OptHyper& h, const float* avg, float* x, float* m, float* v, void* out,
-                             fa_dtype odt, int64_t head, int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu,
-                             hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    if (!avg || !x || !m || head < 0 || nvec < 0 || head + nvec * 4 > n) return hipErrorInvalidValue;
+                             fa_dtype odt, const Split& sp, const Tuning& tu, hipStream_t s) {
+    if (sp.n <= 0) return hipSuccess;
+    if (!sp.valid() || sp.V != 4 || !avg || !x || !m) return hipErrorInvalidValue;
     if (!v && (rule == FA_OPT_ADAGRAD || rule == FA_OPT_ADAM || rule == FA_OPT_YOGI)) return hipErrorInvalidValue;
 #define FA_OPT_RULE(R) \
-    case R: return launch_opt_r<R>(h, avg, x, m, v, out, odt, head, nvec, n, vector_ok, tu, s)
+    case R: return launch_opt_r<R>(h, avg, x, m, v, out, odt, sp, tu, s)
     switch (rule) {
         FA_OPT_RULE(kOptBoot);
         FA_OPT_RULE(FA_OPT_MOMENTUM);

@@ -195,33 +195,32 @@ int64_t blocks_for(int64_t work, const Tuning& tu, int64_t cap) {
 }
 
 template <typename IN, typename OUT, int P>
-hipError_t launch_trimmed_p(const ClientTable& t, int nc, int trim, void* out, int64_t head, int64_t nvec, int64_t n,
-                            bool vector_ok, const Tuning& tu, hipStream_t s) {
+hipError_t launch_trimmed_p(const ClientTable& t, int nc, int trim, void* out, const Split& sp, const Tuning& tu,
+                            hipStream_t s) {
     constexpr int V = In<IN>::kVec;
     const float div = (float)(nc - 2 * trim);
     if constexpr (P * V <= 128) {
-        if (vector_ok && nvec > 0) {
+        if (sp.vec && sp.nvec > 0) {
             // nt loads, write-through stores: every byte is touched once (as the literal kernel)
             hipLaunchKernelGGL((trimmed_vec_kernel<IN, OUT, P, kStSc1>),
-                               dim3((unsigned)blocks_for(nvec, tu, (int64_t)1 << 30)), dim3(tu.block), 0, s, t, nc,
-                               trim, div, out, head, nvec);
-            const int64_t tail0 = head + nvec * V, edges = head + (n - tail0);
-            if (edges > 0)
+                               dim3((unsigned)blocks_for(sp.nvec, tu, (int64_t)1 << 30)), dim3(tu.block), 0, s, t,
+                               nc, trim, div, out, sp.head, sp.nvec);
+            if (sp.edges() > 0)
                 hipLaunchKernelGGL((trimmed_elem_kernel<IN, OUT, P>), dim3(1), dim3(64), 0, s, t, nc, trim, div, out,
-                                   head, tail0, n);
+                                   sp.head, sp.tail0(), sp.n);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((trimmed_elem_kernel<IN, OUT, P>), dim3((unsigned)blocks_for(n, tu, kElemMaxBlocks)),
-                       dim3(tu.block), 0, s, t, nc, trim, div, out, n, n, n);
+    hipLaunchKernelGGL((trimmed_elem_kernel<IN, OUT, P>), dim3((unsigned)blocks_for(sp.n, tu, kElemMaxBlocks)),
+                       dim3(tu.block), 0, s, t, nc, trim, div, out, sp.n, sp.n, sp.n);
     return hipGetLastError();
 }
 
 template <typename IN, typename OUT>
-hipError_t launch_trimmed_t(const ClientTable& t, int nc, int trim, void* out, int64_t head, int64_t nvec, int64_t n,
-                            bool vector_ok, const Tuning& tu, hipStream_t s) {
+hipError_t launch_trimmed_t(const ClientTable& t, int nc, int trim, void* out, const Split& sp, const Tuning& tu,
+                            hipStream_t s) {
 #define FA_TRIM_P(P) \
-    if (nc <= P) return launch_trimmed_p<IN, OUT, P>(t, nc, trim, out, head, nvec, n, vector_ok, tu, s)
+    if (nc <= P) return launch_trimmed_p<IN, OUT, P>(t, nc, trim, out, sp, tu, s)
     FA_TRIM_P(2);
     FA_TRIM_P(4);
     FA_TRIM_P(8);
@@ -229,28 +228,29 @@ hipError_t launch_trimmed_t(const ClientTable& t, int nc, int trim, void* out, i
     FA_TRIM_P(32);
     FA_TRIM_P(64);
 #undef FA_TRIM_P
-    int64_t g = std::min<int64_t>((n + kWideBlock - 1) / kWideBlock, kElemMaxBlocks);
+    int64_t g = std::min<int64_t>((sp.n + kWideBlock - 1) / kWideBlock, kElemMaxBlocks);
     if (tu.max_blocks > 0) g = std::min<int64_t>(g, tu.max_blocks);
     hipLaunchKernelGGL((trimmed_wide_kernel<IN, OUT>), dim3((unsigned)std::max<int64_t>(1, g)), dim3(kWideBlock), 0, s,
-                       t, nc, trim, (float)(nc - 2 * trim), out, n);
+                       t, nc, trim, (float)(nc - 2 * trim), out, sp.n);
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_trimmed(const ClientTable& t, int nc, fa_dtype in, fa_dtype out, int trim, void* dst, int64_t head,
-                          int64_t nvec, int64_t n, bool vector_ok, const Tuning& tu, hipStream_t s) {
+hipError_t launch_trimmed(const ClientTable& t, int nc, fa_dtype in, fa_dtype out, int trim, void* dst,
+                          const Split& sp, const Tuning& tu, hipStream_t s) {
+    if (!sp.valid() || sp.V != (in == FA_F32 ? 4 : 8)) return hipErrorInvalidValue;
     if (nc < 1 || nc > FA_TRIMMED_MAX_CLIENTS || trim < 0 || 2 * trim >= nc || !dtype_pair_ok(in, out))
         return hipErrorInvalidValue;
     auto with_out = [&](auto i) {
         using IN = decltype(i);
-        if (out == FA_F32) return launch_trimmed_t<IN, float>(t, nc, trim, dst, head, nvec, n, vector_ok, tu, s);
+        if (out == FA_F32) return launch_trimmed_t<IN, float>(t, nc, trim, dst, sp, tu, s);
         if constexpr (sizeof(IN) == 2) {  // a 16-bit input keeps its own type or widens to fp32
-            return launch_trimmed_t<IN, IN>(t, nc, trim, dst, head, nvec, n, vector_ok, tu, s);
+            return launch_trimmed_t<IN, IN>(t, nc, trim, dst, sp, tu, s);
         } else {
             if (out == FA_BF16)
-                return launch_trimmed_t<IN, uint16_t>(t, nc, trim, dst, head, nvec, n, vector_ok, tu, s);
-            return launch_trimmed_t<IN, _Float16>(t, nc, trim, dst, head, nvec, n, vector_ok, tu, s);
+                return launch_trimmed_t<IN, uint16_t>(t, nc, trim, dst, sp, tu, s);
+            return launch_trimmed_t<IN, _Float16>(t, nc, trim, dst, sp, tu, s);
         }
     };
     switch (in) {

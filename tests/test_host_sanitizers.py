@@ -101,3 +101,42 @@ def test_receipt_ledger_under_asan_ubsan():
         assert r.returncode == 0, r.stderr[-2000:]
         res = json.loads(r.stdout.strip().splitlines()[-1])
         assert res["failed"] == 0 and res["checks"] >= 50
+
+
+def split_selftest_checks():
+    """The number of checks tests/tools/split_selftest.cpp makes, from its ranges."""
+    total = 0
+    for si in (2, 4):
+        V = 16 // si
+        for phase in range(V):
+            lead = (V - phase) % V  # elements from the lead operand to its 16-byte boundary
+            for n in range(3 * V + 2):
+                total += 3 + 3  # head, nvec, valid(); three invalid splits
+                total += 3 + (2 if V == 4 else 0)  # tail0 / edges as the trimmed, clip and optimizer launches had them
+                total += 1  # a refused operand stays refused
+                for es in (2, 4):
+                    for _off in range(0, 32, es):
+                        total += 1  # reduce_on's output test
+                        if es == si:
+                            total += 1 + (1 if n >= lead else 0)  # the input test; one rule where the head is whole
+                        if es == 4:
+                            total += 1  # init / ref / scratch
+                        if V == 4:
+                            total += 1  # opt_on's output test
+    return total
+
+
+def test_split_rule_matches_the_four_legacy_spellings():
+    """The vector / element split of a launch (csrc/fa_split.h) against the four hand-written copies of its rule
+    that it replaced, kept verbatim in tests/tools/split_selftest.cpp: head, nvec, valid(), tail0(), edges() and
+    every require on every lead phase, n in 0 .. 3V + 1 and operand offset in 0 .. 31, plain and under ASan+UBSan.
+    The count is computed here from the same ranges, so a loop that shrinks fails."""
+    subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "tools")], capture_output=True, timeout=600, check=True)
+    want = split_selftest_checks()
+    assert want > 10_000
+    for exe in ("split_selftest", "split_selftest_asan"):
+        r = subprocess.run([os.path.join(BIN, exe)], capture_output=True, text=True, timeout=60,
+                           env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1"))
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads(r.stdout.strip().splitlines()[-1])
+        assert res["failed"] == 0 and res["checks"] == want, (res, want)
