@@ -107,6 +107,41 @@
  *              stream round trip more than a plain round) and then enqueues the chain.  Added without a new
  *              FA_ABI_VERSION: fa_clip_sumsq_device with n == 0 touches no device and answers FA_OK -- that is
  *              how a caller probes for it.
+ *   Krum stage (fa_set_krum): distance-based selection of the owners of an FA_FEDAVG part (Krum / Multi-Krum:
+ *              Blanchard et al., "Machine Learning with Adversaries: Byzantine Tolerant Gradient Descent", NeurIPS
+ *              2017).  The owners whose whole bucket lies far from everyone else's are left out, the rest are
+ *              averaged with their own weights.  No part-level state and no reference model.  Parameters: f, the
+ *              number of owners assumed Byzantine, and m, how many owners to keep, with 0 <= f, 2 f + 2 < D (so
+ *              D >= 3), 1 <= m <= D - f and D <= FA_KRUM_MAX_CLIENTS; m = 1 is Krum, m = D - f the usual
+ *              Multi-Krum.  Per round, with weights w_k:
+ *              1. Distances.  For every unordered pair a < b: x is widened to fp32 exactly,
+ *                 d = fl32(x_{a,i} - x_{b,i}), q = (double)d * (double)d (exact in fp64), Q_ab = sum_i q.  As in
+ *                 the clip stage the summation order is NOT specified: every partial sum is an fp64 add of
+ *                 non-negative terms, so whatever the order |Q_ab - exact| <= n * 2^-53 * exact.  No floating-point
+ *                 atomics: for one layout (GPU count, tuning, n, D) the result is the same bits on every run.  Each
+ *                 pair is computed once and mirrored: the reported D x D matrix is bit-symmetric.  Its diagonal is
+ *                 +0 by definition -- it is not computed, also for a bucket that holds a NaN.  NaN and inf
+ *                 propagate into Q.  On range shards and range pieces the per-shard / per-piece matrices are added
+ *                 on the host in fp64, in GPU order and then piece order.
+ *              2. Scores (fa_krum_select, pure host arithmetic in fp64).  For client k take the D - 1 values Q_kj,
+ *                 j != k, replace NaN by +inf and sort them ascending; S_k = the first D - f - 2 of them added in
+ *                 ascending order, starting from +0.
+ *              3. Selection.  Order the clients by (S_k, k) ascending: ties go to the lower index.  The selected
+ *                 set is the first m of them, except that a client with S_k = +inf is never selected: fewer than m
+ *                 may be selected, possibly none.
+ *              4. Weights (fa_krum_weights, pure host arithmetic).  In fp64, in client order, W = the sum of
+ *                 (double)w_k over all D clients and W_s = the same sum over the selected ones.  If all D are
+ *                 selected, or W_s is not > 0, or W / W_s is not finite: w'_k = w_k.  Otherwise
+ *                 w'_k = (float)((double)w_k * (W / W_s)).  The round keeps its total mass: for m = 1 the result is
+ *                 the chosen owner's bucket times about W (each element fl32(w'_k x)), not a bit copy of it.
+ *              5. Aggregate.  The FA_FEDAVG chain from +0 over the selected clients in ascending client order with
+ *                 the weights w'.  With nobody deselected it is the plain FA_FEDAVG aggregate bit for bit; with
+ *                 nobody selected it is +0.  It is the part's fp32 aggregate a: it feeds the server-optimizer
+ *                 stage if the part has one, otherwise it is rounded once to the out dtype as for FA_FEDAVG.
+ *              A reducing call of such a part enqueues the distance pass on every GPU, waits for the matrices (one
+ *              stream round trip more than a plain round), selects on the host and then enqueues the chain.  Added
+ *              without a new FA_ABI_VERSION: fa_pairdist_device with n == 0 touches no device, writes D * D zeros
+ *              and answers FA_OK -- that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -140,6 +175,8 @@ typedef enum { FA_FEDAVG = 0, FA_LITERAL = 1, FA_TRIMMED = 2 /* trimmed mean / m
 #define FA_TRIM_MEDIAN (-1)
 /* Most clients of an FA_TRIMMED bucket (more: FA_ERR_ARG; a sort has no multi-pass form). */
 #define FA_TRIMMED_MAX_CLIENTS 128
+/* Most clients of a part with the Krum stage, and of fa_pairdist_device (more: FA_ERR_ARG). */
+#define FA_KRUM_MAX_CLIENTS 128
 
 typedef enum {
     FA_OK = 0,
@@ -422,6 +459,40 @@ float fa_clip_scale(double sumsq, float max_norm, int* excluded);
  * it and returns the D sums. */
 int fa_clip_sumsq_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in,
                          const float* d_ref, double* h_sumsq, void* hip_stream);
+
+/* Krum stage: distance-based selection of an FA_FEDAVG part's owners (the header comment, "Krum stage").  Gives a
+ * part the stage with parameters f and m (part_id >= 0; calling again changes them), or sets the context default
+ * that FA_FEDAVG parts defined later take (part_id < 0; checked against D when such a part is defined, where a
+ * misfit makes fa_bucket_define fail).  m == -1 means D - f; m == 0 removes the stage.  FA_ERR_ARG, naming the
+ * cause: f < 0 or m < -1, f or m that do not fit the part's D (0 <= f, 2 f + 2 < D, 1 <= m <= D - f), D >
+ * FA_KRUM_MAX_CLIENTS, an FA_LITERAL or FA_TRIMMED part, an FA_SHARD_CLIENT_RS context, a part (or context
+ * default) that has the clip stage -- and fa_set_clip on a Krum part: the two do not compose.  A server optimizer
+ * composes, in either call order.  Like the other stage parts a Krum part is never kept host-side
+ * (fa_bucket_host_read says 0), FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager, it gets its own launches in
+ * fa_reduce_parts, and a reducing call needs every client submitted (FA_ERR_STATE otherwise); fa_reduce_part marks
+ * the round reduced.  Such a call waits on the host for the distance pass before it enqueues the chain: one stream
+ * round trip.  Range shards and range pieces work.  The stage keeps no state across rounds. */
+int fa_set_krum(fa_ctx* ctx, int part_id, int f, int m);
+/* What the part's last reducing call did: dist = the D x D matrix Q (row-major), scores[k] = S_k, selected[k] =
+ * 0 / 1, *n_selected = how many are selected.  Any pointer may be NULL.  FA_ERR_STATE on a part without the stage
+ * or never reduced with it. */
+int fa_krum_get_round(fa_ctx* ctx, int part_id, double* dist, double* scores, int* selected, int* n_selected);
+/* Rules 2-3 of the stage, pure host arithmetic, usable without a device: the scores and the selection flags (D
+ * entries each, either may be NULL) of the D x D row-major matrix dist under f and m (-1: D - f).  FA_ERR_ARG for
+ * a null dist and for D, f, m as in fa_set_krum.  A caller that wants Krum over a whole model sums the matrices of
+ * its parts, selects once and runs fa_reduce_device with the weights of fa_krum_weights. */
+int fa_krum_select(const double* dist, int D, int f, int m, double* scores, int* selected, int* n_selected);
+/* Rule 4, pure host arithmetic: w_out[k] = w'_k for every k (the deselected ones included: they do not enter the
+ * chain). */
+int fa_krum_weights(const float* w, const int* selected, int D, float* w_out);
+/* Rule 1 on raw device pointers: h_dist (D * D doubles, row-major) = the matrix Q of the D client buckets (n
+ * elements of `in`) on device `gpu`, 1 <= D <= FA_KRUM_MAX_CLIENTS.  ctx may be NULL (then `gpu` is the HIP
+ * device).  Every argument is checked before any device call: D, the dtype, h_dist, and for n > 0 null pointers
+ * and element alignment (FA_ERR_ALIGN); with n == 0 and valid arguments it touches no device, writes D * D zeros
+ * and answers FA_OK.  Otherwise it enqueues on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null
+ * stream), waits for it and returns the matrix. */
+int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, double* h_dist,
+                       void* hip_stream);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

@@ -22,6 +22,7 @@ F32, BF16, F16 = 0, 1, 2  # F16: IEEE binary16 (torch.float16 / np.float16)
 FEDAVG, LITERAL, TRIMMED = 0, 1, 2
 TRIM_MEDIAN = -1  # FA_TRIM_MEDIAN: the largest valid trim, (D-1)/2
 TRIMMED_MAX_CLIENTS = 128
+KRUM_MAX_CLIENTS = 128  # FA_KRUM_MAX_CLIENTS: the Krum stage and pairdist_device
 # fa_opt_rule: the server-optimizer stage (FedAvgM, FedAdagrad, FedAdam, FedYogi; fa.h "Server optimizer")
 OPT_NONE, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 0, 1, 2, 3, 4
 SHARD_RANGE, SHARD_CLIENT_RS, ACCUMULATE_ON_ARRIVAL, TEST_SHARED_DEVICE = 0x1, 0x2, 0x4, 0x100
@@ -96,6 +97,11 @@ def lib():
         "fa_clip_get_round": (I, [P, I, P, P, P, ctypes.POINTER(I)]),
         "fa_clip_scale": (F, [ctypes.c_double, F, ctypes.POINTER(I)]),
         "fa_clip_sumsq_device": (I, [P, I, P, I, S, I, P, P, P]),
+        "fa_set_krum": (I, [P, I, I, I]),
+        "fa_krum_get_round": (I, [P, I, P, P, P, ctypes.POINTER(I)]),
+        "fa_krum_select": (I, [P, I, I, I, P, P, ctypes.POINTER(I)]),
+        "fa_krum_weights": (I, [P, P, I, P]),
+        "fa_pairdist_device": (I, [P, I, P, I, S, I, P, P]),
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
         "fa_submit_gather": (I, [P, I, I, I, P, P, F]),
@@ -275,6 +281,44 @@ def clip_scale(sumsq, max_norm):
     ex = ctypes.c_int(0)
     s = lib().fa_clip_scale(float(sumsq), float(max_norm), ctypes.byref(ex))
     return np.float32(s), bool(ex.value)
+
+
+def pairdist_device(clients, n, in_dtype, stream=None, gpu=0, ctx=None):
+    """fa_pairdist_device: the pairwise squared L2 distances Q_ab (np.float64, shape (D, D), bit-symmetric, +0
+    diagonal) of D device-resident client buckets (fa.h "Krum stage", rule 1).  Enqueued on `stream` and waited
+    for.  With n == 0 no device is touched and the matrix is zeros: the feature probe."""
+    D = len(clients)
+    arr = (ctypes.c_void_p * max(1, D))(*[_addr(c) for c in clients])
+    q = np.empty((D, D), np.float64)
+    check(lib().fa_pairdist_device(ctx.handle if ctx is not None else None, gpu, arr, D, n, in_dtype, q.ctypes.data,
+                                   _stream(stream)))
+    return q
+
+
+def krum_select(dist, f, m=None):
+    """fa_krum_select (host arithmetic, rules 2-3): (scores float64[D], selected bool[D]) of the (D, D) matrix
+    `dist` with f owners assumed Byzantine and m kept (None: D - f)."""
+    dist = np.ascontiguousarray(dist, np.float64)
+    D = dist.shape[0] if dist.ndim == 2 else 0
+    if dist.ndim != 2 or dist.shape[1] != D:
+        raise ValueError("need a square matrix")
+    scores, sel = np.empty(D, np.float64), np.empty(D, np.intc)
+    ns = ctypes.c_int()
+    check(lib().fa_krum_select(dist.ctypes.data, D, int(f), -1 if m is None else int(m), scores.ctypes.data,
+                               sel.ctypes.data, ctypes.byref(ns)))
+    return scores, sel.astype(bool)
+
+
+def krum_weights(weights, selected):
+    """fa_krum_weights (host arithmetic, rule 4): the weights w' (np.float32, one per client) of a round whose
+    selection is `selected`."""
+    w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+    sel = np.ascontiguousarray(np.asarray(selected).reshape(-1).astype(np.intc))
+    if sel.size != w.size:
+        raise ValueError("need one flag per weight")
+    out = np.empty(w.size, np.float32)
+    check(lib().fa_krum_weights(w.ctypes.data, sel.ctypes.data, w.size, out.ctypes.data))
+    return out
 
 
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
@@ -553,6 +597,21 @@ class Aggregator:
             if g.size != self.parts[part_id][0]:
                 raise ValueError("bucket %d holds %d elements, got %d" % (part_id, self.parts[part_id][0], g.size))
         check(lib().fa_clip_set_reference(self.handle, part_id, None if g is None else g.ctypes.data))
+
+    def set_krum(self, f, m=None, part_id=-1):
+        """fa_set_krum: Krum / Multi-Krum selection on a FEDAVG part with f owners assumed Byzantine and m kept
+        (None: D - f; 1: Krum; part_id < 0: the default of FEDAVG parts defined later); m=0 removes the stage."""
+        check(lib().fa_set_krum(self.handle, part_id, int(f), -1 if m is None else int(m)))
+
+    def krum_round(self, part_id):
+        """fa_krum_get_round: (dist float64[D, D], scores float64[D], selected bool[D]) of the part's last
+        reducing call."""
+        D = self.parts[part_id][3]
+        q, s, sel = np.empty((D, D), np.float64), np.empty(D, np.float64), np.empty(D, np.intc)
+        ns = ctypes.c_int()
+        check(lib().fa_krum_get_round(self.handle, part_id, q.ctypes.data, s.ctypes.data, sel.ctypes.data,
+                                      ctypes.byref(ns)))
+        return q, s, sel.astype(bool)
 
     def submit(self, part_id, slot, host, weight=1.0, pinned=False):
         host = np.ascontiguousarray(host)

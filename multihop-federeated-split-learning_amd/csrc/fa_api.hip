@@ -254,6 +254,11 @@ struct GpuRes {
     double* clip_dev = nullptr;
     double* clip_host = nullptr;
     size_t clip_sums = 0;          // sums either array has room for
+    // Krum stage: the distance pass's device scratch (the D x D matrices, one per piece, then the per-workgroup
+    // partials) and the pinned array the matrices are read back into, grown on use (ensure_krum_scratch)
+    double* krum_dev = nullptr;
+    double* krum_host = nullptr;
+    size_t krum_dist = 0, krum_part = 0;  // doubles of matrices (either array) and of partials there is room for
     // fa_output_crc32: the piece table (pinned staging + device copy) and the per-piece results, grown on use
     char* crc_host = nullptr;
     char* crc_dev = nullptr;
@@ -341,11 +346,18 @@ struct Part {
     std::vector<float> clip_s;
     std::vector<int> clip_in;
     int clip_n = 0;
+    // Krum stage (fa.h "Krum stage"; krum_m == 0: none): f, the resolved m, and what the last reducing call
+    // found -- the D x D matrix, the scores, the selection flags.  Host state only.
+    int krum_f = 0, krum_m = 0;
+    bool krum_reported = false;
+    std::vector<double> krum_q, krum_s;
+    std::vector<int> krum_sel;
+    int krum_n = 0;
 };
 
-// A part whose reducing calls are rounds of their own (a server-optimizer or clip stage): never batched,
+// A part whose reducing calls are rounds of their own (a server-optimizer, clip or Krum stage): never batched,
 // eager or host-read, every client submitted before each.
-inline bool staged(const Part& p) { return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f; }
+inline bool staged(const Part& p) { return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0; }
 
 }  // namespace
 
@@ -356,6 +368,7 @@ struct fa_ctx {
     int trim = FA_TRIM_MEDIAN;  // default of FA_TRIMMED parts defined later
     fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};  // default stage of FedAvg / trimmed parts defined later
     float clip = 0.0f;          // default clip bound of FedAvg parts defined later (0: none)
+    int krum_f = 0, krum_m = 0; // default Krum stage of FedAvg parts defined later (m == 0: none, -1: D - f)
     CtxTuning tuning;
     std::vector<GpuRes> gpu;
     std::map<int, Part> parts;
@@ -591,6 +604,118 @@ int clip_sumsq_on(const fa::Tuning& tu, const void* const* clients, int D, size_
         const fa::ClientTable t = client_table(clients, nullptr, k0, nc);
         FA_HIP(fa::launch_clip_sumsq(t, nc, in, ref, sp, d_part, d_sums + k0, tu, s));
     }
+    return FA_OK;
+}
+
+// ------------------------------------------------------------------ Krum stage
+
+// The refusals of f and m for D clients (fa.h "Krum stage"), naming the cause; *m_out = m with -1 resolved.
+int check_krum(int D, int f, int m, int* m_out) {
+    if (D > FA_KRUM_MAX_CLIENTS) return fail(FA_ERR_ARG, "krum: D = %d clients (at most %d)", D, FA_KRUM_MAX_CLIENTS);
+    if (f < 0 || 2 * f + 2 >= D)
+        return fail(FA_ERR_ARG, "krum: f = %d does not fit D = %d clients (0 <= f and 2 f + 2 < D)", f, D);
+    const int mm = m == -1 ? D - f : m;
+    if (mm < 1 || mm > D - f)
+        return fail(FA_ERR_ARG, "krum: m = %d does not fit D = %d, f = %d (1 <= m <= D - f, or -1 for D - f)", m, D, f);
+    if (m_out) *m_out = mm;
+    return FA_OK;
+}
+
+// Rules 2-3 of fa.h "Krum stage" (D, f, m checked): volatile keeps each step one rounded fp64 add.
+void krum_select(const double* dist, int D, int f, int m, double* scores, int* selected, int* n_selected) {
+    const double inf = HUGE_VAL;
+    std::vector<double> row((size_t)D - 1), sc((size_t)D);
+    for (int k = 0; k < D; ++k) {
+        size_t c = 0;
+        for (int j = 0; j < D; ++j) {
+            if (j == k) continue;
+            const double q = dist[(size_t)k * D + j];
+            row[c++] = q != q ? inf : q;
+        }
+        std::sort(row.begin(), row.end());
+        volatile double acc = 0.0;
+        for (int i = 0; i < D - f - 2; ++i) acc = acc + row[(size_t)i];
+        sc[(size_t)k] = acc;
+    }
+    std::vector<int> order((size_t)D);
+    for (int k = 0; k < D; ++k) order[(size_t)k] = k;
+    // by (S_k, k) ascending; a NaN score (only from a matrix holding -inf) sorts as +inf
+    auto key = [&](int k) { return sc[(size_t)k] != sc[(size_t)k] ? inf : sc[(size_t)k]; };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key(a) < key(b); });
+    int ns = 0;
+    for (int k = 0; k < D; ++k) {
+        if (scores) scores[k] = sc[(size_t)k];
+        if (selected) selected[k] = 0;
+    }
+    for (int i = 0; i < m; ++i) {
+        const int k = order[(size_t)i];
+        if (!(sc[(size_t)k] < inf)) break;  // +inf is never selected, nor anything after it
+        if (selected) selected[k] = 1;
+        ++ns;
+    }
+    if (n_selected) *n_selected = ns;
+}
+
+// Rule 4: the weights of a round whose selection is `selected` (w_out[k] is set for every k; only the selected
+// ones enter the chain).
+void krum_weights(const float* w, const int* selected, int D, float* w_out) {
+    volatile double W = 0.0, Ws = 0.0;
+    int ns = 0;
+    for (int k = 0; k < D; ++k) {
+        W = W + (double)w[k];
+        if (selected[k]) {
+            Ws = Ws + (double)w[k];
+            ++ns;
+        }
+    }
+    volatile double ratio = 0.0;
+    bool plain = ns == D || !(Ws > 0.0);
+    if (!plain) {
+        ratio = W / Ws;
+        const double r = ratio;
+        plain = r != r || r == HUGE_VAL || r == -HUGE_VAL;
+    }
+    for (int k = 0; k < D; ++k) {
+        if (plain) {
+            w_out[k] = w[k];
+        } else {
+            volatile double prod = (double)w[k] * ratio;
+            w_out[k] = (float)prod;
+        }
+    }
+}
+
+// Room on the current device for the distance pass of `mats` matrices of D clients.
+int ensure_krum_scratch(GpuRes& r, int D, size_t mats) {
+    const size_t dist = mats * (size_t)D * (size_t)D;
+    const size_t part = (size_t)fa::krum_pairs(D) * (size_t)fa::kKrumMaxPartials;
+    if (r.krum_dist >= dist && r.krum_part >= part && r.krum_dev) return FA_OK;
+    if (r.krum_dev) (void)hipFree(r.krum_dev);
+    if (r.krum_host) (void)hipHostFree(r.krum_host);
+    r.krum_dev = r.krum_host = nullptr;
+    const size_t dcap = std::max<size_t>(std::max(dist, r.krum_dist), 256), pcap = std::max<size_t>(std::max(part, r.krum_part), 1);
+    r.krum_dist = r.krum_part = 0;
+    const size_t dev_bytes = (dcap + pcap) * sizeof(double);
+    if (hipMalloc((void**)&r.krum_dev, dev_bytes) != hipSuccess ||
+        hipHostMalloc((void**)&r.krum_host, dcap * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        if (r.krum_dev) (void)hipFree(r.krum_dev);
+        r.krum_dev = nullptr;
+        return fail(FA_ERR_NOMEM, "krum: distance-pass scratch of %zu B failed", dev_bytes);
+    }
+    r.krum_dist = dcap;
+    r.krum_part = pcap;
+    return FA_OK;
+}
+
+// Enqueues the distance pass on the current device: d_dist (D * D doubles) = the matrix of clients[0..D) (n > 0
+// elements of `in`); d_part: the partials scratch.  The vector form where every client allows it (fa_split.h).
+int pairdist_on(const fa::Tuning& tu, const void* const* clients, int D, size_t n, fa_dtype in, double* d_part,
+                double* d_dist, hipStream_t s) {
+    fa::Split sp = fa::split_at(clients[0], dsize(in), n);
+    for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
+    const fa::ClientTable t = client_table(clients, nullptr, 0, D);
+    FA_HIP(fa::launch_pairdist(t, D, in, sp, d_part, d_dist, tu, s));
     return FA_OK;
 }
 
@@ -1170,6 +1295,75 @@ int clip_take_reference(Part& p, int g, int j, hipStream_t st) {
     return FA_OK;
 }
 
+// What the Krum stage makes of a round (fa.h "Krum stage", rules 1-4): the selected clients in ascending order
+// and their weights w'_k.
+struct KrumPlan {
+    std::vector<int> inc;
+    std::vector<float> w;
+};
+
+// Rules 1-4 for part p (range layout): the distance pass of every piece on every GPU, one wait per GPU for its
+// matrices, then the host arithmetic.  The per-shard and per-piece matrices are added in fp64 in GPU order,
+// then piece order.  Leaves the round's report in the part.
+int krum_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, KrumPlan* plan) {
+    const size_t D = (size_t)p.D, DD = D * D;
+    std::vector<const void*> ptrs;
+    for (int g = 0; g < ctx->G; ++g) {
+        if (p.cnt[(size_t)g] == 0) continue;
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        hipStream_t st = s ? s : r.compute;
+        int rc = wait_copies(ctx, g, st);
+        const size_t mats = (size_t)p.npiece[(size_t)g];
+        if (rc || (rc = ensure_krum_scratch(r, p.D, mats))) return rc;
+        for (int j = 0; j < p.npiece[(size_t)g]; ++j) {
+            rc = pairdist_on(ctx->tuning.tu, piece_ptrs(p, g, j, 0, p.D, ptrs), p.D, piece_cnt(p, g, j), p.in,
+                             r.krum_dev + r.krum_dist, r.krum_dev + (size_t)j * DD, st);
+            if (rc) return rc;
+        }
+        FA_HIP(hipMemcpyAsync(r.krum_host, r.krum_dev, mats * DD * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    p.krum_q.assign(DD, 0.0);
+    for (int g = 0; g < ctx->G; ++g) {
+        if (p.cnt[(size_t)g] == 0) continue;
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        FA_HIP(hipStreamSynchronize(s ? s : r.compute));
+        for (int j = 0; j < p.npiece[(size_t)g]; ++j)
+            for (size_t i = 0; i < DD; ++i) {
+                volatile double q = p.krum_q[i] + r.krum_host[(size_t)j * DD + i];
+                p.krum_q[i] = q;
+            }
+    }
+    p.krum_s.assign(D, 0.0);
+    p.krum_sel.assign(D, 0);
+    krum_select(p.krum_q.data(), p.D, p.krum_f, p.krum_m, p.krum_s.data(), p.krum_sel.data(), &p.krum_n);
+    std::vector<float> wp(D);
+    krum_weights(w, p.krum_sel.data(), p.D, wp.data());
+    for (size_t k = 0; k < D; ++k)
+        if (p.krum_sel[k]) {
+            plan->inc.push_back((int)k);
+            plan->w.push_back(wp[k]);
+        }
+    p.krum_reported = true;
+    return FA_OK;
+}
+
+// Rule 5 for piece j of GPU g (the current device): the chain over the selected clients into dst (dtype odt),
+// +0 with nobody selected.
+int krum_chain(fa_ctx* ctx, Part& p, int g, int j, const KrumPlan& plan, void* dst, fa_dtype odt, hipStream_t st) {
+    const size_t cnt = piece_cnt(p, g, j);
+    if (cnt == 0) return FA_OK;
+    if (plan.inc.empty()) {
+        FA_HIP(hipMemsetAsync(dst, 0, cnt * dsize(odt), st));
+        return FA_OK;
+    }
+    std::vector<const void*> ptrs;
+    for (int k : plan.inc) ptrs.push_back(piece_ptr(p, g, k, j));
+    return reduce_on(ctx, g, ctx->tuning.tu, ptrs.data(), plan.w.data(), (int)ptrs.size(), cnt, p.in, dst, odt, FA_FEDAVG,
+                     0.0f, nullptr, st);
+}
+
 // Enqueue the full reduction of part p on every GPU (the ctx's streams, or `s` for a one-GPU ctx):
 // range -> each GPU's shard; rs -> the clients' fp32 partials, piece by piece, each piece's RCCL
 // reduce-scatter (ring over xGMI) overlapping the reduction of the next.
@@ -1193,6 +1387,11 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
             if (clipping)
                 if (int rc = clip_plan(ctx, p, w, s, &plan)) return rc;
         }
+        // a Krum stage: the distance pass, the host's wait for its matrices and the selection come first
+        const bool krum = p.krum_m != 0;
+        KrumPlan kplan;
+        if (krum)
+            if (int rc = krum_plan(ctx, p, w, s, &kplan)) return rc;
         std::vector<const void*> ptrs;
         for (int g = 0; g < G; ++g) {
             GpuRes& r = ctx->gpu[(size_t)g];
@@ -1216,6 +1415,8 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
                     rc = reduce_on(ctx, g, tu, &last, w, 1, cnt, p.in, dst, p.out, FA_LITERAL, p.divisor, nullptr, st);
                 } else if (clipping)
                     rc = clip_chain(ctx, p, g, j, plan, adst, adt, st);
+                else if (krum)
+                    rc = krum_chain(ctx, p, g, j, kplan, adst, adt, st);
                 else
                     rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                                    mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
@@ -2080,6 +2281,8 @@ void fa_destroy(fa_ctx* ctx) {
         if (r.scratch) (void)hipFree(r.scratch);
         if (r.clip_dev) (void)hipFree(r.clip_dev);
         if (r.clip_host) (void)hipHostFree(r.clip_host);
+        if (r.krum_dev) (void)hipFree(r.krum_dev);
+        if (r.krum_host) (void)hipHostFree(r.krum_host);
         if (r.crc_host) (void)hipHostFree(r.crc_host);
         if (r.crc_dev) (void)hipFree(r.crc_dev);
         for (hipStream_t s : {r.compute, r.copy, r.comm})
@@ -2110,6 +2313,10 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
                                     "FA_SHARD_CLIENT_RS context (use FA_SHARD_RANGE)");
         if (int rc = check_trim(ctx->trim, n_clients)) return rc;
     }
+    const bool krummed = ctx->krum_m != 0 && mode == FA_FEDAVG && !rs;  // takes the context's Krum stage
+    int krum_m = 0;
+    if (krummed)
+        if (int rc = check_krum(n_clients, ctx->krum_f, ctx->krum_m, &krum_m)) return rc;
     auto it = ctx->parts.find(part_id);
     if (it != ctx->parts.end()) {
         free_part(ctx, it->second);
@@ -2130,7 +2337,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     const size_t G = (size_t)ctx->G;
     const bool staged = ctx->opt.rule != FA_OPT_NONE && mode != FA_LITERAL && !rs;  // takes the context's stage
     const bool clipped = ctx->clip > 0.0f && mode == FA_FEDAVG && !rs;  // takes the context's clip bound
-    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged && !clipped;
+    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged && !clipped && !krummed;
     if (rs) {
         const size_t unit = G * kShardUnit;
         p.npad = (n_elems + unit - 1) / unit * unit;
@@ -2224,6 +2431,10 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
             g_err = why;
             return rc;
         }
+    }
+    if (krummed) {
+        p.krum_f = ctx->krum_f;
+        p.krum_m = krum_m;
     }
     ctx->parts.emplace(part_id, std::move(p));
     return FA_OK;
@@ -2333,6 +2544,8 @@ int fa_set_clip(fa_ctx* ctx, int part_id, float max_norm) {
         return fail(FA_ERR_ARG, "clip: not on an FA_SHARD_CLIENT_RS context (its aggregate is not bit-specified; use "
                                 "FA_SHARD_RANGE)");
     if (part_id < 0) {
+        if (max_norm > 0.0f && ctx->krum_m != 0)
+            return fail(FA_ERR_ARG, "clip: the context default has a Krum stage (the two stages do not compose)");
         ctx->clip = max_norm;
         return FA_OK;
     }
@@ -2342,6 +2555,8 @@ int fa_set_clip(fa_ctx* ctx, int part_id, float max_norm) {
     if (max_norm > 0.0f && p->mode != FA_FEDAVG)
         return fail(FA_ERR_ARG, "clip: part %d is an %s part (the stage clips FA_FEDAVG updates)", part_id,
                     p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_TRIMMED");
+    if (max_norm > 0.0f && p->krum_m != 0)
+        return fail(FA_ERR_ARG, "clip: part %d has a Krum stage (the two stages do not compose)", part_id);
     return set_part_clip(ctx, *p, max_norm);
 }
 
@@ -2425,6 +2640,119 @@ int fa_clip_sumsq_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int
     if (!ctx) {
         if (own.clip_dev) (void)hipFree(own.clip_dev);
         if (own.clip_host) (void)hipHostFree(own.clip_host);
+    }
+    if (rc) return rc;
+    FA_HIP(e);
+    return FA_OK;
+}
+
+int fa_set_krum(fa_ctx* ctx, int part_id, int f, int m) {
+    g_err.clear();
+    if (f < 0 || m < -1) return fail(FA_ERR_ARG, "krum: f = %d, m = %d (f >= 0; m >= 1, -1 for D - f, 0 removes the stage)", f, m);
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (m != 0 && (ctx->flags & FA_SHARD_CLIENT_RS))
+        return fail(FA_ERR_ARG, "krum: not on an FA_SHARD_CLIENT_RS context (a pair's distance needs both clients on one "
+                                "GPU; use FA_SHARD_RANGE)");
+    if (part_id < 0) {
+        if (m != 0 && ctx->clip > 0.0f)
+            return fail(FA_ERR_ARG, "krum: the context default has a clip stage (the two stages do not compose)");
+        ctx->krum_f = m != 0 ? f : 0;
+        ctx->krum_m = m;
+        return FA_OK;
+    }
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (m == 0) {  // the stage and its report go
+        p->krum_f = p->krum_m = 0;
+        p->krum_reported = false;
+        p->krum_q.clear();
+        p->krum_s.clear();
+        p->krum_sel.clear();
+        return FA_OK;
+    }
+    if (p->mode != FA_FEDAVG)
+        return fail(FA_ERR_ARG, "krum: part %d is an %s part (the stage selects the owners of an FA_FEDAVG average)", part_id,
+                    p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_TRIMMED");
+    if (p->clip > 0.0f)
+        return fail(FA_ERR_ARG, "krum: part %d has a clip stage (the two stages do not compose)", part_id);
+    int mm = 0;
+    if ((rc = check_krum(p->D, f, m, &mm))) return rc;
+    const bool fresh = p->krum_m == 0;
+    p->krum_f = f;
+    p->krum_m = mm;
+    if (fresh) {
+        // non-eager and never kept host-side from here on: what this round chained or kept so far goes back to
+        // the plain path (as for the other stages)
+        p->krum_reported = false;
+        p->reduced = 0;
+        p->ready = false;
+    }
+    return FA_OK;
+}
+
+int fa_krum_get_round(fa_ctx* ctx, int part_id, double* dist, double* scores, int* selected, int* n_selected) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (p->krum_m == 0) return fail(FA_ERR_STATE, "part %d has no Krum stage", part_id);
+    if (!p->krum_reported) return fail(FA_ERR_STATE, "part %d: no round reduced with the Krum stage yet", part_id);
+    const size_t D = (size_t)p->D;
+    if (dist) std::copy(p->krum_q.begin(), p->krum_q.end(), dist);
+    for (size_t k = 0; k < D; ++k) {
+        if (scores) scores[k] = p->krum_s[k];
+        if (selected) selected[k] = p->krum_sel[k];
+    }
+    if (n_selected) *n_selected = p->krum_n;
+    return FA_OK;
+}
+
+int fa_krum_select(const double* dist, int D, int f, int m, double* scores, int* selected, int* n_selected) {
+    g_err.clear();
+    if (!dist) return fail(FA_ERR_ARG, "krum: dist is null");
+    if (D < 1) return fail(FA_ERR_ARG, "krum: D must be >= 1");
+    int mm = 0;
+    if (int rc = check_krum(D, f, m, &mm)) return rc;
+    krum_select(dist, D, f, mm, scores, selected, n_selected);
+    return FA_OK;
+}
+
+int fa_krum_weights(const float* w, const int* selected, int D, float* w_out) {
+    g_err.clear();
+    if (!w || !selected || !w_out) return fail(FA_ERR_ARG, "krum: w, selected or w_out is null");
+    if (D < 1) return fail(FA_ERR_ARG, "krum: D must be >= 1");
+    krum_weights(w, selected, D, w_out);
+    return FA_OK;
+}
+
+int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, double* h_dist,
+                       void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (D < 1 || D > FA_KRUM_MAX_CLIENTS) return fail(FA_ERR_ARG, "krum: D = %d outside 1..%d", D, FA_KRUM_MAX_CLIENTS);
+    if (!dvalid(in)) return fail(FA_ERR_ARG, "bad dtype");
+    if (!h_dist) return fail(FA_ERR_ARG, "krum: h_dist is null");
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    const size_t DD = (size_t)D * (size_t)D;
+    if (n == 0) {
+        std::fill(h_dist, h_dist + DD, 0.0);
+        return FA_OK;
+    }
+    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    GpuRes own;  // a context-less call brings its scratch and frees it before it returns
+    GpuRes& r = ctx ? ctx->gpu[(size_t)gpu] : own;
+    int rc = ensure_krum_scratch(r, D, 1);
+    if (!rc) rc = pairdist_on(c.tu, d_clients, D, n, in, r.krum_dev + r.krum_dist, r.krum_dev, c.s);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(r.krum_host, r.krum_dev, DD * sizeof(double), hipMemcpyDeviceToHost, c.s);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c.s);
+    if (!rc && e == hipSuccess) std::copy(r.krum_host, r.krum_host + DD, h_dist);
+    if (!ctx) {
+        if (own.krum_dev) (void)hipFree(own.krum_dev);
+        if (own.krum_host) (void)hipHostFree(own.krum_host);
     }
     if (rc) return rc;
     FA_HIP(e);

@@ -118,6 +118,17 @@ hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const fl
                              double* partials, double* sums, const Tuning& tu, hipStream_t s);
 // dst[i] = src[i] widened to fp32 exactly (the part's output into its reference; signed zeros kept).
 hipError_t launch_clip_widen(const void* src, fa_dtype dt, float* dst, int64_t n, hipStream_t s);
+// The Krum stage's distance pass (fa.h "Krum stage", rule 1), fa_krum.hip.  dist (device, D * D doubles, row-major)
+// := Q_ab = sum_i ((double)fl32(x_{a,i} - x_{b,i}))^2 over the n elements of clients t.src[0..D), 1 <= D <=
+// kMaxClients (weights not read), each pair computed once and mirrored, the diagonal +0: one launch over all
+// clients writes one fp64 partial per (pair, workgroup) into `partials` (room for krum_pairs(D) *
+// kKrumMaxPartials doubles; not read for D == 1), a second one adds each pair's partials in a fixed order.  No
+// atomics.  sp: the Split (fa_split.h) led by the first client.
+constexpr int64_t kKrumMaxBlocks = 1024;  // 4 workgroups of 34 KiB LDS per CU on 256 CUs; tiles beyond it are strided
+constexpr int64_t kKrumMaxPartials = kKrumMaxBlocks + 1;  // per pair: the grid's, plus one for head and tail
+inline int64_t krum_pairs(int D) { return (int64_t)D * (D - 1) / 2; }
+hipError_t launch_pairdist(const ClientTable& t, int D, fa_dtype in, const Split& sp, double* partials, double* dist,
+                           const Tuning& tu, hipStream_t s);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
                        const Tuning& tu, hipStream_t s);

@@ -30,6 +30,8 @@
 // --server-state FILE carries them across restarts.
 // --clip-norm C bounds every owner's update (its receipt minus the global model it was last sent) to an L2
 // norm of C before the FedAvg chain (fa.h "Clip stage"); --clip-state FILE carries that model across restarts.
+// --krum-f F [--krum-m M] averages, per bucket, only the M owners (default D - F) whose receipts lie closest to
+// the others' (Krum / Multi-Krum, fa.h "Krum stage"); the stage keeps no state across rounds.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -95,6 +97,10 @@ struct Options {
     float clip_norm = 0.0f;
     bool clip_given = false;
     std::string clip_state;
+    // --krum-f F [--krum-m M]: the Krum stage of every bucket (fa_set_krum on the context, before any bucket is
+    // defined); M defaults to DATA_OWNERS - F
+    int krum_f = 0, krum_m = -1;
+    bool krum_given = false, krum_m_given = false;
 };
 
 const char* server_rule_name(int rule) {
@@ -237,6 +243,7 @@ void usage() {
                  "       [--server-opt momentum|adagrad|adam|yogi --server-lr L [--server-beta1 B] [--server-beta2 B]\n"
                  "        [--server-tau T] [--server-state FILE]]\n"
                  "       [--clip-norm C [--clip-state FILE]]\n"
+                 "       [--krum-f F [--krum-m M]]\n"
                  "--mode trimmed: per element the T lowest and T highest of the owners' values are dropped and the\n"
                  "rest averaged (2T < DATA_OWNERS <= 128; without --trim, and with --mode median, the median), so up\n"
                  "to T owners that send NaN, inf or huge values change no reply; --samples is ignored; not with\n"
@@ -251,6 +258,10 @@ void usage() {
                  "update holds a NaN or an inf is left out of the round; the first round of a bucket without a stored\n"
                  "model clips nothing; --clip-state FILE is read at startup if it exists (the model last sent) and\n"
                  "rewritten after every round; not with --mode literal|trimmed|median or --layout rs.\n"
+                 "--krum-f F: per bucket only the M owners (--krum-m, default DATA_OWNERS - F; 1 is Krum) whose receipts\n"
+                 "lie closest to the others' are averaged, with their own weights scaled up to the round's mass; F is\n"
+                 "the number of owners assumed Byzantine, 0 <= F, 2F + 2 < DATA_OWNERS <= 128, 1 <= M <= DATA_OWNERS - F;\n"
+                 "not with --clip-norm, --mode literal|trimmed|median or --layout rs.\n"
                  "A bucket takes the dtype of its first receipt's parameters (all fp32, all bf16 or all fp16, by\n"
                  "their storage type) and is reduced and replied in it; a later receipt of another size or dtype\n"
                  "ends the process (exit 1).\n";
@@ -332,6 +343,12 @@ bool parse_args(int argc, char** argv, Options* o) {
             o->clip_given = true;
         } else if (a == "--clip-state") {
             o->clip_state = val("--clip-state");
+        } else if (a == "--krum-f") {
+            o->krum_f = std::atoi(val("--krum-f"));
+            o->krum_given = true;
+        } else if (a == "--krum-m") {
+            o->krum_m = std::atoi(val("--krum-m"));
+            o->krum_m_given = true;
         } else if (a == "--trim") {
             o->trim = std::atoi(val("--trim"));
             o->trim_given = true;
@@ -424,6 +441,39 @@ bool parse_args(int argc, char** argv, Options* o) {
             return false;
         }
     }
+    if (!o->krum_given && o->krum_m_given) {
+        std::cerr << "--krum-m goes with --krum-f\n";
+        return false;
+    }
+    if (o->krum_given) {
+        if (o->clip_given) {
+            std::cerr << "--krum-f and --clip-norm do not compose: one of them\n";
+            return false;
+        }
+        if (o->mode != FA_FEDAVG) {
+            std::cerr << "--krum-f selects the owners of a weighted average: not with --mode "
+                      << (o->mode == FA_LITERAL ? "literal" : o->median ? "median" : "trimmed") << "\n";
+            return false;
+        }
+        if (o->rs) {
+            std::cerr << "--krum-f needs both owners of a pair on one GPU: not with --layout rs\n";
+            return false;
+        }
+        if (o->data_owners > FA_KRUM_MAX_CLIENTS) {
+            std::cerr << "--krum-f takes at most " << FA_KRUM_MAX_CLIENTS << " data owners\n";
+            return false;
+        }
+        if (o->krum_f < 0 || 2 * o->krum_f + 2 >= o->data_owners) {
+            std::cerr << "--krum-f " << o->krum_f << ": 0 <= F and 2F + 2 < " << o->data_owners << " data owners\n";
+            return false;
+        }
+        if (!o->krum_m_given) o->krum_m = o->data_owners - o->krum_f;
+        if (o->krum_m < 1 || o->krum_m > o->data_owners - o->krum_f) {
+            std::cerr << "--krum-m " << o->krum_m << ": 1 <= M <= " << o->data_owners - o->krum_f
+                      << " (DATA_OWNERS - F)\n";
+            return false;
+        }
+    }
     return o->data_owners >= 1 && o->stall_report_s > 0 && o->receipt_timeout_s >= 0;
 }
 
@@ -475,6 +525,7 @@ public:
         if (o.mode == FA_TRIMMED) FA_CHECK(fa_set_trim(ctx_, -1, o.trim));
         if (o.server.rule != FA_OPT_NONE) FA_CHECK(fa_set_server_opt(ctx_, -1, &o.server));  // before any bucket
         if (o.clip_given) FA_CHECK(fa_set_clip(ctx_, -1, o.clip_norm));
+        if (o.krum_given) FA_CHECK(fa_set_krum(ctx_, -1, o.krum_f, o.krum_m));
         if (o.rs_chunks > 0) {
             fa_tuning t{};
             t.rs_chunks = o.rs_chunks;
@@ -724,6 +775,16 @@ public:
             clip_clipped_ += (unsigned long long)clipped;
             for (int i : inc) clip_excluded_ += i ? 0 : 1;
         }
+        if (o_.krum_given) {  // what the Krum stage made of this bucket's receipts, for the round line
+            KrumRound& kr = krum_[mp];
+            kr.scores.assign((size_t)o_.data_owners, 0.0);
+            kr.selected.assign((size_t)o_.data_owners, 0);
+            int kept = 0;
+            FA_CHECK(fa_krum_get_round(ctx_, mp, nullptr, kr.scores.data(), kr.selected.data(), &kept));
+            if (kept == 0)
+                std::cerr << "[aggregator] KRUM: part " << mp << ": NO OWNER SELECTED (every score is infinite): the "
+                          << "reply of this bucket is all zeros\n";
+        }
         b.held.clear();
         b.arrived.clear();
         b.bytes_in = 0;
@@ -800,6 +861,41 @@ public:
                 std::exit(1);
             }
         }
+        return os.str();
+    }
+
+    // --krum-f: the round line's tail -- per bucket the ids of the owners left out and every owner's score in
+    // slot order (17 significant digits: they read back to the same doubles), the owners' ids in that order once.
+    std::string krum_tail() {
+        std::ostringstream os;
+        os << ",\"krum_f\":" << o_.krum_f << ",\"krum_m\":" << o_.krum_m << ",\"krum_owners\":[";
+        for (size_t k = 0; k < expected_.size(); ++k) os << (k ? "," : "") << expected_[k];
+        os << "]";
+        for (int pass = 0; pass < 2; ++pass) {
+            os << (pass == 0 ? ",\"krum_left_out\":{" : ",\"krum_scores\":{");
+            bool first = true;
+            for (auto& kv : krum_) {
+                os << (first ? "" : ",") << "\"" << kv.first << "\":[";
+                first = false;
+                bool lead = true;
+                for (size_t k = 0; k < kv.second.scores.size(); ++k) {
+                    if (pass == 0) {
+                        if (kv.second.selected[k]) continue;
+                        os << (lead ? "" : ",") << expected_[k];
+                    } else {
+                        char buf[40];
+                        const double v = kv.second.scores[k];
+                        if (std::isfinite(v)) snprintf(buf, sizeof buf, "%.17g", v);
+                        else snprintf(buf, sizeof buf, "\"%s\"", std::isnan(v) ? "nan" : "inf");
+                        os << (lead ? "" : ",") << buf;
+                    }
+                    lead = false;
+                }
+                os << "]";
+            }
+            os << "}";
+        }
+        krum_.clear();
         return os.str();
     }
 
@@ -975,6 +1071,12 @@ private:
     // --clip-norm: this round's clipped and excluded receipts and each bucket's squared distances (clip_tail)
     unsigned long long clip_clipped_ = 0, clip_excluded_ = 0;
     std::map<int, std::vector<double>> clip_q_;
+    // --krum-f: this round's scores and selection flags of each bucket, in slot order (krum_tail)
+    struct KrumRound {
+        std::vector<double> scores;
+        std::vector<int> selected;
+    };
+    std::map<int, KrumRound> krum_;
     std::map<int, int> slots_;  // client id -> slot
     std::vector<char> claimed_;  // slot -> an arrived client holds it
     std::vector<int> expected_;  // the data owners' ids in slot order
@@ -1166,7 +1268,7 @@ int main(int argc, char** argv) {
                      server_rule_name(o.server.rule), (double)o.server.lr, agg.save_server_state());
             server_tail = buf;
         }
-        const std::string clip_tail = o.clip_given ? agg.clip_tail() : std::string();
+        const std::string clip_tail = o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : std::string();
         printf("{\"round\":%d,\"phase1\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f},"
                "\"phase2\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,\"layers\":%d,"
