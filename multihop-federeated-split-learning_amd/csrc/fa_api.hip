@@ -237,6 +237,18 @@ int for_each_gpu(CopyPool* workers, int G, const std::function<int(int)>& fn) {
     return FA_OK;
 }
 
+// The scratch of a measure pass (the clip stage's norm pass, the Krum stage's distance pass) on one GPU, grown
+// on use (ensure_measure_scratch): `dev` holds room for `outs` fp64 results (a pass's sums or matrices, piece
+// after piece) followed by `parts` per-workgroup partials, `host` is the pinned array the results are read
+// back into.  One instance serves both stages and every part of a context, because every user waits on the
+// host for the stream it enqueued on before it returns, the error returns included (measure_pass,
+// measure_device): between two calls nothing on the device reads or writes it.
+struct MeasureScratch {
+    double* dev = nullptr;
+    double* host = nullptr;
+    size_t outs = 0, parts = 0;
+};
+
 struct GpuRes {
     int dev = 0;
     hipStream_t compute = nullptr, copy = nullptr, comm = nullptr;
@@ -249,16 +261,7 @@ struct GpuRes {
     std::map<hipStream_t, uint64_t> waited;  // per stream: the copy batch it last waited for
     hipEvent_t step_ev = nullptr;  // orders the rs exchange of a piece after its reduction
     void* scratch = nullptr;       // fp32 chain accumulator for a 16-bit output, D > kMaxClients
-    // clip stage: the norm pass's device scratch (the sums, then the per-workgroup partials) and the pinned
-    // array the sums are read back into, grown on use (ensure_clip_scratch)
-    double* clip_dev = nullptr;
-    double* clip_host = nullptr;
-    size_t clip_sums = 0;          // sums either array has room for
-    // Krum stage: the distance pass's device scratch (the D x D matrices, one per piece, then the per-workgroup
-    // partials) and the pinned array the matrices are read back into, grown on use (ensure_krum_scratch)
-    double* krum_dev = nullptr;
-    double* krum_host = nullptr;
-    size_t krum_dist = 0, krum_part = 0;  // doubles of matrices (either array) and of partials there is room for
+    MeasureScratch measure;        // the clip and Krum stages' measure passes
     // fa_output_crc32: the piece table (pinned staging + device copy) and the per-piece results, grown on use
     char* crc_host = nullptr;
     char* crc_dev = nullptr;
@@ -358,6 +361,11 @@ struct Part {
 // A part whose reducing calls are rounds of their own (a server-optimizer, clip or Krum stage): never batched,
 // eager or host-read, every client submitted before each.
 inline bool staged(const Part& p) { return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0; }
+// A part that gets its first stage: what this round chained or kept host-side so far goes back to the plain path.
+inline void restart_round_plain(Part& p) {
+    p.reduced = 0;
+    p.ready = false;
+}
 
 }  // namespace
 
@@ -571,25 +579,33 @@ float clip_scale(double sumsq, float max_norm, int* excluded) {
     return (float)q;
 }
 
-// Room on GPU g (the current device) for the norm pass of `sums` (client, piece) sums.
-int ensure_clip_scratch(GpuRes& r, size_t sums) {
-    if (r.clip_sums >= sums) return FA_OK;
-    if (r.clip_dev) (void)hipFree(r.clip_dev);
-    if (r.clip_host) (void)hipHostFree(r.clip_host);
-    r.clip_dev = r.clip_host = nullptr;
-    r.clip_sums = 0;
-    const size_t cap = std::max<size_t>(sums, 256);
-    const size_t dev_bytes = (cap + (size_t)fa::kMaxClients * (size_t)fa::kClipMaxPartials) * sizeof(double);
-    if (hipMalloc((void**)&r.clip_dev, dev_bytes) != hipSuccess ||
-        hipHostMalloc((void**)&r.clip_host, cap * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+void free_measure_scratch(MeasureScratch& m) {
+    if (m.dev) (void)hipFree(m.dev);
+    if (m.host) (void)hipHostFree(m.host);
+    m = MeasureScratch{};
+}
+
+// Room on the current device for a measure pass of `outs` results and `parts` partials.  Never shrinks: a
+// reallocation keeps the larger of the old and the new count of each.  stage: "clip: norm-pass", "krum:
+// distance-pass".
+int ensure_measure_scratch(MeasureScratch& m, size_t outs, size_t parts, const char* stage) {
+    if (m.dev && m.outs >= outs && m.parts >= parts) return FA_OK;
+    const size_t ocap = std::max<size_t>(std::max(outs, m.outs), 256), pcap = std::max<size_t>(std::max(parts, m.parts), 1);
+    free_measure_scratch(m);
+    const size_t dev_bytes = (ocap + pcap) * sizeof(double);
+    if (hipMalloc((void**)&m.dev, dev_bytes) != hipSuccess ||
+        hipHostMalloc((void**)&m.host, ocap * sizeof(double), hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
-        if (r.clip_dev) (void)hipFree(r.clip_dev);
-        r.clip_dev = nullptr;
-        return fail(FA_ERR_NOMEM, "clip: norm-pass scratch of %zu B failed", dev_bytes);
+        if (m.dev) (void)hipFree(m.dev);
+        m = MeasureScratch{};
+        return fail(FA_ERR_NOMEM, "%s scratch of %zu B failed", stage, dev_bytes);
     }
-    r.clip_sums = cap;
+    m.outs = ocap;
+    m.parts = pcap;
     return FA_OK;
 }
+constexpr size_t kClipParts = (size_t)fa::kMaxClients * (size_t)fa::kClipMaxPartials;  // the norm pass's partials
+inline size_t krum_parts(int D) { return (size_t)fa::krum_pairs(D) * (size_t)fa::kKrumMaxPartials; }
 
 // Enqueues the norm pass on the current device: d_sums[k] = Q_k of clients[k] (n elements of `in`) against ref,
 // k < D, in passes of kMaxClients clients; d_part: kMaxClients * kClipMaxPartials doubles of scratch.  The
@@ -685,29 +701,6 @@ void krum_weights(const float* w, const int* selected, int D, float* w_out) {
     }
 }
 
-// Room on the current device for the distance pass of `mats` matrices of D clients.
-int ensure_krum_scratch(GpuRes& r, int D, size_t mats) {
-    const size_t dist = mats * (size_t)D * (size_t)D;
-    const size_t part = (size_t)fa::krum_pairs(D) * (size_t)fa::kKrumMaxPartials;
-    if (r.krum_dist >= dist && r.krum_part >= part && r.krum_dev) return FA_OK;
-    if (r.krum_dev) (void)hipFree(r.krum_dev);
-    if (r.krum_host) (void)hipHostFree(r.krum_host);
-    r.krum_dev = r.krum_host = nullptr;
-    const size_t dcap = std::max<size_t>(std::max(dist, r.krum_dist), 256), pcap = std::max<size_t>(std::max(part, r.krum_part), 1);
-    r.krum_dist = r.krum_part = 0;
-    const size_t dev_bytes = (dcap + pcap) * sizeof(double);
-    if (hipMalloc((void**)&r.krum_dev, dev_bytes) != hipSuccess ||
-        hipHostMalloc((void**)&r.krum_host, dcap * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        if (r.krum_dev) (void)hipFree(r.krum_dev);
-        r.krum_dev = nullptr;
-        return fail(FA_ERR_NOMEM, "krum: distance-pass scratch of %zu B failed", dev_bytes);
-    }
-    r.krum_dist = dcap;
-    r.krum_part = pcap;
-    return FA_OK;
-}
-
 // Enqueues the distance pass on the current device: d_dist (D * D doubles) = the matrix of clients[0..D) (n > 0
 // elements of `in`); d_part: the partials scratch.  The vector form where every client allows it (fa_split.h).
 int pairdist_on(const fa::Tuning& tu, const void* const* clients, int D, size_t n, fa_dtype in, double* d_part,
@@ -716,6 +709,31 @@ int pairdist_on(const fa::Tuning& tu, const void* const* clients, int D, size_t 
     for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
     const fa::ClientTable t = client_table(clients, nullptr, 0, D);
     FA_HIP(fa::launch_pairdist(t, D, in, sp, d_part, d_dist, tu, s));
+    return FA_OK;
+}
+
+// The body of the two raw device entries (arguments checked): one measure pass, enqueue(call, d_part, d_out) ->
+// FA_*, on the context's scratch, or without a context on scratch of its own, freed before the return; its
+// `outs` results into h_out after the wait for the stream, which follows whatever was enqueued (MeasureScratch).
+template <typename Enqueue>
+int measure_device(fa_ctx* ctx, int gpu, void* hip_stream, size_t outs, size_t parts, const char* stage, double* h_out,
+                   Enqueue enqueue) {
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    MeasureScratch own;
+    MeasureScratch& m = ctx ? ctx->gpu[(size_t)gpu].measure : own;
+    int rc = ensure_measure_scratch(m, outs, parts, stage);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        rc = enqueue(c, m.dev + m.outs, m.dev);
+        if (!rc) e = hipMemcpyAsync(m.host, m.dev, outs * sizeof(double), hipMemcpyDeviceToHost, c.s);
+        const hipError_t es = hipStreamSynchronize(c.s);
+        if (e == hipSuccess) e = es;
+        if (!rc && e == hipSuccess) std::copy(m.host, m.host + outs, h_out);
+    }
+    if (!ctx) free_measure_scratch(own);
+    if (rc) return rc;
+    FA_HIP(e);
     return FA_OK;
 }
 
@@ -1188,48 +1206,76 @@ int host_reduce(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, const Gathe
     return FA_OK;
 }
 
-// What the clip stage makes of a round's weights (fa.h "Clip stage", rules 1-3): the included clients in
-// ascending order, their weights w'_k, and the reference's weight c0.
-struct ClipPlan {
+// What a measure-then-select stage makes of a round (fa.h "Clip stage", rules 1-3; "Krum stage", rules 1-4): the
+// clients that enter the chain in ascending order, their weights w'_k, and the weight c0 of the clip reference
+// as the chain's first term (0: none, as always for Krum).
+struct SubsetPlan {
     std::vector<int> inc;
     std::vector<float> w;
     float c0 = 0.0f;
 };
 
-// Rules 1-3 for part p (range layout, a reference present): the norm pass of every piece on every GPU, one wait
-// per GPU for its sums, then the host arithmetic.  The per-shard and per-piece sums are added in fp64 in GPU
-// order, then piece order.  Leaves the round's report in the part.
-int clip_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, ClipPlan* plan) {
-    const size_t D = (size_t)p.D;
+// A stage's measure pass over part p (range layout).  On every GPU with elements, after its H2D copies:
+// launch(g, j, clients, cnt, d_part, d_out, stream) -> FA_* enqueues the pass of piece j, in order, its `outs`
+// fp64 results into d_out (d_part: `parts` partials of scratch), then one D2H brings all the pieces' results.
+// Then, per GPU in order, one wait and each piece's results into acc[0, outs), zeroed by the caller: one rounded
+// fp64 add per element, in GPU order, then piece order (fa.h).  An error ends the enqueuing, not the waits:
+// every GPU enqueued on is waited for (MeasureScratch).
+template <typename Launch>
+int measure_pass(fa_ctx* ctx, Part& p, hipStream_t s, size_t outs, size_t parts, const char* stage, double* acc,
+                 Launch launch) {
     std::vector<const void*> ptrs;
-    for (int g = 0; g < ctx->G; ++g) {
-        if (p.cnt[(size_t)g] == 0) continue;
-        GpuRes& r = ctx->gpu[(size_t)g];
-        DeviceGuard dg(r.dev);
-        hipStream_t st = s ? s : r.compute;
+    const auto enqueue = [&](int g) -> int {
+        MeasureScratch& m = ctx->gpu[(size_t)g].measure;
+        hipStream_t st = s ? s : ctx->gpu[(size_t)g].compute;
+        const size_t np = (size_t)p.npiece[(size_t)g];
         int rc = wait_copies(ctx, g, st);
-        const size_t sums = (size_t)p.npiece[(size_t)g] * D;
-        if (rc || (rc = ensure_clip_scratch(r, sums))) return rc;
-        for (int j = 0; j < p.npiece[(size_t)g]; ++j) {
-            rc = clip_sumsq_on(ctx->tuning.tu, piece_ptrs(p, g, j, 0, p.D, ptrs), p.D, piece_cnt(p, g, j), p.in,
-                               p.cref[(size_t)g] + piece_lo(p, g, j), r.clip_dev + r.clip_sums,
-                               r.clip_dev + (size_t)j * D, st);
-            if (rc) return rc;
-        }
-        FA_HIP(hipMemcpyAsync(r.clip_host, r.clip_dev, sums * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (rc || (rc = ensure_measure_scratch(m, np * outs, parts, stage))) return rc;
+        for (size_t j = 0; j < np; ++j)
+            if ((rc = launch(g, (int)j, piece_ptrs(p, g, (int)j, 0, p.D, ptrs), piece_cnt(p, g, (int)j), m.dev + m.outs,
+                             m.dev + j * outs, st)))
+                return rc;
+        FA_HIP(hipMemcpyAsync(m.host, m.dev, np * outs * sizeof(double), hipMemcpyDeviceToHost, st));
+        return FA_OK;
+    };
+    int rc = FA_OK, tried = 0;  // GPUs [0, tried) may have work of this pass in flight
+    for (; !rc && tried < ctx->G; ++tried) {
+        if (p.cnt[(size_t)tried] == 0) continue;
+        DeviceGuard dg(ctx->gpu[(size_t)tried].dev);
+        rc = enqueue(tried);
     }
-    std::fill(p.clip_q.begin(), p.clip_q.end(), 0.0);
-    for (int g = 0; g < ctx->G; ++g) {
+    for (int g = 0; g < tried; ++g) {
         if (p.cnt[(size_t)g] == 0) continue;
         GpuRes& r = ctx->gpu[(size_t)g];
         DeviceGuard dg(r.dev);
-        FA_HIP(hipStreamSynchronize(s ? s : r.compute));
-        for (int j = 0; j < p.npiece[(size_t)g]; ++j)
-            for (size_t k = 0; k < D; ++k) {
-                volatile double q = p.clip_q[k] + r.clip_host[(size_t)j * D + k];
-                p.clip_q[k] = q;
+        const hipError_t e = hipStreamSynchronize(s ? s : r.compute);
+        if (rc) continue;
+        if (e != hipSuccess) {
+            rc = fail(FA_ERR_HIP, "hipStreamSynchronize(s ? s : r.compute): %s (%s:%d)", hipGetErrorString(e), __FILE__,
+                      __LINE__);
+            continue;
+        }
+        for (size_t j = 0; j < (size_t)p.npiece[(size_t)g]; ++j)
+            for (size_t i = 0; i < outs; ++i) {
+                volatile double q = acc[i] + r.measure.host[j * outs + i];
+                acc[i] = q;
             }
     }
+    return rc;
+}
+
+// Rules 1-3 for part p (range layout, a reference present): the norm pass (measure_pass), then the host
+// arithmetic.  Leaves the round's report in the part.
+int clip_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* plan) {
+    const size_t D = (size_t)p.D;
+    std::fill(p.clip_q.begin(), p.clip_q.end(), 0.0);
+    if (int rc = measure_pass(ctx, p, s, D, kClipParts, "clip: norm-pass", p.clip_q.data(),
+                              [&](int g, int j, const void* const* clients, size_t cnt, double* d_part, double* d_out,
+                                  hipStream_t st) {
+                                  return clip_sumsq_on(ctx->tuning.tu, clients, p.D, cnt, p.in,
+                                                       p.cref[(size_t)g] + piece_lo(p, g, j), d_part, d_out, st);
+                              }))
+        return rc;
     double W = 0.0, Wp = 0.0;
     p.clip_n = 0;
     for (size_t k = 0; k < D; ++k) {
@@ -1251,15 +1297,17 @@ int clip_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, ClipPlan* pla
     return FA_OK;
 }
 
-// Rule 4 for piece j of GPU g (the current device): the chain over the included clients with the reference as
-// its first term, into dst (dtype odt).  An f32 part passes g as the chain's first client with weight c0; a
-// 16-bit part first writes fmaf(c0, g, +0) into its fp32 buffer (a one-client f32 chain) and continues from it.
-int clip_chain(fa_ctx* ctx, Part& p, int g, int j, const ClipPlan& plan, void* dst, fa_dtype odt, hipStream_t st) {
+// The chain of a stage's plan for piece j of GPU g (the current device), into dst (dtype odt): over the plan's
+// clients (clip rule 4, Krum rule 5), with c0 != 0 the clip reference as its first term.  An f32 part passes g
+// as the chain's first client with weight c0; a 16-bit part first writes fmaf(c0, g, +0) into its fp32 buffer
+// (a one-client f32 chain) and continues from it.  Only then are p.cref and p.cinit touched: a Krum part has
+// neither.
+int subset_chain(fa_ctx* ctx, Part& p, int g, int j, const SubsetPlan& plan, void* dst, fa_dtype odt, hipStream_t st) {
     const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
     if (cnt == 0) return FA_OK;
     const fa::Tuning& tu = ctx->tuning.tu;
-    const void* ref = p.cref[(size_t)g] + lo;
     const bool lead = plan.c0 != 0.0f;
+    const void* ref = lead ? p.cref[(size_t)g] + lo : nullptr;
     if (plan.inc.empty()) {  // the first term alone, +0 without one
         if (lead) return reduce_on(ctx, g, tu, &ref, &plan.c0, 1, cnt, FA_F32, dst, odt, FA_FEDAVG, 0.0f, nullptr, st);
         FA_HIP(hipMemsetAsync(dst, 0, cnt * dsize(odt), st));
@@ -1295,46 +1343,17 @@ int clip_take_reference(Part& p, int g, int j, hipStream_t st) {
     return FA_OK;
 }
 
-// What the Krum stage makes of a round (fa.h "Krum stage", rules 1-4): the selected clients in ascending order
-// and their weights w'_k.
-struct KrumPlan {
-    std::vector<int> inc;
-    std::vector<float> w;
-};
-
-// Rules 1-4 for part p (range layout): the distance pass of every piece on every GPU, one wait per GPU for its
-// matrices, then the host arithmetic.  The per-shard and per-piece matrices are added in fp64 in GPU order,
-// then piece order.  Leaves the round's report in the part.
-int krum_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, KrumPlan* plan) {
-    const size_t D = (size_t)p.D, DD = D * D;
-    std::vector<const void*> ptrs;
-    for (int g = 0; g < ctx->G; ++g) {
-        if (p.cnt[(size_t)g] == 0) continue;
-        GpuRes& r = ctx->gpu[(size_t)g];
-        DeviceGuard dg(r.dev);
-        hipStream_t st = s ? s : r.compute;
-        int rc = wait_copies(ctx, g, st);
-        const size_t mats = (size_t)p.npiece[(size_t)g];
-        if (rc || (rc = ensure_krum_scratch(r, p.D, mats))) return rc;
-        for (int j = 0; j < p.npiece[(size_t)g]; ++j) {
-            rc = pairdist_on(ctx->tuning.tu, piece_ptrs(p, g, j, 0, p.D, ptrs), p.D, piece_cnt(p, g, j), p.in,
-                             r.krum_dev + r.krum_dist, r.krum_dev + (size_t)j * DD, st);
-            if (rc) return rc;
-        }
-        FA_HIP(hipMemcpyAsync(r.krum_host, r.krum_dev, mats * DD * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    p.krum_q.assign(DD, 0.0);
-    for (int g = 0; g < ctx->G; ++g) {
-        if (p.cnt[(size_t)g] == 0) continue;
-        GpuRes& r = ctx->gpu[(size_t)g];
-        DeviceGuard dg(r.dev);
-        FA_HIP(hipStreamSynchronize(s ? s : r.compute));
-        for (int j = 0; j < p.npiece[(size_t)g]; ++j)
-            for (size_t i = 0; i < DD; ++i) {
-                volatile double q = p.krum_q[i] + r.krum_host[(size_t)j * DD + i];
-                p.krum_q[i] = q;
-            }
-    }
+// Rules 1-4 for part p (range layout): the distance pass (measure_pass), then the host arithmetic.  Leaves the
+// round's report in the part.
+int krum_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* plan) {
+    const size_t D = (size_t)p.D;
+    p.krum_q.assign(D * D, 0.0);
+    if (int rc = measure_pass(ctx, p, s, D * D, krum_parts(p.D), "krum: distance-pass", p.krum_q.data(),
+                              [&](int, int, const void* const* clients, size_t cnt, double* d_part, double* d_out,
+                                  hipStream_t st) {
+                                  return pairdist_on(ctx->tuning.tu, clients, p.D, cnt, p.in, d_part, d_out, st);
+                              }))
+        return rc;
     p.krum_s.assign(D, 0.0);
     p.krum_sel.assign(D, 0);
     krum_select(p.krum_q.data(), p.D, p.krum_f, p.krum_m, p.krum_s.data(), p.krum_sel.data(), &p.krum_n);
@@ -1347,21 +1366,6 @@ int krum_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, KrumPlan* pla
         }
     p.krum_reported = true;
     return FA_OK;
-}
-
-// Rule 5 for piece j of GPU g (the current device): the chain over the selected clients into dst (dtype odt),
-// +0 with nobody selected.
-int krum_chain(fa_ctx* ctx, Part& p, int g, int j, const KrumPlan& plan, void* dst, fa_dtype odt, hipStream_t st) {
-    const size_t cnt = piece_cnt(p, g, j);
-    if (cnt == 0) return FA_OK;
-    if (plan.inc.empty()) {
-        FA_HIP(hipMemsetAsync(dst, 0, cnt * dsize(odt), st));
-        return FA_OK;
-    }
-    std::vector<const void*> ptrs;
-    for (int k : plan.inc) ptrs.push_back(piece_ptr(p, g, k, j));
-    return reduce_on(ctx, g, ctx->tuning.tu, ptrs.data(), plan.w.data(), (int)ptrs.size(), cnt, p.in, dst, odt, FA_FEDAVG,
-                     0.0f, nullptr, st);
 }
 
 // Enqueue the full reduction of part p on every GPU (the ctx's streams, or `s` for a one-GPU ctx):
@@ -1377,7 +1381,7 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
         // a clip stage with a reference: the norm pass and the host's wait for its sums come first (without a
         // reference the round is the bootstrap: the plain aggregate, reported as unclipped)
         const bool clip = p.clip > 0.0f, clipping = clip && p.clip_has_ref;
-        ClipPlan plan;
+        SubsetPlan plan;
         if (clip) {
             p.clip_q.assign((size_t)p.D, 0.0);
             p.clip_s.assign((size_t)p.D, 1.0f);
@@ -1388,10 +1392,9 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
                 if (int rc = clip_plan(ctx, p, w, s, &plan)) return rc;
         }
         // a Krum stage: the distance pass, the host's wait for its matrices and the selection come first
-        const bool krum = p.krum_m != 0;
-        KrumPlan kplan;
+        const bool krum = p.krum_m != 0;  // never with a clip stage
         if (krum)
-            if (int rc = krum_plan(ctx, p, w, s, &kplan)) return rc;
+            if (int rc = krum_plan(ctx, p, w, s, &plan)) return rc;
         std::vector<const void*> ptrs;
         for (int g = 0; g < G; ++g) {
             GpuRes& r = ctx->gpu[(size_t)g];
@@ -1413,10 +1416,8 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
                 if (p.mode == FA_LITERAL) {
                     const void* last = piece_ptr(p, g, p.last_slot >= 0 ? p.last_slot : p.D - 1, j);
                     rc = reduce_on(ctx, g, tu, &last, w, 1, cnt, p.in, dst, p.out, FA_LITERAL, p.divisor, nullptr, st);
-                } else if (clipping)
-                    rc = clip_chain(ctx, p, g, j, plan, adst, adt, st);
-                else if (krum)
-                    rc = krum_chain(ctx, p, g, j, kplan, adst, adt, st);
+                } else if (clipping || krum)
+                    rc = subset_chain(ctx, p, g, j, plan, adst, adt, st);
                 else
                     rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                                    mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
@@ -1813,13 +1814,8 @@ int set_part_opt(fa_ctx* ctx, Part& p, const fa_server_opt& o) {
     // the zeroing ran on the null stream, which the context's non-blocking streams do not wait for
     if (int rc = opt_quiesce(ctx)) return rc;
     p.opt = o;
-    if (fresh) {
-        // the part is non-eager and never kept host-side from here on: what this round chained or kept so far
-        // goes back to the plain path.  A rule change leaves a round already stepped as it is: the finalize
-        // after it copies out, one step per round.
-        p.reduced = 0;
-        p.ready = false;
-    }
+    // A rule change leaves a round already stepped as it is: the finalize after it copies out, one step per round.
+    if (fresh) restart_round_plain(p);
     return FA_OK;
 }
 
@@ -1853,10 +1849,7 @@ int set_part_clip(fa_ctx* ctx, Part& p, float max_norm) {
     p.clip = max_norm;
     p.clip_has_ref = false;
     p.clip_reported = false;
-    // non-eager and never kept host-side from here on: what this round chained or kept so far goes back to
-    // the plain path (as for a server-optimizer stage)
-    p.reduced = 0;
-    p.ready = false;
+    restart_round_plain(p);
     return FA_OK;
 }
 
@@ -2279,10 +2272,7 @@ void fa_destroy(fa_ctx* ctx) {
         for (hipEvent_t e : {r.copy_ev, r.step_ev})
             if (e) (void)hipEventDestroy(e);
         if (r.scratch) (void)hipFree(r.scratch);
-        if (r.clip_dev) (void)hipFree(r.clip_dev);
-        if (r.clip_host) (void)hipHostFree(r.clip_host);
-        if (r.krum_dev) (void)hipFree(r.krum_dev);
-        if (r.krum_host) (void)hipHostFree(r.krum_host);
+        free_measure_scratch(r.measure);
         if (r.crc_host) (void)hipHostFree(r.crc_host);
         if (r.crc_dev) (void)hipFree(r.crc_dev);
         for (hipStream_t s : {r.compute, r.copy, r.comm})
@@ -2627,23 +2617,10 @@ int fa_clip_sumsq_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int
     if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
     if (!d_ref) return fail(FA_ERR_ARG, "clip: d_ref is null");
     if (!aligned(d_ref, 4)) return fail(FA_ERR_ALIGN, "clip: reference not 4-byte aligned");
-    const DeviceCall c = device_call(ctx, gpu, hip_stream);
-    DeviceGuard dg(c.dev);
-    GpuRes own;  // a context-less call brings its scratch and frees it before it returns
-    GpuRes& r = ctx ? ctx->gpu[(size_t)gpu] : own;
-    int rc = ensure_clip_scratch(r, (size_t)D);
-    if (!rc) rc = clip_sumsq_on(c.tu, d_clients, D, n, in, d_ref, r.clip_dev + r.clip_sums, r.clip_dev, c.s);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(r.clip_host, r.clip_dev, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, c.s);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c.s);
-    if (!rc && e == hipSuccess) std::copy(r.clip_host, r.clip_host + D, h_sumsq);
-    if (!ctx) {
-        if (own.clip_dev) (void)hipFree(own.clip_dev);
-        if (own.clip_host) (void)hipHostFree(own.clip_host);
-    }
-    if (rc) return rc;
-    FA_HIP(e);
-    return FA_OK;
+    return measure_device(ctx, gpu, hip_stream, (size_t)D, kClipParts, "clip: norm-pass", h_sumsq,
+                          [&](const DeviceCall& c, double* d_part, double* d_out) {
+                              return clip_sumsq_on(c.tu, d_clients, D, n, in, d_ref, d_part, d_out, c.s);
+                          });
 }
 
 int fa_set_krum(fa_ctx* ctx, int part_id, int f, int m) {
@@ -2682,11 +2659,8 @@ int fa_set_krum(fa_ctx* ctx, int part_id, int f, int m) {
     p->krum_f = f;
     p->krum_m = mm;
     if (fresh) {
-        // non-eager and never kept host-side from here on: what this round chained or kept so far goes back to
-        // the plain path (as for the other stages)
         p->krum_reported = false;
-        p->reduced = 0;
-        p->ready = false;
+        restart_round_plain(*p);
     }
     return FA_OK;
 }
@@ -2740,23 +2714,10 @@ int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D
         return FA_OK;
     }
     if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
-    const DeviceCall c = device_call(ctx, gpu, hip_stream);
-    DeviceGuard dg(c.dev);
-    GpuRes own;  // a context-less call brings its scratch and frees it before it returns
-    GpuRes& r = ctx ? ctx->gpu[(size_t)gpu] : own;
-    int rc = ensure_krum_scratch(r, D, 1);
-    if (!rc) rc = pairdist_on(c.tu, d_clients, D, n, in, r.krum_dev + r.krum_dist, r.krum_dev, c.s);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(r.krum_host, r.krum_dev, DD * sizeof(double), hipMemcpyDeviceToHost, c.s);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c.s);
-    if (!rc && e == hipSuccess) std::copy(r.krum_host, r.krum_host + DD, h_dist);
-    if (!ctx) {
-        if (own.krum_dev) (void)hipFree(own.krum_dev);
-        if (own.krum_host) (void)hipHostFree(own.krum_host);
-    }
-    if (rc) return rc;
-    FA_HIP(e);
-    return FA_OK;
+    return measure_device(ctx, gpu, hip_stream, DD, krum_parts(D), "krum: distance-pass", h_dist,
+                          [&](const DeviceCall& c, double* d_part, double* d_out) {
+                              return pairdist_on(c.tu, d_clients, D, n, in, d_part, d_out, c.s);
+                          });
 }
 
 int fa_set_literal_divisor(fa_ctx* ctx, int part_id, float divisor) {

@@ -11,9 +11,10 @@
 // is no atomic anywhere, so for one layout (n, grid, pointer phases) every run gives the same bits; the order
 // itself is not part of the rule (fa.h bounds the error of any order).
 //
-// Numerics: d = x - g is one fp32 subtraction of the exactly widened input; (double)d * (double)d is exact in
-// fp64 (24 x 24 significand bits), so fma(dd, dd, acc) is the single rounding of the add.  Contraction is off
-// for the TU all the same, as in fa_server_opt.hip: nothing here may change by the compiler's choice.
+// Numerics (sq_add of fa_device.h, shared with fa_krum.hip): d = x - g is one fp32 subtraction of the exactly
+// widened input; (double)d * (double)d is exact in fp64 (24 x 24 significand bits), so fma(dd, dd, acc) is the
+// single rounding of the add.  Contraction is off for the TU all the same, as in fa_server_opt.hip: nothing
+// here may change by the compiler's choice.  The grid is measure_grid of fa_split.h over tiles of 4096 elements.
 //
 // Two forms, as the other kernel TUs: the vector form when every client and the reference share one 16-byte
 // phase, and the element form (one element per lane and load) for the head, the tail and mixed phases.
@@ -34,21 +35,6 @@ namespace {
 constexpr int kClipThreads = 256, kClipWaves = kClipThreads / 64;
 constexpr int kClipLaneElems = 16;                                  // elements of g a lane keeps in registers
 constexpr int64_t kClipTile = (int64_t)kClipThreads * kClipLaneElems;  // elements per tile
-
-// The sum of v over the wave's 64 lanes, the same bits in every lane (each step adds the two halves of a pair,
-// and fp64 addition commutes).
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double sq_add(float x, float g, double acc) {
-#pragma clang fp contract(off)
-    const float d = x - g;
-    const double dd = (double)d;
-    return __builtin_fma(dd, dd, acc);  // dd * dd is exact: one rounding, that of the add
-}
 
 // LDS: one fp64 sum per (wave, client), touched only by lane 0 of its wave between the two barriers.
 struct ClipLds {
@@ -184,29 +170,10 @@ __global__ __launch_bounds__(256) void clip_widen_kernel(const void* src, float*
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = In<T>::scalar(src, i);
 }
 
-int64_t blocks_of(int64_t tiles, const Tuning& tu) {
-    int64_t cap = kClipMaxBlocks;
-    if (tu.max_blocks > 0) cap = std::min<int64_t>(cap, tu.max_blocks);
-    return std::max<int64_t>(1, std::min(tiles, cap));
-}
-
-// The launch geometry of one pass: workgroups of the vector kernel, of the element kernel, and the partials
-// per client (their sum).
-struct ClipGrid {
-    int64_t vec_blocks, elem_blocks;
-};
-ClipGrid clip_grid(const Split& sp, const Tuning& tu) {
-    if (sp.vec && sp.nvec > 0) {
-        const int64_t tile_vecs = kClipTile / sp.V;
-        return ClipGrid{blocks_of((sp.nvec + tile_vecs - 1) / tile_vecs, tu), sp.edges() > 0 ? 1 : 0};
-    }
-    return ClipGrid{0, blocks_of((sp.n + kClipTile - 1) / kClipTile, tu)};
-}
-
 template <typename T>
-hipError_t launch_sumsq_t(const ClientTable& t, int nc, const float* ref, const Split& sp, const ClipGrid& gr,
+hipError_t launch_sumsq_t(const ClientTable& t, int nc, const float* ref, const Split& sp, const MeasureGrid& gr,
                           double* partials, double* sums, hipStream_t s) {
-    const int64_t np = gr.vec_blocks + gr.elem_blocks;
+    const int64_t np = gr.np();
     if (gr.vec_blocks > 0) {
         hipLaunchKernelGGL((clip_sumsq_vec_kernel<T>), dim3((unsigned)gr.vec_blocks), dim3(kClipThreads), 0, s, t, nc, ref,
                            sp.head, sp.nvec, partials, np);
@@ -227,7 +194,7 @@ hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const fl
                              double* partials, double* sums, const Tuning& tu, hipStream_t s) {
     if (!sp.valid() || sp.V != (in == FA_F32 ? 4 : 8)) return hipErrorInvalidValue;
     if (nc < 1 || nc > kMaxClients || sp.n <= 0 || !ref || !partials || !sums) return hipErrorInvalidValue;
-    const ClipGrid gr = clip_grid(sp, tu);
+    const MeasureGrid gr = measure_grid(sp, kClipTile, kClipMaxBlocks, tu.max_blocks);
     switch (in) {
         case FA_F32: return launch_sumsq_t<float>(t, nc, ref, sp, gr, partials, sums, s);
         case FA_BF16: return launch_sumsq_t<uint16_t>(t, nc, ref, sp, gr, partials, sums, s);

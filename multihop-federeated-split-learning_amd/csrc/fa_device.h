@@ -1,5 +1,5 @@
-// fa_device.h -- device-side helpers shared by the kernel TUs (fa_kernels.hip, fa_trimmed.hip): 16-byte loads,
-// the store policies, the bf16 / fp16 conversions and the element-type traits In<> / Out<>.
+// fa_device.h -- device-side helpers shared by the kernel TUs: 16-byte loads, the store policies, the bf16 /
+// fp16 conversions, the measure passes' fp64 sums and the element-type traits In<> / Out<>.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,6 +59,23 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ uint32_t f32_to_f16x2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, f16x2{(_Float16)lo, (_Float16)hi});
+}
+
+// The measure passes (fa_clip.hip, fa_krum.hip).  acc + ((double)fl32(x - y))^2: the fp32 subtraction of the
+// exactly widened inputs is one rounding, dd * dd is exact in fp64 (24 x 24 significand bits), so the fma's
+// single rounding is that of the add.
+__device__ __forceinline__ double sq_add(float x, float y, double acc) {
+#pragma clang fp contract(off)
+    const float d = x - y;
+    const double dd = (double)d;
+    return __builtin_fma(dd, dd, acc);
+}
+// The sum of v over the wave's 64 lanes, the same bits in every lane (each step adds the two halves of a pair,
+// and fp64 addition commutes).
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
 }
 
 // Element-type traits: a lane owns 16 bytes of every input bucket.

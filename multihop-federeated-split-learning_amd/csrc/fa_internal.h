@@ -110,8 +110,9 @@ hipError_t launch_server_opt(int rule, const OptHyper& h, const float* avg, floa
 // The clip stage's norm pass (fa.h "Clip stage"), fa_clip.hip.  sums[k] = sum_i ((double)fl32(x_{k,i} - ref_i))^2
 // over the n elements of clients t.src[0..nc), 1 <= nc <= kMaxClients (weights not read): one launch over all
 // clients writes one fp64 partial per (client, workgroup) into `partials` (room for nc * kClipMaxPartials
-// doubles), a second one adds each client's partials in a fixed order.  No atomics.  sp: the Split
-// (fa_split.h) led by the first client, ref required as well.
+// doubles; a client's are the np of measure_grid, fa_split.h, stored np apart), a second one adds each client's
+// partials in a fixed order.  No atomics.  sp: the Split (fa_split.h) led by the first client, ref required as
+// well.  The caller's scratch holds results and partials of either pass (MeasureScratch, fa_api.hip).
 constexpr int64_t kClipMaxBlocks = 2048;  // 8 workgroups per CU on 256 CUs; tiles beyond it are strided
 constexpr int64_t kClipMaxPartials = kClipMaxBlocks + 1;  // per client: the grid's, plus one for head and tail
 hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const float* ref, const Split& sp,
@@ -122,8 +123,8 @@ hipError_t launch_clip_widen(const void* src, fa_dtype dt, float* dst, int64_t n
 // := Q_ab = sum_i ((double)fl32(x_{a,i} - x_{b,i}))^2 over the n elements of clients t.src[0..D), 1 <= D <=
 // kMaxClients (weights not read), each pair computed once and mirrored, the diagonal +0: one launch over all
 // clients writes one fp64 partial per (pair, workgroup) into `partials` (room for krum_pairs(D) *
-// kKrumMaxPartials doubles; not read for D == 1), a second one adds each pair's partials in a fixed order.  No
-// atomics.  sp: the Split (fa_split.h) led by the first client.
+// kKrumMaxPartials doubles, laid out as the clip pass's; not read for D == 1), a second one adds each pair's
+// partials in a fixed order.  No atomics.  sp: the Split (fa_split.h) led by the first client.
 constexpr int64_t kKrumMaxBlocks = 1024;  // 4 workgroups of 34 KiB LDS per CU on 256 CUs; tiles beyond it are strided
 constexpr int64_t kKrumMaxPartials = kKrumMaxBlocks + 1;  // per pair: the grid's, plus one for head and tail
 inline int64_t krum_pairs(int D) { return (int64_t)D * (D - 1) / 2; }

@@ -19,8 +19,9 @@
 // for one layout (n, D, grid, pointer phases) every run gives the same bits; the order itself is not part of
 // the rule (fa.h bounds the error of any order).
 //
-// Numerics as in fa_clip.hip: d is one fp32 subtraction of the exactly widened inputs, (double)d * (double)d
-// is exact in fp64, so fma(dd, dd, acc) is the single rounding of the add.  Contraction is off for the TU.
+// Numerics: sq_add of fa_device.h, shared with fa_clip.hip (one fp32 subtraction of the exactly widened inputs,
+// an exact fp64 square, the single rounding of the add).  Contraction is off for the TU.  The grid is
+// measure_grid of fa_split.h over tiles of E elements.
 //
 // Two forms, as the other kernel TUs: the vector form fills the tile with 16-byte non-temporal loads when
 // every client shares one 16-byte phase; the element form (one element per lane and load) fills it for the
@@ -75,19 +76,6 @@ __device__ __forceinline__ void block_of(int blk, int B, int* bi, int* bj) {
     }
     *bi = i;
     *bj = i + r;
-}
-
-__device__ __forceinline__ double sq_add(float x, float y, double acc) {
-#pragma clang fp contract(off)
-    const float d = x - y;
-    const double dd = (double)d;
-    return __builtin_fma(dd, dd, acc);  // dd * dd is exact: one rounding, that of the add
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // What a lane owns: NBL blocks (on[q]: it has a q-th one) and a slice of the element groups.
@@ -293,25 +281,11 @@ __global__ __launch_bounds__(64) void pairdist_finish_kernel(const double* parti
     }
 }
 
-int64_t blocks_of(int64_t tiles, const Tuning& tu) {
-    int64_t cap = kKrumMaxBlocks;
-    if (tu.max_blocks > 0) cap = std::min<int64_t>(cap, tu.max_blocks);
-    return std::max<int64_t>(1, std::min(tiles, cap));
-}
-
 template <typename T, int NBL>
 hipError_t launch_pairdist_t(const ClientTable& t, const KrumGeom& gm, const Split& sp, double* partials, double* dist,
                              const Tuning& tu, hipStream_t s) {
-    constexpr int V = In<T>::kVec;
-    int64_t vec_blocks = 0, elem_blocks = 0;
-    if (sp.vec && sp.nvec > 0) {
-        const int64_t EV = gm.E / V;
-        vec_blocks = blocks_of((sp.nvec + EV - 1) / EV, tu);
-        elem_blocks = sp.edges() > 0 ? 1 : 0;
-    } else {
-        elem_blocks = blocks_of((sp.n + gm.E - 1) / gm.E, tu);
-    }
-    const int64_t np = vec_blocks + elem_blocks;
+    const MeasureGrid gr = measure_grid(sp, gm.E, kKrumMaxBlocks, tu.max_blocks);
+    const int64_t vec_blocks = gr.vec_blocks, elem_blocks = gr.elem_blocks, np = gr.np();
     if (vec_blocks > 0) {
         hipLaunchKernelGGL((pairdist_vec_kernel<T, NBL>), dim3((unsigned)vec_blocks), dim3(kKrumThreads), 0, s, t, gm,
                            sp.head, sp.nvec, partials, np);

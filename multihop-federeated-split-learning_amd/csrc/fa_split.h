@@ -13,7 +13,8 @@
 // One wrinkle is kept: a bucket that ends before the lead's boundary (n < lead) has head = n and no vector, and
 // there inputs were still judged by their phase (h = lead), every other operand after the clamped head
 // (h = head).  require_input and require keep both, so such a bucket takes the kernel it always took; for
-// n >= lead they are one test.  Host-only, no HIP: the CPU suite tests it (tests/tools/split_selftest.cpp).
+// n >= lead they are one test.  Host-only, no HIP: the CPU suite tests it (tests/tools/split_selftest.cpp), and
+// measure_grid below, the grid of the two measure passes over a Split (tests/tools/grid_selftest.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -42,6 +43,25 @@ inline Split split_at(const void* lead, size_t elem, size_t n) {
     const int64_t to16 = (int64_t)(((size_t)V - ((uintptr_t)lead % 16) / elem) % (size_t)V);
     const int64_t head = to16 < (int64_t)n ? to16 : (int64_t)n;
     return Split{head, ((int64_t)n - head) / V, (int64_t)n, V, to16, true};
+}
+
+// The grid of a measure pass (fa_clip.hip, fa_krum.hip) over sp in tiles of `tile` elements (a multiple of V):
+// one workgroup per tile up to `cap`, the stage's own cap lowered by Tuning::max_blocks if that is > 0, the
+// tiles beyond it strided.  With a vector part the vector kernel takes its tiles and one workgroup of the
+// element kernel the edges, if any; else the element kernel takes all n elements.  np: the partials the pass
+// writes per result, one per workgroup.
+struct MeasureGrid {
+    int64_t vec_blocks, elem_blocks;
+    int64_t np() const { return vec_blocks + elem_blocks; }
+};
+inline MeasureGrid measure_grid(const Split& sp, int64_t tile, int64_t cap, int max_blocks) {
+    if (max_blocks > 0 && max_blocks < cap) cap = max_blocks;
+    const auto blocks = [cap](int64_t n, int64_t per) {
+        const int64_t tiles = (n + per - 1) / per;
+        return tiles < 1 ? 1 : tiles < cap ? tiles : cap;
+    };
+    if (sp.vec && sp.nvec > 0) return MeasureGrid{blocks(sp.nvec, tile / sp.V), sp.edges() > 0 ? 1 : 0};
+    return MeasureGrid{0, blocks(sp.n, tile)};
 }
 
 }  // namespace fa

@@ -140,3 +140,19 @@ def test_split_rule_matches_the_four_legacy_spellings():
         assert r.returncode == 0, r.stderr[-2000:]
         res = json.loads(r.stdout.strip().splitlines()[-1])
         assert res["failed"] == 0 and res["checks"] == want, (res, want)
+
+
+def test_measure_grid_matches_the_two_legacy_ladders():
+    """The grid of a measure pass (fa::measure_grid, csrc/fa_split.h) against the two hand-written copies it
+    replaced, kept verbatim in tests/tools/grid_selftest.cpp: fa_clip.hip's clip_grid and the head of
+    fa_krum.hip's launch_pairdist_t, on both element sizes, two lead phases, the vector form allowed and refused,
+    six max_blocks and thirteen n for the clip tile and the Krum tiles of D = 3, 33, 128, and eleven cases whose
+    numbers are written out; plain and under ASan+UBSan.  The count is computed from the same ranges."""
+    subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "tools")], capture_output=True, timeout=600, check=True)
+    want = 1 + 2 * 4 * 2 * 2 * 6 * 13 + 11  # krum E; sizes x stages x phases x vec x max_blocks x n; the pinned cases
+    for exe in ("grid_selftest", "grid_selftest_asan"):
+        r = subprocess.run([os.path.join(BIN, exe)], capture_output=True, text=True, timeout=60,
+                           env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1"))
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads(r.stdout.strip().splitlines()[-1])
+        assert res["failed"] == 0 and res["checks"] == want, (res, want)
