@@ -142,6 +142,58 @@
  *              stream round trip more than a plain round), selects on the host and then enqueues the chain.  Added
  *              without a new FA_ABI_VERSION: fa_pairdist_device with n == 0 touches no device, writes D * D zeros
  *              and answers FA_OK -- that is how a caller probes for it.
+ *   Noise stage (fa_set_noise, fa_noise_device, fa_noise_host): Gaussian noise on the round's aggregate, the other
+ *              half of DP-FedAvg (McMahan et al., "Learning Differentially Private Recurrent Language Models"):
+ *              a'_i = a_i + stddev z_i with z_i a standard normal, specified bit for bit.  Parameters: stddev
+ *              (fp32, finite, > 0), seed (u64), stream (u32; within the library the part id) and round (u32).
+ *              Element i is the element's index in the whole bucket, never the index within a shard or a piece:
+ *              the result does not depend on the layout (GPU count, shards, pieces, pointer phase).  Every step
+ *              of rules 2-4 is one IEEE fp32 operation rounded to nearest-even; nothing is fused; division and
+ *              square root are correctly rounded; subnormals are kept.
+ *              1. Generator.  Philox4x32-10 (Salmon et al., "Parallel Random Numbers: As Easy as 1, 2, 3", SC'11):
+ *                 multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, ten rounds.  For
+ *                 group j = i >> 2: counter = (lo32(j), hi32(j), round, stream), key = (lo32(seed), hi32(seed)).
+ *                 Of the output words (r0, r1, r2, r3) the pair (r0, r1) makes the normals of elements 4j and
+ *                 4j + 1, the pair (r2, r3) those of 4j + 2 and 4j + 3; in a pair the first word gives the radius
+ *                 (rule 2), the second the direction (rule 3).  Known answers (counter; key; output):
+ *                   0 0 0 0; 0 0; 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *                   ffffffff x 4; ffffffff x 2; 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *                   243f6a88 85a308d3 13198a2e 03707344; a4093822 299f31d0; d16cfe09 94fdcceb 5001e420 24126ea1
+ *              2. Radius, from a word r.  N = r + 1 as an integer in 1 .. 2^32, b the position of its leading one,
+ *                 mant = the top 24 bits of N (bit b moved to bit 23, lower bits truncated, a short N shifted up).
+ *                 m = (float)mant * 2^-23 in [1, 2), e = b - 32: u = m 2^e lies in (0, 1].  If m > fl(sqrt 2):
+ *                 m = fl(m * 0.5f) (exact), e = e + 1.  f = fl(m - 1); s = fl(f / fl(2 + f)); t = fl(s s);
+ *                   p = fl(C9 t); p = fl(p + C7); p = fl(p t); p = fl(p + C5); p = fl(p t); p = fl(p + C3);
+ *                   p = fl(p t); p = fl(p s); p = fl(p + s); l = fl(p + p),       Ck = fl(1/k)
+ *                 L = fl(fl((float)e * LN2) + l), LN2 = fl(ln 2) = 0x1.62e43p-1; R = sqrt(fl(-2 * L)).
+ *                 r = 0xFFFFFFFF gives R = -0 (both normals are zeros); the largest R, from r = 0, is 6.6604.
+ *              3. Direction, from a word r.  q = r >> 30; k = (r & 0x3FFFFFFF) >> 6;
+ *                 v = (float)(k - 2^23) * 2^-23 in [-1, 1); x = fl(v * PI4), PI4 = fl(pi/4) = 0x1.921fb6p-1;
+ *                 y = fl(x x);
+ *                   p = fl(S9 y); p = fl(p + S7); p = fl(p y); p = fl(p + S5); p = fl(p y); p = fl(p + S3);
+ *                   p = fl(p y); p = fl(p x); sx = fl(p + x),    S3 = fl(-1/6), S5 = fl(1/120), S7 = fl(-1/5040),
+ *                                                                 S9 = fl(1/362880)
+ *                   p = fl(K8 y); p = fl(p + K6); p = fl(p y); p = fl(p + K4); p = fl(p y); p = fl(p + K2);
+ *                   p = fl(p y); cx = fl(p + 1),                 K2 = fl(-1/2), K4 = fl(1/24), K6 = fl(-1/720),
+ *                                                                 K8 = fl(1/40320)
+ *                 The angle is q pi/2 + x: (cos, sin) = (cx, sx) for q = 0, (-sx, cx) for 1, (-cx, -sx) for 2,
+ *                 (sx, -cx) for 3.  The four quadrants of [-pi/4, pi/4) tile the circle; no rotation by pi/4 is
+ *                 applied, so a small component keeps the relative accuracy of sx.
+ *              4. Normals and output.  From one word pair z0 = fl(R cos), z1 = fl(R sin);
+ *                 a'_i = fl(a_i + fl(stddev z_i)).  A NaN or inf in a propagates (NaN payloads unspecified).
+ *              5. Place in the round.  a is the part's fp32 aggregate exactly as for the server optimizer (the
+ *                 plain chain, the clipped or Krum subset chain, step 4 of FA_TRIMMED); a' takes its place: it
+ *                 feeds the server-optimizer stage if there is one, otherwise it is rounded once to the out dtype.
+ *                 The clip stage's new reference is the output as before: what the owners receive, noise included.
+ *                 A clip bootstrap round (no reference, nothing clipped) still gets its noise; that it bounds
+ *                 nothing is the caller's business.  One reducing call uses the part's current round and then adds
+ *                 1 to it; the call that would use 2^32 fails with FA_ERR_STATE.
+ *              Accuracy: against the same transform in fp64 from the same u and angle every normal lies within
+ *              8 * 2^-24 * max(1, |z|) (measured: 4.1 of these units).  Limits: 24-bit uniforms, so |z| <= 6.6604
+ *              and the tails end there; fp32 arithmetic, as in the usual DP libraries; Philox is not a
+ *              cryptographic generator: the privacy of the result rests on the seed staying secret and on a
+ *              (seed, stream, round) triple never being used twice.  Added without a new FA_ABI_VERSION:
+ *              fa_noise_device with n == 0 touches no device and answers FA_OK -- that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -493,6 +545,38 @@ int fa_krum_weights(const float* w, const int* selected, int D, float* w_out);
  * stream), waits for it and returns the matrix. */
 int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, double* h_dist,
                        void* hip_stream);
+
+/* Noise stage: Gaussian noise on a part's fp32 aggregate (the header comment, "Noise stage").  Gives a part the
+ * stage with standard deviation stddev > 0 and the seed (part_id >= 0; the part id is the stream; calling again
+ * changes stddev and seed and keeps the round counter), or sets the context default that FA_FEDAVG and FA_TRIMMED
+ * parts defined later take (part_id < 0; FA_LITERAL parts ignore it).  stddev == 0 removes the stage (and the fp32
+ * aggregate buffer of a 16-bit part, unless a server optimizer needs it); a stage given anew starts at round 0.
+ * FA_ERR_ARG, naming the cause: stddev not finite or < 0, an FA_LITERAL part, an FA_SHARD_CLIENT_RS context (its
+ * aggregate is not bit-specified).  FA_ERR_NOMEM when the buffer cannot be allocated.  The stage composes with the
+ * clip stage, the Krum stage, the server optimizers and FA_TRIMMED, in any call order, and with range shards and
+ * range pieces.  Like the other stage parts a noise part is never kept host-side (fa_bucket_host_read says 0),
+ * FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager, it gets its own launches in fa_reduce_parts, and a reducing call
+ * needs every client submitted (FA_ERR_STATE otherwise); fa_reduce_part marks the round reduced.  Each reducing
+ * call uses the part's round counter and then adds 1 to it: calling fa_reduce_part twice draws two noises. */
+int fa_set_noise(fa_ctx* ctx, int part_id, float stddev, uint64_t seed);
+/* The stage a part has (*stddev == 0: none), or with part_id < 0 the context default.  Either pointer may be NULL. */
+int fa_get_noise(fa_ctx* ctx, int part_id, float* stddev, uint64_t* seed);
+/* The round counter the part's next reducing call uses, in 0 .. 2^32 (2^32: that call fails with FA_ERR_STATE).
+ * set: round <= 2^32, to replay a round or to continue a sequence after a restart.  FA_ERR_STATE on a part without
+ * the stage. */
+int fa_noise_get_round(fa_ctx* ctx, int part_id, uint64_t* round);
+int fa_noise_set_round(fa_ctx* ctx, int part_id, uint64_t round);
+/* Rules 1-4 on raw device pointers: d_out[i] (n of `out`, one rounding) = fl(d_avg[i] + fl(stddev z_{idx0 + i})) over
+ * the n fp32 of d_avg on device `gpu`; d_out may be d_avg itself for FA_F32.  ctx may be NULL (then `gpu` is the HIP
+ * device).  Every argument is checked before any device call: stddev (finite, > 0), the out dtype, idx0 + n < 2^64,
+ * and for n > 0 null pointers and element alignment (FA_ERR_ALIGN); with n == 0 and valid arguments it returns FA_OK
+ * without touching a device.  Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
+int fa_noise_device(fa_ctx* ctx, int gpu, const float* d_avg, size_t n, void* d_out, fa_dtype out, float stddev,
+                    uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, void* hip_stream);
+/* Rules 1-4's normals, pure host arithmetic, usable without a device: z[0, n) = the unit normals of elements idx0 ..
+ * idx0 + n - 1 under (seed, stream, round), the bits the kernel adds (built without contraction: also on a host
+ * with FMA units).  To audit a round: out == fl(a + fl(stddev z)). */
+int fa_noise_host(uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, size_t n, float* z);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

@@ -102,6 +102,12 @@ def lib():
         "fa_krum_select": (I, [P, I, I, I, P, P, ctypes.POINTER(I)]),
         "fa_krum_weights": (I, [P, P, I, P]),
         "fa_pairdist_device": (I, [P, I, P, I, S, I, P, P]),
+        "fa_set_noise": (I, [P, I, F, U64]),
+        "fa_get_noise": (I, [P, I, ctypes.POINTER(F), ctypes.POINTER(U64)]),
+        "fa_noise_get_round": (I, [P, I, ctypes.POINTER(U64)]),
+        "fa_noise_set_round": (I, [P, I, U64]),
+        "fa_noise_device": (I, [P, I, P, S, P, I, F, U64, U32, U32, U64, P]),
+        "fa_noise_host": (I, [U64, U32, U32, U64, S, P]),
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
         "fa_submit_gather": (I, [P, I, I, I, P, P, F]),
@@ -319,6 +325,24 @@ def krum_weights(weights, selected):
     out = np.empty(w.size, np.float32)
     check(lib().fa_krum_weights(w.ctypes.data, sel.ctypes.data, w.size, out.ctypes.data))
     return out
+
+
+def noise_device(avg, n, out, out_dtype=F32, stddev=1.0, seed=0, stream_id=0, round=0, idx0=0, stream=None, gpu=0,
+                 ctx=None):
+    """fa_noise_device: out[i] = avg[i] + stddev z_{idx0 + i} over n device-resident fp32 (fa.h "Noise stage"), out in
+    out_dtype with one rounding (`avg` itself for F32: in place).  stream_id is the generator's stream word (the
+    library uses the part id), `stream` the HIP stream.  Enqueued, not synchronized.  With n == 0 no device is
+    touched: the feature probe."""
+    check(lib().fa_noise_device(ctx.handle if ctx is not None else None, gpu, _addr(avg), n, _addr(out), out_dtype,
+                                float(stddev), int(seed), int(stream_id), int(round), int(idx0), _stream(stream)))
+
+
+def noise_host(seed, stream_id, round, idx0, n):
+    """fa_noise_host (host arithmetic): the n unit normals (np.float32) of bucket elements idx0 .. idx0 + n - 1 under
+    (seed, stream_id, round), the bits the kernel adds."""
+    z = np.empty(n, np.float32)
+    check(lib().fa_noise_host(int(seed), int(stream_id), int(round), int(idx0), n, z.ctypes.data))
+    return z
 
 
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
@@ -612,6 +636,28 @@ class Aggregator:
         check(lib().fa_krum_get_round(self.handle, part_id, q.ctypes.data, s.ctypes.data, sel.ctypes.data,
                                       ctypes.byref(ns)))
         return q, s, sel.astype(bool)
+
+    def set_noise(self, stddev, seed, part_id=-1):
+        """fa_set_noise: Gaussian noise of standard deviation `stddev` on the part's fp32 aggregate, drawn from
+        `seed` (u64), the part id and the part's round counter (part_id < 0: the default of FEDAVG and TRIMMED parts
+        defined later); again changes stddev and seed and keeps the round; stddev=0 removes the stage."""
+        check(lib().fa_set_noise(self.handle, part_id, float(stddev), int(seed)))
+
+    def noise(self, part_id=-1):
+        """fa_get_noise: (stddev, seed) of the part's stage (stddev 0: none), or of the context default."""
+        sd, seed = ctypes.c_float(), ctypes.c_uint64()
+        check(lib().fa_get_noise(self.handle, part_id, ctypes.byref(sd), ctypes.byref(seed)))
+        return sd.value, seed.value
+
+    def noise_round(self, part_id):
+        """fa_noise_get_round: the round the part's next reducing call draws its noise from."""
+        r = ctypes.c_uint64()
+        check(lib().fa_noise_get_round(self.handle, part_id, ctypes.byref(r)))
+        return r.value
+
+    def set_noise_round(self, part_id, r):
+        """fa_noise_set_round: replay a round, or continue a sequence after a restart."""
+        check(lib().fa_noise_set_round(self.handle, part_id, int(r)))
 
     def submit(self, part_id, slot, host, weight=1.0, pinned=False):
         host = np.ascontiguousarray(host)

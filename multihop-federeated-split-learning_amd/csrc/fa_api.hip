@@ -290,6 +290,7 @@ struct Run {
 };
 
 struct Part {
+    int id = 0;  // its part_id (the noise stage's stream)
     size_t n = 0;
     fa_dtype in = FA_F32, out = FA_F32;
     int D = 0;
@@ -332,8 +333,9 @@ struct Part {
     std::vector<std::vector<HostSeg>> host_src;
     int n_host = 0;  // slots whose receipt is kept host-side this round
     // Server-optimizer stage (fa.h "Server optimizer"; opt.rule == FA_OPT_NONE: none).  Per GPU the fp32 state
-    // over its cnt elements (ov only for the adaptive rules) and, for a 16-bit output, the fp32 buffer the
-    // round's aggregate is reduced into; each its own allocation, freed with the stage or the part.
+    // over its cnt elements (ov only for the adaptive rules), each its own allocation, freed with the stage or
+    // the part.  oavg: for a 16-bit output, the fp32 buffer the round's aggregate is reduced into, there while
+    // the part has this stage or the noise stage (ensure_oavg, drop_oavg_if_unused).
     fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};
     std::vector<float*> ox, om, ov, oavg;
     bool opt_master = false;  // x holds a model (set, or bootstrapped): the next reduction is a step
@@ -356,11 +358,18 @@ struct Part {
     std::vector<double> krum_q, krum_s;
     std::vector<int> krum_sel;
     int krum_n = 0;
+    // Noise stage (fa.h "Noise stage"; noise == 0: none): stddev, the seed and the round the next reducing call
+    // uses (2^32: that call is refused).  Host state only, besides oavg above.
+    float noise = 0.0f;
+    uint64_t noise_seed = 0;
+    uint64_t noise_round = 0;
 };
 
-// A part whose reducing calls are rounds of their own (a server-optimizer, clip or Krum stage): never batched,
-// eager or host-read, every client submitted before each.
-inline bool staged(const Part& p) { return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0; }
+// A part whose reducing calls are rounds of their own (a server-optimizer, clip, Krum or noise stage): never
+// batched, eager or host-read, every client submitted before each.
+inline bool staged(const Part& p) {
+    return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0 || p.noise > 0.0f;
+}
 // A part that gets its first stage: what this round chained or kept host-side so far goes back to the plain path.
 inline void restart_round_plain(Part& p) {
     p.reduced = 0;
@@ -377,6 +386,8 @@ struct fa_ctx {
     fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};  // default stage of FedAvg / trimmed parts defined later
     float clip = 0.0f;          // default clip bound of FedAvg parts defined later (0: none)
     int krum_f = 0, krum_m = 0; // default Krum stage of FedAvg parts defined later (m == 0: none, -1: D - f)
+    float noise = 0.0f;         // default noise stage of FedAvg / trimmed parts defined later (0: none)
+    uint64_t noise_seed = 0;
     CtxTuning tuning;
     std::vector<GpuRes> gpu;
     std::map<int, Part> parts;
@@ -482,6 +493,18 @@ int opt_on(const fa::Tuning& tu, int rule, const fa_server_opt& o, const float* 
     FA_HIP(fa::launch_server_opt(rule, opt_hyper(o), avg, x, m, v, out, odt, sp, tu, s));
     return FA_OK;
 }
+
+// One launch of the noise stage on the current device: out (dtype odt; avg itself for an in-place f32 pass) :=
+// avg + stddev z over n elements that are bucket elements idx0 .., split (fa_split.h) with avg in the lead.
+int noise_on(const fa::Tuning& tu, const float* avg, void* out, fa_dtype odt, float stddev, uint64_t seed, uint32_t stream,
+             uint32_t round, uint64_t idx0, size_t n, hipStream_t s) {
+    if (n == 0) return FA_OK;
+    fa::Split sp = fa::split_at(avg, 4, n);
+    sp.require(out, dsize(odt));
+    FA_HIP(fa::launch_noise(avg, out, odt, stddev, seed, stream, round, idx0, sp, tu, s));
+    return FA_OK;
+}
+constexpr uint64_t kNoiseRounds = (uint64_t)1 << 32;  // rounds 0 .. 2^32 - 1 exist
 
 // The device reduction for one GPU, shared by every entry: D clients (any D >= 1; more than kMaxClients
 // continue the chain from an fp32 accumulator in further passes) -> dst.  `divisor` is the mode's parameter:
@@ -831,20 +854,48 @@ int check_part(fa_ctx* ctx, int part_id, Part** out) {
     return FA_OK;
 }
 
+// The fp32 aggregate buffer of a 16-bit part: wanted while it has a server-optimizer or a noise stage.
+inline bool wants_oavg(const Part& p) { return p.out != FA_F32 && (p.opt.rule != FA_OPT_NONE || p.noise > 0.0f); }
+void drop_oavg_if_unused(fa_ctx* ctx, Part& p) {
+    if (wants_oavg(p)) return;
+    for (size_t g = 0; g < p.oavg.size(); ++g) {
+        DeviceGuard dg(ctx->gpu[g].dev);
+        if (p.oavg[g]) (void)hipFree(p.oavg[g]);  // waits for the device's pending work
+    }
+    p.oavg.clear();
+}
+// Allocates what is missing of it (`stage` names the caller in the message); on failure what was there stays.
+int ensure_oavg(fa_ctx* ctx, Part& p, const char* stage) {
+    if (!wants_oavg(p)) return FA_OK;
+    const size_t G = (size_t)ctx->G;
+    if (p.oavg.size() != G) p.oavg.assign(G, nullptr);
+    for (size_t g = 0; g < G; ++g) {
+        if (p.oavg[g]) continue;
+        DeviceGuard dg(ctx->gpu[g].dev);
+        const size_t bytes = std::max<size_t>(16, p.cnt[g] * 4);
+        if (hipMalloc((void**)&p.oavg[g], bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p.oavg[g] = nullptr;
+            return fail(FA_ERR_NOMEM, "%s: aggregate buffer alloc of %zu B failed on GPU %zu", stage, bytes, g);
+        }
+    }
+    return FA_OK;
+}
+
 // Frees the stage's arrays on every GPU (hipFree waits for the device's pending work) and forgets the master.
 void free_opt(fa_ctx* ctx, Part& p) {
     for (size_t g = 0; g < p.ox.size(); ++g) {
         DeviceGuard dg(ctx->gpu[g].dev);
-        for (auto* arr : {&p.ox, &p.om, &p.ov, &p.oavg})
+        for (auto* arr : {&p.ox, &p.om, &p.ov})
             if (g < arr->size() && (*arr)[g]) (void)hipFree((*arr)[g]);
     }
     p.ox.clear();
     p.om.clear();
     p.ov.clear();
-    p.oavg.clear();
     p.opt = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};
     p.opt_master = false;
     p.opt_steps = 0;
+    drop_oavg_if_unused(ctx, p);
 }
 
 // The same for the clip stage: its arrays go, the reference is forgotten.
@@ -862,6 +913,7 @@ void free_clip(fa_ctx* ctx, Part& p) {
 }
 
 void free_part(fa_ctx* ctx, Part& p) {
+    p.noise = 0.0f;
     free_opt(ctx, p);
     free_clip(ctx, p);
     for (size_t g = 0; g < p.pool.size(); ++g) {
@@ -1377,6 +1429,10 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
     // small receipts kept where they arrived are read there only by the finalize that ends their round (the
     // caller keeps them until then); a reduction before it takes them into the slots first
     if (int rc = host_flush(ctx, p)) return rc;
+    const bool noisy = p.noise > 0.0f;  // never on an rs part
+    if (noisy && p.noise_round >= kNoiseRounds)
+        return fail(FA_ERR_STATE, "noise: part %d has used all 2^32 rounds of its seed (fa_set_noise a new seed and "
+                                  "fa_noise_set_round)", p.id);
     if (!p.rs) {
         // a clip stage with a reference: the norm pass and the host's wait for its sums come first (without a
         // reference the round is the bootstrap: the plain aggregate, reported as unclipped)
@@ -1407,12 +1463,13 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
                 const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
                 void* dst = static_cast<char*>(p.dout[(size_t)g]) + lo * dsize(p.out);
                 // the aggregate into adst (dst without a stage; FA_LITERAL never has one) -- clipped, if the part has a
-                // reference; with a server optimizer in fp32 (an f32 part: in its output, where the stage then runs in
-                // place), then one step or the bootstrap of a part without a master -- then the new reference
-                const bool opt = p.opt.rule != FA_OPT_NONE;
-                float* avg = !opt ? nullptr : p.out == FA_F32 ? static_cast<float*>(dst) : p.oavg[(size_t)g] + lo;
-                void* adst = opt ? (void*)avg : dst;
-                const fa_dtype adt = opt ? FA_F32 : p.out;
+                // reference; with a server optimizer or a noise stage in fp32 (an f32 part: in its output, where the
+                // stages then run in place) -- then the noise (in place before a server optimizer, else into dst with
+                // the one rounding), then one step or the bootstrap of a part without a master, then the new reference
+                const bool opt = p.opt.rule != FA_OPT_NONE, wide = opt || noisy;
+                float* avg = !wide ? nullptr : p.out == FA_F32 ? static_cast<float*>(dst) : p.oavg[(size_t)g] + lo;
+                void* adst = wide ? (void*)avg : dst;
+                const fa_dtype adt = wide ? FA_F32 : p.out;
                 if (p.mode == FA_LITERAL) {
                     const void* last = piece_ptr(p, g, p.last_slot >= 0 ? p.last_slot : p.D - 1, j);
                     rc = reduce_on(ctx, g, tu, &last, w, 1, cnt, p.in, dst, p.out, FA_LITERAL, p.divisor, nullptr, st);
@@ -1421,6 +1478,9 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
                 else
                     rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                                    mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
+                if (!rc && noisy)
+                    rc = noise_on(tu, avg, opt ? (void*)avg : dst, opt ? FA_F32 : p.out, p.noise, p.noise_seed,
+                                  (uint32_t)p.id, (uint32_t)p.noise_round, (uint64_t)(p.off[(size_t)g] + lo), cnt, st);
                 if (!rc && opt)
                     rc = opt_on(tu, p.opt_master ? p.opt.rule : fa::kOptBoot, p.opt, avg, p.ox[(size_t)g] + lo,
                                 p.om[(size_t)g] + lo, opt_adaptive(p.opt.rule) ? p.ov[(size_t)g] + lo : nullptr, cnt,
@@ -1436,6 +1496,7 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
             p.opt_master = true;
         }
         if (clip) p.clip_has_ref = true;  // what this round sent out
+        if (noisy) ++p.noise_round;       // one reducing call = one round of the generator
         return FA_OK;
     }
     if (p.mode == FA_LITERAL) {  // the last client's GPU computes the whole bucket; nothing to exchange
@@ -1780,7 +1841,6 @@ int set_part_opt(fa_ctx* ctx, Part& p, const fa_server_opt& o) {
         p.ox.assign(G, nullptr);
         p.om.assign(G, nullptr);
         p.ov.assign(G, nullptr);
-        p.oavg.assign(G, nullptr);
         p.opt_master = false;
         p.opt_steps = 0;
     }
@@ -1803,7 +1863,6 @@ int set_part_opt(fa_ctx* ctx, Part& p, const fa_server_opt& o) {
         int rc = need(p.ox, true, fresh);
         if (!rc) rc = need(p.om, true, true);
         if (!rc) rc = need(p.ov, opt_adaptive(o.rule), true);
-        if (!rc) rc = need(p.oavg, p.out != FA_F32, false);
         if (rc) {
             const std::string why = g_err;
             free_opt(ctx, p);
@@ -1814,6 +1873,12 @@ int set_part_opt(fa_ctx* ctx, Part& p, const fa_server_opt& o) {
     // the zeroing ran on the null stream, which the context's non-blocking streams do not wait for
     if (int rc = opt_quiesce(ctx)) return rc;
     p.opt = o;
+    if (int rc = ensure_oavg(ctx, p, "server opt")) {
+        const std::string why = g_err;
+        free_opt(ctx, p);
+        g_err = why;
+        return rc;
+    }
     // A rule change leaves a round already stepped as it is: the finalize after it copies out, one step per round.
     if (fresh) restart_round_plain(p);
     return FA_OK;
@@ -1850,6 +1915,36 @@ int set_part_clip(fa_ctx* ctx, Part& p, float max_norm) {
     p.clip_has_ref = false;
     p.clip_reported = false;
     restart_round_plain(p);
+    return FA_OK;
+}
+
+// fa_set_noise on a part (stddev checked; not FA_LITERAL, not rs).  0: the stage goes, and the aggregate buffer
+// unless a server optimizer keeps it.  A part that has the stage: stddev and seed change, the round stays.
+// Else the stage starts at round 0, a 16-bit part gets its fp32 aggregate buffer.
+int set_part_noise(fa_ctx* ctx, Part& p, float stddev, uint64_t seed) {
+    if (stddev == 0.0f) {
+        p.noise = 0.0f;
+        p.noise_seed = 0;
+        p.noise_round = 0;
+        drop_oavg_if_unused(ctx, p);
+        return FA_OK;
+    }
+    const bool fresh = !(p.noise > 0.0f);
+    p.noise = stddev;
+    if (int rc = ensure_oavg(ctx, p, "noise")) {
+        if (fresh) {
+            const std::string why = g_err;
+            p.noise = 0.0f;
+            drop_oavg_if_unused(ctx, p);  // what the failed attempt did allocate
+            g_err = why;
+        }
+        return rc;
+    }
+    p.noise_seed = seed;
+    if (fresh) {
+        p.noise_round = 0;
+        restart_round_plain(p);
+    }
     return FA_OK;
 }
 
@@ -2313,6 +2408,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
         ctx->parts.erase(it);
     }
     Part p;
+    p.id = part_id;
     p.n = n_elems;
     p.in = in;
     p.out = out;
@@ -2327,7 +2423,9 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     const size_t G = (size_t)ctx->G;
     const bool staged = ctx->opt.rule != FA_OPT_NONE && mode != FA_LITERAL && !rs;  // takes the context's stage
     const bool clipped = ctx->clip > 0.0f && mode == FA_FEDAVG && !rs;  // takes the context's clip bound
-    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged && !clipped && !krummed;
+    const bool noisy = ctx->noise > 0.0f && mode != FA_LITERAL && !rs;  // takes the context's noise stage
+    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged && !clipped &&
+                       !krummed && !noisy;
     if (rs) {
         const size_t unit = G * kShardUnit;
         p.npad = (n_elems + unit - 1) / unit * unit;
@@ -2425,6 +2523,14 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     if (krummed) {
         p.krum_f = ctx->krum_f;
         p.krum_m = krum_m;
+    }
+    if (noisy) {
+        if (int rc = set_part_noise(ctx, p, ctx->noise, ctx->noise_seed)) {
+            const std::string why = g_err;
+            free_part(ctx, p);
+            g_err = why;
+            return rc;
+        }
     }
     ctx->parts.emplace(part_id, std::move(p));
     return FA_OK;
@@ -2718,6 +2824,90 @@ int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D
                           [&](const DeviceCall& c, double* d_part, double* d_out) {
                               return pairdist_on(c.tu, d_clients, D, n, in, d_part, d_out, c.s);
                           });
+}
+
+int fa_set_noise(fa_ctx* ctx, int part_id, float stddev, uint64_t seed) {
+    g_err.clear();
+    if (!finite_f(stddev) || stddev < 0.0f) return fail(FA_ERR_ARG, "noise: stddev %g must be finite and >= 0", (double)stddev);
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (stddev > 0.0f && (ctx->flags & FA_SHARD_CLIENT_RS))
+        return fail(FA_ERR_ARG, "noise: not on an FA_SHARD_CLIENT_RS context (its aggregate is not bit-specified; use "
+                                "FA_SHARD_RANGE)");
+    if (part_id < 0) {
+        ctx->noise = stddev;
+        ctx->noise_seed = stddev > 0.0f ? seed : 0;
+        return FA_OK;
+    }
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (stddev > 0.0f && p->mode == FA_LITERAL) return fail(FA_ERR_ARG, "noise: part %d is an FA_LITERAL part", part_id);
+    return set_part_noise(ctx, *p, stddev, seed);
+}
+
+int fa_get_noise(fa_ctx* ctx, int part_id, float* stddev, uint64_t* seed) {
+    g_err.clear();
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    float sd = ctx->noise;
+    uint64_t sv = ctx->noise_seed;
+    if (part_id >= 0) {
+        Part* p;
+        int rc = check_part(ctx, part_id, &p);
+        if (rc) return rc;
+        sd = p->noise;
+        sv = p->noise_seed;
+    }
+    if (stddev) *stddev = sd;
+    if (seed) *seed = sv;
+    return FA_OK;
+}
+
+int fa_noise_get_round(fa_ctx* ctx, int part_id, uint64_t* round) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (!(p->noise > 0.0f)) return fail(FA_ERR_STATE, "part %d has no noise stage", part_id);
+    if (!round) return fail(FA_ERR_ARG, "round is null");
+    *round = p->noise_round;
+    return FA_OK;
+}
+
+int fa_noise_set_round(fa_ctx* ctx, int part_id, uint64_t round) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (!(p->noise > 0.0f)) return fail(FA_ERR_STATE, "part %d has no noise stage", part_id);
+    if (round > kNoiseRounds) return fail(FA_ERR_ARG, "noise: round %llu beyond 2^32", (unsigned long long)round);
+    p->noise_round = round;
+    return FA_OK;
+}
+
+int fa_noise_device(fa_ctx* ctx, int gpu, const float* d_avg, size_t n, void* d_out, fa_dtype out, float stddev,
+                    uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (!finite_f(stddev) || !(stddev > 0.0f)) return fail(FA_ERR_ARG, "noise: stddev %g must be finite and > 0", (double)stddev);
+    if (!dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
+    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "noise: idx0 + n beyond 2^64");
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) return FA_OK;
+    if (!d_avg || !d_out) return fail(FA_ERR_ARG, "noise: %s pointer is null", !d_avg ? "d_avg" : "d_out");
+    if (!aligned(d_avg, 4)) return fail(FA_ERR_ALIGN, "noise: aggregate not 4-byte aligned");
+    if (!aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    return noise_on(c.tu, d_avg, d_out, out, stddev, seed, stream, round, idx0, n, c.s);
+}
+
+int fa_noise_host(uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, size_t n, float* z) {
+    g_err.clear();
+    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "noise: idx0 + n beyond 2^64");
+    if (n == 0) return FA_OK;
+    if (!z) return fail(FA_ERR_ARG, "noise: z is null");
+    fa::noise_host(seed, stream, round, idx0, n, z);
+    return FA_OK;
 }
 
 int fa_set_literal_divisor(fa_ctx* ctx, int part_id, float divisor) {

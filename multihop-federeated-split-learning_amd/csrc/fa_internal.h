@@ -130,6 +130,14 @@ constexpr int64_t kKrumMaxPartials = kKrumMaxBlocks + 1;  // per pair: the grid'
 inline int64_t krum_pairs(int D) { return (int64_t)D * (D - 1) / 2; }
 hipError_t launch_pairdist(const ClientTable& t, int D, fa_dtype in, const Split& sp, double* partials, double* dist,
                            const Tuning& tu, hipStream_t s);
+// The noise stage (fa.h "Noise stage"), fa_noise.hip.  out[i] (dtype odt, one rounding) := fl(avg[i] + fl(stddev z_i))
+// over n elements, z_i the unit normal of bucket element idx0 + i under (seed, stream, round): the result does not
+// depend on how a bucket is cut into launches.  out may be avg itself for FA_F32.  sp: the Split (fa_split.h) led by
+// avg, 4 elements per vector, out required as well.
+hipError_t launch_noise(const float* avg, void* out, fa_dtype odt, float stddev, uint64_t seed, uint32_t stream,
+                        uint32_t round, uint64_t idx0, const Split& sp, const Tuning& tu, hipStream_t s);
+// The same normals on the host (fa_noise_host): z[0, n) := z_{idx0} .. z_{idx0 + n - 1}.  The kernel's own source.
+void noise_host(uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, size_t n, float* z);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
                        const Tuning& tu, hipStream_t s);

@@ -32,6 +32,8 @@
 // norm of C before the FedAvg chain (fa.h "Clip stage"); --clip-state FILE carries that model across restarts.
 // --krum-f F [--krum-m M] averages, per bucket, only the M owners (default D - F) whose receipts lie closest to
 // the others' (Krum / Multi-Krum, fa.h "Krum stage"); the stage keeps no state across rounds.
+// --dp-noise-multiplier Z (with --clip-norm C) adds Gaussian noise of stddev Z C max_k w_k to every bucket's clipped
+// aggregate (fa.h "Noise stage"): DP-FedAvg; the seed is fresh entropy at every start unless --dp-seed fixes it.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -41,6 +43,7 @@
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <random>
 #include <set>
 #include <memory>
 #include <sstream>
@@ -101,6 +104,12 @@ struct Options {
     // defined); M defaults to DATA_OWNERS - F
     int krum_f = 0, krum_m = -1;
     bool krum_given = false, krum_m_given = false;
+    // --dp-noise-multiplier Z [--dp-seed S]: the noise stage of every bucket (fa_set_noise on the context, before any
+    // bucket is defined) with stddev = Z * C * max_k w_k, C the --clip-norm; the seed comes from the operating
+    // system's entropy at every start unless --dp-seed fixes it
+    double dp_z = 0.0;
+    uint64_t dp_seed = 0;
+    bool dp_given = false, dp_seed_given = false;
 };
 
 const char* server_rule_name(int rule) {
@@ -244,6 +253,7 @@ void usage() {
                  "        [--server-tau T] [--server-state FILE]]\n"
                  "       [--clip-norm C [--clip-state FILE]]\n"
                  "       [--krum-f F [--krum-m M]]\n"
+                 "       [--dp-noise-multiplier Z [--dp-seed S]]\n"
                  "--mode trimmed: per element the T lowest and T highest of the owners' values are dropped and the\n"
                  "rest averaged (2T < DATA_OWNERS <= 128; without --trim, and with --mode median, the median), so up\n"
                  "to T owners that send NaN, inf or huge values change no reply; --samples is ignored; not with\n"
@@ -262,6 +272,11 @@ void usage() {
                  "lie closest to the others' are averaged, with their own weights scaled up to the round's mass; F is\n"
                  "the number of owners assumed Byzantine, 0 <= F, 2F + 2 < DATA_OWNERS <= 128, 1 <= M <= DATA_OWNERS - F;\n"
                  "not with --clip-norm, --mode literal|trimmed|median or --layout rs.\n"
+                 "--dp-noise-multiplier Z (with --clip-norm C): Gaussian noise of standard deviation Z * C * max_k w_k (w_k\n"
+                 "the round's weights: the sensitivity of the clipped weighted sum to one owner) is added to every bucket's\n"
+                 "aggregate before it is stepped or replied: DP-FedAvg.  The seed is drawn from the operating system at\n"
+                 "every start, never stored, and no noise is ever replayed; --dp-seed S (u64) fixes it to reproduce a run,\n"
+                 "which voids the guarantee.  Z finite and > 0; not with --mode literal or --layout rs.\n"
                  "A bucket takes the dtype of its first receipt's parameters (all fp32, all bf16 or all fp16, by\n"
                  "their storage type) and is reduced and replied in it; a later receipt of another size or dtype\n"
                  "ends the process (exit 1).\n";
@@ -349,6 +364,12 @@ bool parse_args(int argc, char** argv, Options* o) {
         } else if (a == "--krum-m") {
             o->krum_m = std::atoi(val("--krum-m"));
             o->krum_m_given = true;
+        } else if (a == "--dp-noise-multiplier") {
+            o->dp_z = std::atof(val("--dp-noise-multiplier"));
+            o->dp_given = true;
+        } else if (a == "--dp-seed") {
+            o->dp_seed = (uint64_t)std::strtoull(val("--dp-seed"), nullptr, 0);
+            o->dp_seed_given = true;
         } else if (a == "--trim") {
             o->trim = std::atoi(val("--trim"));
             o->trim_given = true;
@@ -419,6 +440,28 @@ bool parse_args(int argc, char** argv, Options* o) {
         }
         if (adaptive && (!std::isfinite(so.tau) || !(so.tau > 0))) {
             std::cerr << "--server-tau " << so.tau << ": finite and > 0\n";
+            return false;
+        }
+    }
+    if (!o->dp_given && o->dp_seed_given) {
+        std::cerr << "--dp-seed goes with --dp-noise-multiplier\n";
+        return false;
+    }
+    if (o->dp_given) {
+        if (o->mode == FA_LITERAL) {
+            std::cerr << "--dp-noise-multiplier adds noise to a clipped weighted average: not with --mode literal\n";
+            return false;
+        }
+        if (o->rs) {
+            std::cerr << "--dp-noise-multiplier needs a bit-specified aggregate: not with --layout rs\n";
+            return false;
+        }
+        if (!o->clip_given) {
+            std::cerr << "--dp-noise-multiplier needs --clip-norm C: the noise is scaled to the clipped sum's sensitivity\n";
+            return false;
+        }
+        if (!std::isfinite(o->dp_z) || !(o->dp_z > 0)) {
+            std::cerr << "--dp-noise-multiplier " << o->dp_z << ": finite and > 0\n";
             return false;
         }
     }
@@ -538,6 +581,24 @@ public:
         }
         for (int k = 0; k < (int)order.size(); ++k) slots_.insert({order[k], k});
         expected_ = order;
+        if (o.dp_given) {  // before any bucket: stddev = Z C max_k w_k, the add/remove sensitivity of the clipped sum
+            float wmax = 0.0f;
+            for (int id : expected_) wmax = std::max(wmax, weight_of(id));
+            dp_stddev_ = (float)(o.dp_z * (double)o.clip_norm * (double)wmax);
+            if (!std::isfinite(dp_stddev_) || !(dp_stddev_ > 0)) {
+                std::cerr << "[aggregator] --dp-noise-multiplier: Z * C * max weight = " << dp_stddev_ << " is not a usable stddev\n";
+                std::exit(2);
+            }
+            uint64_t seed = o.dp_seed;
+            if (o.dp_seed_given) {
+                std::cerr << "[aggregator] DP NOISE: the seed is FIXED by --dp-seed: this run can be reproduced and its noise "
+                             "is not private\n";
+            } else {
+                std::random_device rd;  // the operating system's entropy; nothing is persisted
+                seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
+            }
+            FA_CHECK(fa_set_noise(ctx_, -1, dp_stddev_, seed));
+        }
         claimed_.assign(o.data_owners, 0);
     }
     ~Aggregator() { fa_destroy(ctx_); }
@@ -864,6 +925,23 @@ public:
         return os.str();
     }
 
+    // --dp-noise-multiplier: the round line's tail -- the multiplier, the stddev it gave (9 significant digits: it
+    // reads back to the same float) and the generator round this round's buckets drew from (the most, if they
+    // differ).
+    std::string dp_tail() {
+        unsigned long long used = 0;
+        for (auto& kv : buckets_) {
+            if (!kv.second.defined) continue;
+            uint64_t next = 0;
+            FA_CHECK(fa_noise_get_round(ctx_, kv.first, &next));
+            if (next > 0) used = std::max<unsigned long long>(used, next - 1);
+        }
+        char buf[160];
+        snprintf(buf, sizeof buf, ",\"dp_noise_multiplier\":%.17g,\"dp_stddev\":%.9g,\"dp_round\":%llu", o_.dp_z,
+                 (double)dp_stddev_, used);
+        return buf;
+    }
+
     // --krum-f: the round line's tail -- per bucket the ids of the owners left out and every owner's score in
     // slot order (17 significant digits: they read back to the same doubles), the owners' ids in that order once.
     std::string krum_tail() {
@@ -1071,6 +1149,7 @@ private:
     // --clip-norm: this round's clipped and excluded receipts and each bucket's squared distances (clip_tail)
     unsigned long long clip_clipped_ = 0, clip_excluded_ = 0;
     std::map<int, std::vector<double>> clip_q_;
+    float dp_stddev_ = 0.0f;  // --dp-noise-multiplier: the stddev given to the context
     // --krum-f: this round's scores and selection flags of each bucket, in slot order (krum_tail)
     struct KrumRound {
         std::vector<double> scores;
@@ -1268,7 +1347,8 @@ int main(int argc, char** argv) {
                      server_rule_name(o.server.rule), (double)o.server.lr, agg.save_server_state());
             server_tail = buf;
         }
-        const std::string clip_tail = o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : std::string();
+        const std::string clip_tail =
+            (o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : std::string()) + (o.dp_given ? agg.dp_tail() : std::string());
         printf("{\"round\":%d,\"phase1\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f},"
                "\"phase2\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,\"layers\":%d,"
