@@ -36,6 +36,82 @@ def distances(xs, kind):
     return Q
 
 
+# ------------------------------------------------------------------ lattice inputs: rule 1 in closed form
+#
+# Client k holds x_k[i] = scale * c_k * u_i with small integers u_i and scale a power of two, so
+#     Q_ab = scale^2 (c_a - c_b)^2 sum_i u_i^2
+# and every difference, square and partial sum in any order is an integer times a power of two that fits its
+# format: a kernel that follows rule 1 returns exactly these bits, whatever its summation order.
+
+LATTICE_CLIENTS = 128
+LATTICE_SEED = 0x1A77
+LATTICE_N = 4121  # the GPU sweep's size (tests/test_krum_geometry_gpu.py asserts what it needs of it)
+# the smallest subnormal of each type: x = scale c u is then subnormal in its type (bf16: up to |c u| = 127; the
+# larger ones fill the first normal binade) and every fl32 difference below 2^23 steps is an fp32 subnormal
+SUBNORMAL_SCALE = {"f32": 2.0 ** -149, "bf16": 2.0 ** -133, "f16": 2.0 ** -24}
+SMALLEST_NORMAL = {"f32": 2.0 ** -126, "bf16": 2.0 ** -126, "f16": 2.0 ** -14}
+
+
+_MIAN_CHOWLA = {}
+
+
+def mian_chowla(count):
+    """The first `count` terms of the Mian-Chowla sequence (greedy Sidon: all pairwise sums a + b, a <= b, differ,
+    hence all positive differences differ, hence all (c_a - c_b)^2 of distinct unordered pairs)."""
+    if count not in _MIAN_CHOWLA:
+        _MIAN_CHOWLA[count] = _mian_chowla(count)
+    return list(_MIAN_CHOWLA[count])
+
+
+def _mian_chowla(count):
+    seq, sums, x = [], set(), 0
+    while len(seq) < count:
+        x += 1
+        new = {x + y for y in seq} | {2 * x}
+        if sums.isdisjoint(new):
+            seq.append(x)
+            sums |= new
+    return seq
+
+
+def pow2_exponent(scale):
+    m, e = math.frexp(scale)
+    assert m == 0.5, "scale %r is not a power of two" % (scale,)
+    return e - 1
+
+
+def lattice(n, kind, scale=1.0):
+    """(c, u, xs): the coefficients of the LATTICE_CLIENTS clients (np.int64), the n integers u_i in {-2 .. 2}
+    (np.int64, seeded, never 0: an element that is dropped or taken twice changes every pair's sum) and the
+    buckets xs[k] = scale c_k u_i of `kind`.  f32: c is the Mian-Chowla sequence, so every matrix entry names its
+    pair; bf16 and f16: c_k = k, so |c_k u_i| <= 254 is exact in both."""
+    u = np.asarray([-2, -1, 1, 2], np.int64)[np.random.default_rng(LATTICE_SEED).integers(0, 4, n)]
+    c = np.asarray(mian_chowla(LATTICE_CLIENTS) if kind == "f32" else range(LATTICE_CLIENTS), np.int64)
+    e = pow2_exponent(scale)
+    xs = []
+    for k in range(LATTICE_CLIENTS):
+        v = np.ldexp((c[k] * u).astype(F64), e)  # exact in fp64
+        x = round_out(v.astype(F32), kind)
+        assert np.array_equal(widen(x, kind).astype(F64), v), "client %d of the lattice is not exact in %s" % (k, kind)
+        xs.append(x)
+    return c, u, xs
+
+
+def lattice_distances(c, u, scale=1.0, D=None):
+    """The closed form of rule 1 for the first D lattice clients over the elements u: exact integers (< 2^53,
+    asserted) times scale^2."""
+    c = [int(v) for v in np.asarray(c)[:D]]
+    su = sum(int(v) * int(v) for v in np.asarray(u))
+    D = len(c)
+    Q = np.zeros((D, D), F64)
+    for a in range(D):
+        for b in range(a + 1, D):
+            q = (c[a] - c[b]) ** 2 * su
+            assert q < 2 ** 53
+            Q[a, b] = Q[b, a] = math.ldexp(float(q), 2 * pow2_exponent(scale))
+    return Q
+
+
 def dist_bound(n, exact):
     """fa.h: whatever the order, |Q - exact| <= n * 2^-53 * exact."""
     return n * 2.0 ** -53 * exact

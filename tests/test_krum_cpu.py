@@ -113,6 +113,74 @@ def test_aggregate_is_the_chain_over_the_selected(O):
     assert K.aggregate(O, xs, "f32", w, np.zeros(4, bool)).view(np.uint32).tolist() == [0] * 67  # nobody: +0
 
 
+# ------------------------------------------------------------------ the lattice inputs and their closed form
+
+LATTICE_KINDS = ["f32", "bf16", "f16"]
+
+
+def test_mian_chowla_is_a_sidon_sequence():
+    c = K.mian_chowla(K.LATTICE_CLIENTS)
+    assert c[:10] == [1, 2, 4, 8, 13, 21, 31, 45, 66, 81] and len(c) == 128 and c == sorted(set(c))
+    sums = [c[a] + c[b] for a in range(128) for b in range(a, 128)]
+    assert len(set(sums)) == len(sums)  # the Sidon property
+    sq = [(c[a] - c[b]) ** 2 for a in range(128) for b in range(a + 1, 128)]
+    assert len(set(sq)) == len(sq) == 8128  # so every entry of the matrix names its pair
+
+
+@pytest.mark.parametrize("kind", LATTICE_KINDS)
+def test_lattice_magnitudes_fit_their_formats(kind):
+    n = K.LATTICE_N
+    c, u, xs = K.lattice(n, kind)
+    assert len(xs) == 128 and all(np.asarray(x).size == n for x in xs)
+    assert sorted(set(u.tolist())) == [-2, -1, 1, 2]  # never 0: every element counts in every pair
+    cu = int(np.abs(c).max()) * int(np.abs(u).max())
+    assert cu < (2 ** 24 if kind == "f32" else 255)  # max |c_k u_i|: exact in the type
+    span = int(c.max() - c.min()) * 2
+    assert span < 2 ** 23  # max |(c_a - c_b) u_i|: exact in fp32, also in steps of its smallest subnormal
+    assert span ** 2 * n < 2 ** 53  # any partial sum of any order is an exact integer
+    assert K.lattice_distances(c, u).max() < 2.0 ** 53
+    assert c.tolist() == (K.mian_chowla(128) if kind == "f32" else list(range(128)))
+    for k in (0, 1, 77, 127):
+        assert K.widen(xs[k], kind).astype(F64).tolist() == (c[k] * u).astype(F64).tolist()
+
+
+@pytest.mark.parametrize("kind", LATTICE_KINDS)
+def test_lattice_subnormal_inputs_are_subnormal(kind):
+    c, u, xs = K.lattice(K.LATTICE_N, kind, K.SUBNORMAL_SCALE[kind])
+    N = K.SMALLEST_NORMAL[kind]
+    for k in range(128):
+        w = np.abs(K.widen(xs[k], kind).astype(F64))
+        assert w.tolist() == np.ldexp(np.abs(c[k] * u).astype(F64), K.pow2_exponent(K.SUBNORMAL_SCALE[kind])).tolist()
+        if kind != "bf16" or k < 64:  # bf16: 2^-133 |c u| < 2^-126 needs |c u| < 128
+            assert (w < N).all() and (w > 0).all() == (c[k] != 0)
+        else:
+            assert (w < 2 * N).all() and (w[np.abs(u) == 1] < N).all()
+    # the fl32 differences: f32, all of them fp32 subnormals; bf16, those of clients at most 63 apart (16-bit
+    # inputs widen to fp32 normals and subnormals alike; f16's are fp32 normals, its inputs f16 subnormals)
+    if kind == "f32":
+        assert int(c.max() - c.min()) * 2 * K.SUBNORMAL_SCALE[kind] < 2.0 ** -126
+    if kind == "bf16":
+        assert 63 * 2 * K.SUBNORMAL_SCALE[kind] < 2.0 ** -126 <= 64 * 2 * K.SUBNORMAL_SCALE[kind]
+
+
+@pytest.mark.parametrize("kind", LATTICE_KINDS)
+@pytest.mark.parametrize("D,n", [(5, K.LATTICE_N), (33, K.LATTICE_N), (128, 259)])
+def test_lattice_closed_form_is_rule_1_bit_for_bit(kind, D, n):
+    for scale in (1.0, K.SUBNORMAL_SCALE[kind]):
+        c, u, xs = K.lattice(n, kind, scale)
+        Q = K.lattice_distances(c, u, scale, D)
+        assert Q.shape == (D, D) and (Q[np.triu_indices(D, 1)] > 0).all()
+        assert bits64(Q) == bits64(K.distances(xs[:D], kind)), (kind, D, scale)
+        if kind == "f32":
+            assert len(set(Q[np.triu_indices(D, 1)].tolist())) == D * (D - 1) // 2
+
+
+def test_lattice_closed_form_follows_a_prefix_of_u():
+    c, u, xs = K.lattice(67, "bf16")
+    for n in (1, 3, 8):
+        assert bits64(K.lattice_distances(c, u[:n], 1.0, 9)) == bits64(K.distances([x[:n] for x in xs[:9]], "bf16"))
+
+
 # ------------------------------------------------------------------ the library, no device
 
 HAND = [
