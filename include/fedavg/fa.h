@@ -142,6 +142,44 @@
  *              stream round trip more than a plain round), selects on the host and then enqueues the chain.  Added
  *              without a new FA_ABI_VERSION: fa_pairdist_device with n == 0 touches no device, writes D * D zeros
  *              and answers FA_OK -- that is how a caller probes for it.
+ *   Bulyan stage (fa_set_bulyan): iterated Krum, then a median-centred mean, on an FA_TRIMMED part (El Mhamdi,
+ *              Guerraoui, Rouault, "The Hidden Vulnerability of Distributed Learning in Byzantium", ICML 2018).  Krum
+ *              alone lets one coordinate of a selected owner be arbitrarily wrong; a trimmed mean alone ignores how
+ *              far an owner's whole bucket lies from the others; Bulyan first picks theta = D - 2f owners by running
+ *              Krum repeatedly and then, per element, averages the theta - 2f picked values closest to their median.
+ *              Parameter: f, the number of owners assumed Byzantine, 0 <= f and 4 f + 3 <= D <=
+ *              FA_TRIMMED_MAX_CLIENTS.  Weights are ignored, as for FA_TRIMMED; the part's trim is not used while the
+ *              stage is set; no state across rounds.  Per round:
+ *              1. Distances.  Exactly rule 1 of the Krum stage: the D x D matrix Q, bit-symmetric, +0 diagonal, the
+ *                 order of the fp64 sums free within n 2^-53 relative, no atomics; shards and pieces are added on the
+ *                 host in GPU order, then piece order.
+ *              2. Iterated selection (fa_bulyan_select, pure host arithmetic in fp64).  R = all D clients in ascending
+ *                 order, theta = D - 2f.  Until theta clients are picked: c = max(1, |R| - f - 2) (the paper leaves
+ *                 the count open once |R| < 2f + 3; this is the choice made here); for every k in R take Q_kj for j in
+ *                 R, j != k, replace NaN by +inf and sort ascending; S_k = the first min(c, |R| - 1) of them added in
+ *                 ascending order from +0, each add one rounded fp64 add (a lone remaining client scores +0); the pick
+ *                 is the smallest (S_k, k).  If its S is +inf the selection stops and fewer than theta are picked;
+ *                 otherwise it is appended to the pick order and removed from R.
+ *              3. Centred mean.  theta' = the number picked.  If theta' = 0 the aggregate is +0.  Otherwise
+ *                 keep = max(1, theta' - 2f) and every element is the centred mean of rule 4 over the picked clients'
+ *                 values (they are passed in ascending client order; the order does not matter to the result).
+ *              4. Centred mean of theta values keeping `keep` (1 <= keep <= theta), per element.  Widen to fp32 and
+ *                 sort ascending under the FA_TRIMMED total order (the same keys) into s_0 .. s_{theta-1}.
+ *                 c_lo = s_{(theta-1)/2}, c_hi = s_{theta/2} (integer division; for odd theta both are the median).
+ *                 j = 0; while j < theta - keep: d_hi = fl32(s_{j+keep} - c_hi), d_lo = fl32(c_lo - s_j); if
+ *                 d_hi < d_lo then j = j + 1, otherwise stop (an IEEE comparison, false when either side is NaN;
+ *                 subnormal differences are kept).  acc = +0, then acc = fl32(acc + s_u) for u = j .. j + keep - 1
+ *                 ascending; out = fl32(acc / (float)keep), correctly rounded; a 16-bit output is that rounded once,
+ *                 as for FA_TRIMMED.  keep == theta is FA_TRIMMED with trim 0 bit for bit.  Ties keep the lower
+ *                 window; a NaN above the window is never slid into; a -inf at the bottom is slid away whenever the
+ *                 centre is finite.  On finite data without ties the window holds exactly the `keep` values nearest
+ *                 the median.
+ *              5. Place in the round.  The value of rule 3 is the part's fp32 aggregate a, exactly where step 4 of
+ *                 FA_TRIMMED is: it feeds the noise stage and the server optimizer if present, otherwise it is rounded
+ *                 once to the out dtype.  A reducing call does the distance pass, one host wait, the selection and
+ *                 then the launches, as a Krum part does.
+ *              Added without a new FA_ABI_VERSION: fa_centered_device with n == 0 touches no device and answers
+ *              FA_OK -- that is how a caller probes for it.
  *   Noise stage (fa_set_noise, fa_noise_device, fa_noise_host): Gaussian noise on the round's aggregate, the other
  *              half of DP-FedAvg (McMahan et al., "Learning Differentially Private Recurrent Language Models"):
  *              a'_i = a_i + stddev z_i with z_i a standard normal, specified bit for bit.  Parameters: stddev
@@ -182,7 +220,8 @@
  *              4. Normals and output.  From one word pair z0 = fl(R cos), z1 = fl(R sin);
  *                 a'_i = fl(a_i + fl(stddev z_i)).  A NaN or inf in a propagates (NaN payloads unspecified).
  *              5. Place in the round.  a is the part's fp32 aggregate exactly as for the server optimizer (the
- *                 plain chain, the clipped or Krum subset chain, step 4 of FA_TRIMMED); a' takes its place: it
+ *                 plain chain, the clipped or Krum subset chain, step 4 of FA_TRIMMED, rule 3 of the Bulyan stage); a'
+ *                 takes its place: it
  *                 feeds the server-optimizer stage if there is one, otherwise it is rounded once to the out dtype.
  *                 The clip stage's new reference is the output as before: what the owners receive, noise included.
  *                 A clip bootstrap round (no reference, nothing clipped) still gets its noise; that it bounds
@@ -545,6 +584,37 @@ int fa_krum_weights(const float* w, const int* selected, int D, float* w_out);
  * stream), waits for it and returns the matrix. */
 int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, double* h_dist,
                        void* hip_stream);
+
+/* Bulyan stage: iterated Krum, then a median-centred mean, on an FA_TRIMMED part (the header comment, "Bulyan
+ * stage").  Gives a part the stage with f owners assumed Byzantine (part_id >= 0; calling again changes f), or sets
+ * the context default that FA_TRIMMED parts defined later take (part_id < 0; checked against D when such a part is
+ * defined, where a misfit makes fa_bucket_define fail).  f == -1 removes the stage: the part is a plain FA_TRIMMED
+ * part with its trim again.  FA_ERR_ARG, naming the cause: f < -1, an f that does not fit the part's D (4 f + 3 <=
+ * D), a part that is not FA_TRIMMED, an FA_SHARD_CLIENT_RS context.  The server optimizers and the noise stage
+ * compose, in either call order; the clip and Krum stages are FA_FEDAVG stages and never meet it.  Like the other
+ * stage parts a Bulyan part gets its own launches in fa_reduce_parts and fa_reduce_part marks the round reduced; like
+ * every FA_TRIMMED part it is never eager or kept host-side and needs every client submitted.  A reducing call waits
+ * on the host for the distance pass before it enqueues the centred mean: one stream round trip.  Range shards and
+ * range pieces work. */
+int fa_set_bulyan(fa_ctx* ctx, int part_id, int f);
+/* What the part's last reducing call did: dist = the D x D matrix Q (row-major); order[i] and pick_scores[i], i <
+ * *n_selected, = the i-th pick and the score S it was picked with (D entries each; the unused ones hold -1 and
+ * +inf); selected[k] = 0 / 1 (D entries).  Any pointer may be NULL.  FA_ERR_STATE on a part without the stage or
+ * never reduced with it. */
+int fa_bulyan_get_round(fa_ctx* ctx, int part_id, double* dist, int* order, double* pick_scores, int* selected,
+                        int* n_selected);
+/* Rule 2 of the stage, pure host arithmetic, usable without a device: the picks of the D x D row-major matrix dist
+ * under f, arrays as in fa_bulyan_get_round (any but dist may be NULL).  FA_ERR_ARG for a null dist and for D and f
+ * as in fa_set_bulyan.  A caller that wants Bulyan over a whole model sums the matrices of its parts, selects once and
+ * runs fa_centered_device over the picked owners' buckets with keep = max(1, *n_selected - 2 f). */
+int fa_bulyan_select(const double* dist, int D, int f, int* order, double* pick_scores, int* selected, int* n_selected);
+/* Rule 4 on raw device pointers: per element the mean of the `keep` values closest to the median of D client
+ * buckets resident on device `gpu`, into d_out; D in 1..FA_TRIMMED_MAX_CLIENTS, keep in 1..D.  ctx may be NULL (then
+ * `gpu` is the HIP device).  Every argument is checked before any device call: D, keep, the dtype pair, and for n >
+ * 0 null pointers and element alignment; with n == 0 and valid arguments it returns FA_OK without touching a device.
+ * Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
+int fa_centered_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, void* d_out,
+                       fa_dtype out, int keep, void* hip_stream);
 
 /* Noise stage: Gaussian noise on a part's fp32 aggregate (the header comment, "Noise stage").  Gives a part the
  * stage with standard deviation stddev > 0 and the seed (part_id >= 0; the part id is the stream; calling again

@@ -102,6 +102,10 @@ def lib():
         "fa_krum_select": (I, [P, I, I, I, P, P, ctypes.POINTER(I)]),
         "fa_krum_weights": (I, [P, P, I, P]),
         "fa_pairdist_device": (I, [P, I, P, I, S, I, P, P]),
+        "fa_set_bulyan": (I, [P, I, I]),
+        "fa_bulyan_get_round": (I, [P, I, P, P, P, P, ctypes.POINTER(I)]),
+        "fa_bulyan_select": (I, [P, I, I, P, P, P, ctypes.POINTER(I)]),
+        "fa_centered_device": (I, [P, I, P, I, S, I, P, I, I, P]),
         "fa_set_noise": (I, [P, I, F, U64]),
         "fa_get_noise": (I, [P, I, ctypes.POINTER(F), ctypes.POINTER(U64)]),
         "fa_noise_get_round": (I, [P, I, ctypes.POINTER(U64)]),
@@ -325,6 +329,31 @@ def krum_weights(weights, selected):
     out = np.empty(w.size, np.float32)
     check(lib().fa_krum_weights(w.ctypes.data, sel.ctypes.data, w.size, out.ctypes.data))
     return out
+
+
+def centered_device(clients, n, in_dtype, out, out_dtype=F32, keep=1, stream=None, gpu=0, ctx=None):
+    """fa_centered_device: per element the mean of the `keep` values closest to the median of D device-resident
+    client buckets -> out (fa.h "Bulyan stage", rule 4; enqueued, not synchronized).  With n == 0 no device is
+    touched: the feature probe."""
+    D = len(clients)
+    arr = (ctypes.c_void_p * max(1, D))(*[_addr(c) for c in clients])
+    check(lib().fa_centered_device(ctx.handle if ctx is not None else None, gpu, arr, D, n, in_dtype, _addr(out),
+                                   out_dtype, int(keep), _stream(stream)))
+
+
+def bulyan_select(dist, f):
+    """fa_bulyan_select (host arithmetic, rule 2): (order, pick_scores, selected bool[D]) of the (D, D) matrix
+    `dist` with f owners assumed Byzantine: the picks in pick order (np.intc) and the score each was picked with
+    (np.float64), both as long as the number picked."""
+    dist = np.ascontiguousarray(dist, np.float64)
+    D = dist.shape[0] if dist.ndim == 2 else 0
+    if dist.ndim != 2 or dist.shape[1] != D:
+        raise ValueError("need a square matrix")
+    order, ps, sel = np.empty(D, np.intc), np.empty(D, np.float64), np.empty(D, np.intc)
+    ns = ctypes.c_int()
+    check(lib().fa_bulyan_select(dist.ctypes.data, D, int(f), order.ctypes.data, ps.ctypes.data, sel.ctypes.data,
+                                 ctypes.byref(ns)))
+    return order[:ns.value].copy(), ps[:ns.value].copy(), sel.astype(bool)
 
 
 def noise_device(avg, n, out, out_dtype=F32, stddev=1.0, seed=0, stream_id=0, round=0, idx0=0, stream=None, gpu=0,
@@ -636,6 +665,22 @@ class Aggregator:
         check(lib().fa_krum_get_round(self.handle, part_id, q.ctypes.data, s.ctypes.data, sel.ctypes.data,
                                       ctypes.byref(ns)))
         return q, s, sel.astype(bool)
+
+    def set_bulyan(self, f, part_id=-1):
+        """fa_set_bulyan: the Bulyan stage (iterated Krum, then a median-centred mean) on a TRIMMED part with f
+        owners assumed Byzantine (part_id < 0: the default of TRIMMED parts defined later); f=None removes it."""
+        check(lib().fa_set_bulyan(self.handle, part_id, -1 if f is None else int(f)))
+
+    def bulyan_round(self, part_id):
+        """fa_bulyan_get_round: (dist float64[D, D], order, pick_scores, selected bool[D]) of the part's last
+        reducing call; order and pick_scores are as long as the number picked, in pick order."""
+        D = self.parts[part_id][3]
+        q, order, ps, sel = (np.empty((D, D), np.float64), np.empty(D, np.intc), np.empty(D, np.float64),
+                             np.empty(D, np.intc))
+        ns = ctypes.c_int()
+        check(lib().fa_bulyan_get_round(self.handle, part_id, q.ctypes.data, order.ctypes.data, ps.ctypes.data,
+                                        sel.ctypes.data, ctypes.byref(ns)))
+        return q, order[:ns.value].copy(), ps[:ns.value].copy(), sel.astype(bool)
 
     def set_noise(self, stddev, seed, part_id=-1):
         """fa_set_noise: Gaussian noise of standard deviation `stddev` on the part's fp32 aggregate, drawn from

@@ -358,6 +358,13 @@ struct Part {
     std::vector<double> krum_q, krum_s;
     std::vector<int> krum_sel;
     int krum_n = 0;
+    // Bulyan stage of an FA_TRIMMED part (fa.h "Bulyan stage"; bulyan_f < 0: none): f, and what the last reducing
+    // call found -- the D x D matrix, the picks in pick order with their scores, the flags.  Host state only.
+    int bulyan_f = -1;
+    bool bulyan_reported = false;
+    std::vector<double> bulyan_q, bulyan_s;
+    std::vector<int> bulyan_order, bulyan_sel;
+    int bulyan_n = 0;
     // Noise stage (fa.h "Noise stage"; noise == 0: none): stddev, the seed and the round the next reducing call
     // uses (2^32: that call is refused).  Host state only, besides oavg above.
     float noise = 0.0f;
@@ -365,10 +372,10 @@ struct Part {
     uint64_t noise_round = 0;
 };
 
-// A part whose reducing calls are rounds of their own (a server-optimizer, clip, Krum or noise stage): never
-// batched, eager or host-read, every client submitted before each.
+// A part whose reducing calls are rounds of their own (a server-optimizer, clip, Krum, Bulyan or noise stage):
+// never batched, eager or host-read, every client submitted before each.
 inline bool staged(const Part& p) {
-    return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0 || p.noise > 0.0f;
+    return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0 || p.bulyan_f >= 0 || p.noise > 0.0f;
 }
 // A part that gets its first stage: what this round chained or kept host-side so far goes back to the plain path.
 inline void restart_round_plain(Part& p) {
@@ -386,6 +393,7 @@ struct fa_ctx {
     fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};  // default stage of FedAvg / trimmed parts defined later
     float clip = 0.0f;          // default clip bound of FedAvg parts defined later (0: none)
     int krum_f = 0, krum_m = 0; // default Krum stage of FedAvg parts defined later (m == 0: none, -1: D - f)
+    int bulyan_f = -1;          // default Bulyan stage of trimmed parts defined later (< 0: none)
     float noise = 0.0f;         // default noise stage of FedAvg / trimmed parts defined later (0: none)
     uint64_t noise_seed = 0;
     CtxTuning tuning;
@@ -732,6 +740,90 @@ int pairdist_on(const fa::Tuning& tu, const void* const* clients, int D, size_t 
     for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
     const fa::ClientTable t = client_table(clients, nullptr, 0, D);
     FA_HIP(fa::launch_pairdist(t, D, in, sp, d_part, d_dist, tu, s));
+    return FA_OK;
+}
+
+// ------------------------------------------------------------------ Bulyan stage
+
+// The refusals of f for D clients (fa.h "Bulyan stage"), naming the cause.
+int check_bulyan(int D, int f) {
+    if (D > FA_TRIMMED_MAX_CLIENTS)
+        return fail(FA_ERR_ARG, "bulyan: D = %d clients (at most %d)", D, FA_TRIMMED_MAX_CLIENTS);
+    if (f < 0 || 4 * f + 3 > D)
+        return fail(FA_ERR_ARG, "bulyan: f = %d does not fit D = %d clients (0 <= f and 4 f + 3 <= D)", f, D);
+    return FA_OK;
+}
+
+// Rule 2 of fa.h "Bulyan stage" (D, f checked): order, pick_scores and selected hold D entries each, any may be
+// null.  Every row is sorted once with its column indices; a round's score is the row's first entries that are
+// still in R, which is the sorted row of rule 2 (equal values add to the same sum in either order).  volatile
+// keeps each step one rounded fp64 add.
+void bulyan_select(const double* dist, int D, int f, int* order, double* pick_scores, int* selected, int* n_selected) {
+    const double inf = HUGE_VAL;
+    const size_t n = (size_t)D;
+    std::vector<std::vector<std::pair<double, int>>> rows(n);
+    for (int k = 0; k < D; ++k) {
+        auto& row = rows[(size_t)k];
+        row.reserve(n - 1);
+        for (int j = 0; j < D; ++j) {
+            if (j == k) continue;
+            const double q = dist[(size_t)k * n + (size_t)j];
+            row.emplace_back(q != q ? inf : q, j);
+        }
+        std::stable_sort(row.begin(), row.end(),
+                         [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
+    }
+    std::vector<char> in_r(n, 1);
+    for (int k = 0; k < D; ++k) {
+        if (order) order[k] = -1;
+        if (pick_scores) pick_scores[k] = inf;
+        if (selected) selected[k] = 0;
+    }
+    const int theta = D - 2 * f;
+    int picked = 0;
+    for (int left = D; picked < theta; --left) {
+        const int take = std::min(std::max(1, left - f - 2), left - 1);
+        int best = -1;
+        double best_s = inf;
+        for (int k = 0; k < D; ++k) {
+            if (!in_r[(size_t)k]) continue;
+            volatile double acc = 0.0;
+            int got = 0;
+            for (const auto& e : rows[(size_t)k]) {
+                if (got == take) break;
+                if (!in_r[(size_t)e.second]) continue;
+                acc = acc + e.first;
+                ++got;
+            }
+            const double s = acc;
+            const double key = s != s ? inf : s;  // a NaN score (only from a matrix holding -inf) counts as +inf
+            if (best < 0 || key < best_s) {
+                best = k;
+                best_s = key;
+            }
+        }
+        if (!(best_s < inf)) break;  // +inf is never picked, nor anything after it
+        if (order) order[picked] = best;
+        if (pick_scores) pick_scores[picked] = best_s;
+        if (selected) selected[best] = 1;
+        in_r[(size_t)best] = 0;
+        ++picked;
+    }
+    if (n_selected) *n_selected = picked;
+}
+
+// Enqueues the centred mean (rule 4) on the current device: nc clients (n > 0 elements of `in`) -> dst.
+int centered_on(const fa::Tuning& tu, const void* const* clients, int nc, size_t n, fa_dtype in, void* dst, fa_dtype out,
+                int keep, hipStream_t s) {
+    const size_t si = dsize(in), so = dsize(out);
+    if (int rc = check_clients(clients, nc, si, "client")) return rc;
+    if (!dst) return fail(FA_ERR_ARG, "output pointer is null");
+    if (!aligned(dst, so)) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", so);
+    fa::Split sp = fa::split_at(clients[0], si, n);
+    for (int k = 0; k < nc; ++k) sp.require_input(clients[k]);
+    sp.require(dst, so);
+    const fa::ClientTable t = client_table(clients, nullptr, 0, nc);
+    FA_HIP(fa::launch_centered(t, nc, in, out, keep, dst, sp, tu, s));
     return FA_OK;
 }
 
@@ -1420,6 +1512,44 @@ int krum_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* p
     return FA_OK;
 }
 
+// Rules 1-2 of the Bulyan stage for part p (range layout): the distance pass (measure_pass), then the iterated
+// selection.  The plan's clients are the picks in ascending client order; its weights stay empty (the rule has
+// none).  Leaves the round's report in the part.
+int bulyan_plan(fa_ctx* ctx, Part& p, hipStream_t s, SubsetPlan* plan) {
+    const size_t D = (size_t)p.D;
+    p.bulyan_q.assign(D * D, 0.0);
+    if (int rc = measure_pass(ctx, p, s, D * D, krum_parts(p.D), "bulyan: distance-pass", p.bulyan_q.data(),
+                              [&](int, int, const void* const* clients, size_t cnt, double* d_part, double* d_out,
+                                  hipStream_t st) {
+                                  return pairdist_on(ctx->tuning.tu, clients, p.D, cnt, p.in, d_part, d_out, st);
+                              }))
+        return rc;
+    p.bulyan_s.assign(D, 0.0);
+    p.bulyan_order.assign(D, -1);
+    p.bulyan_sel.assign(D, 0);
+    bulyan_select(p.bulyan_q.data(), p.D, p.bulyan_f, p.bulyan_order.data(), p.bulyan_s.data(), p.bulyan_sel.data(),
+                  &p.bulyan_n);
+    for (size_t k = 0; k < D; ++k)
+        if (p.bulyan_sel[k]) plan->inc.push_back((int)k);
+    p.bulyan_reported = true;
+    return FA_OK;
+}
+
+// Rule 3 for piece j of GPU g (the current device), into dst (dtype odt): the centred mean over the plan's
+// clients keeping max(1, theta' - 2f) of them, +0 when nobody was picked.
+int bulyan_piece(fa_ctx* ctx, Part& p, int g, int j, const SubsetPlan& plan, void* dst, fa_dtype odt, hipStream_t st) {
+    const size_t cnt = piece_cnt(p, g, j);
+    if (cnt == 0) return FA_OK;
+    if (plan.inc.empty()) {
+        FA_HIP(hipMemsetAsync(dst, 0, cnt * dsize(odt), st));
+        return FA_OK;
+    }
+    std::vector<const void*> ptrs;
+    for (int k : plan.inc) ptrs.push_back(piece_ptr(p, g, k, j));
+    const int nc = (int)ptrs.size();
+    return centered_on(ctx->tuning.tu, ptrs.data(), nc, cnt, p.in, dst, odt, std::max(1, nc - 2 * p.bulyan_f), st);
+}
+
 // Enqueue the full reduction of part p on every GPU (the ctx's streams, or `s` for a one-GPU ctx):
 // range -> each GPU's shard; rs -> the clients' fp32 partials, piece by piece, each piece's RCCL
 // reduce-scatter (ring over xGMI) overlapping the reduction of the next.
@@ -1451,6 +1581,10 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
         const bool krum = p.krum_m != 0;  // never with a clip stage
         if (krum)
             if (int rc = krum_plan(ctx, p, w, s, &plan)) return rc;
+        // a Bulyan stage (an FA_TRIMMED part: never with the two above): the same pass and wait, then the picks
+        const bool bulyan = p.bulyan_f >= 0;
+        if (bulyan)
+            if (int rc = bulyan_plan(ctx, p, s, &plan)) return rc;
         std::vector<const void*> ptrs;
         for (int g = 0; g < G; ++g) {
             GpuRes& r = ctx->gpu[(size_t)g];
@@ -1475,6 +1609,8 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
                     rc = reduce_on(ctx, g, tu, &last, w, 1, cnt, p.in, dst, p.out, FA_LITERAL, p.divisor, nullptr, st);
                 } else if (clipping || krum)
                     rc = subset_chain(ctx, p, g, j, plan, adst, adt, st);
+                else if (bulyan)
+                    rc = bulyan_piece(ctx, p, g, j, plan, adst, adt, st);
                 else
                     rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                                    mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
@@ -2402,6 +2538,9 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     int krum_m = 0;
     if (krummed)
         if (int rc = check_krum(n_clients, ctx->krum_f, ctx->krum_m, &krum_m)) return rc;
+    const bool bulyaned = ctx->bulyan_f >= 0 && mode == FA_TRIMMED;  // takes the context's Bulyan stage
+    if (bulyaned)
+        if (int rc = check_bulyan(n_clients, ctx->bulyan_f)) return rc;
     auto it = ctx->parts.find(part_id);
     if (it != ctx->parts.end()) {
         free_part(ctx, it->second);
@@ -2524,6 +2663,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
         p.krum_f = ctx->krum_f;
         p.krum_m = krum_m;
     }
+    if (bulyaned) p.bulyan_f = ctx->bulyan_f;
     if (noisy) {
         if (int rc = set_part_noise(ctx, p, ctx->noise, ctx->noise_seed)) {
             const std::string why = g_err;
@@ -2824,6 +2964,87 @@ int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D
                           [&](const DeviceCall& c, double* d_part, double* d_out) {
                               return pairdist_on(c.tu, d_clients, D, n, in, d_part, d_out, c.s);
                           });
+}
+
+int fa_set_bulyan(fa_ctx* ctx, int part_id, int f) {
+    g_err.clear();
+    if (f < -1) return fail(FA_ERR_ARG, "bulyan: f = %d (f >= 0; -1 removes the stage)", f);
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (f >= 0 && (ctx->flags & FA_SHARD_CLIENT_RS))
+        return fail(FA_ERR_ARG, "bulyan: not on an FA_SHARD_CLIENT_RS context (the rule needs every client on one GPU; "
+                                "use FA_SHARD_RANGE)");
+    if (part_id < 0) {
+        ctx->bulyan_f = f;
+        return FA_OK;
+    }
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (f < 0) {  // the stage and its report go
+        if (p->bulyan_f >= 0) p->ready = false;
+        p->bulyan_f = -1;
+        p->bulyan_reported = false;
+        p->bulyan_q.clear();
+        p->bulyan_s.clear();
+        p->bulyan_order.clear();
+        p->bulyan_sel.clear();
+        return FA_OK;
+    }
+    if (p->mode != FA_TRIMMED)
+        return fail(FA_ERR_ARG, "bulyan: part %d is an %s part (the stage replaces the window of an FA_TRIMMED part)", part_id,
+                    p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_FEDAVG");
+    if ((rc = check_bulyan(p->D, f))) return rc;
+    if (p->bulyan_f < 0) p->bulyan_reported = false;
+    p->bulyan_f = f;
+    p->ready = false;
+    return FA_OK;
+}
+
+int fa_bulyan_get_round(fa_ctx* ctx, int part_id, double* dist, int* order, double* pick_scores, int* selected,
+                        int* n_selected) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (p->bulyan_f < 0) return fail(FA_ERR_STATE, "part %d has no Bulyan stage", part_id);
+    if (!p->bulyan_reported) return fail(FA_ERR_STATE, "part %d: no round reduced with the Bulyan stage yet", part_id);
+    const size_t D = (size_t)p->D;
+    if (dist) std::copy(p->bulyan_q.begin(), p->bulyan_q.end(), dist);
+    for (size_t k = 0; k < D; ++k) {
+        if (order) order[k] = p->bulyan_order[k];
+        if (pick_scores) pick_scores[k] = p->bulyan_s[k];
+        if (selected) selected[k] = p->bulyan_sel[k];
+    }
+    if (n_selected) *n_selected = p->bulyan_n;
+    return FA_OK;
+}
+
+int fa_bulyan_select(const double* dist, int D, int f, int* order, double* pick_scores, int* selected, int* n_selected) {
+    g_err.clear();
+    if (!dist) return fail(FA_ERR_ARG, "bulyan: dist is null");
+    if (D < 1) return fail(FA_ERR_ARG, "bulyan: D must be >= 1");
+    if (int rc = check_bulyan(D, f)) return rc;
+    bulyan_select(dist, D, f, order, pick_scores, selected, n_selected);
+    return FA_OK;
+}
+
+int fa_centered_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, void* d_out,
+                       fa_dtype out, int keep, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (D < 1 || D > FA_TRIMMED_MAX_CLIENTS)
+        return fail(FA_ERR_ARG, "D = %d: a centred mean takes 1..%d clients", D, FA_TRIMMED_MAX_CLIENTS);
+    if (keep < 1 || keep > D) return fail(FA_ERR_ARG, "keep %d does not fit D = %d clients (1 <= keep <= D)", keep, D);
+    if (!dvalid(in) || !dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
+    FA_PAIR(in, out);
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) return FA_OK;
+    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
+    if (!d_out) return fail(FA_ERR_ARG, "output pointer is null");
+    if (!aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    return centered_on(c.tu, d_clients, D, n, in, d_out, out, keep, c.s);
 }
 
 int fa_set_noise(fa_ctx* ctx, int part_id, float stddev, uint64_t seed) {

@@ -95,6 +95,11 @@ hipError_t launch_literal(const void* x, fa_dtype in, void* dst, fa_dtype out, f
 // Weights are not read.  fa_trimmed.hip.
 hipError_t launch_trimmed(const ClientTable& t, int nc, fa_dtype in, fa_dtype out, int trim, void* dst,
                           const Split& sp, const Tuning& tu, hipStream_t s);
+// The Bulyan stage's centred mean (fa.h "Bulyan stage", rule 4), fa_centered.hip: per element the mean of the
+// `keep` values (1 <= keep <= nc) closest to the median of the nc clients' values, nc <= FA_TRIMMED_MAX_CLIENTS.
+// Arguments, dtype pairs, forms and stores as launch_trimmed.
+hipError_t launch_centered(const ClientTable& t, int nc, fa_dtype in, fa_dtype out, int keep, void* dst,
+                           const Split& sp, const Tuning& tu, hipStream_t s);
 // The server-optimizer stage (fa.h "Server optimizer"), fa_server_opt.hip.  One step of `rule` (an fa_opt_rule
 // other than FA_OPT_NONE, or kOptBoot: x' = avg, m' = v' = +0, v nullable) over n elements: reads avg and the
 // fp32 state x, m, v (v null and untouched for FA_OPT_MOMENTUM), writes the state and, unless out is null, x'

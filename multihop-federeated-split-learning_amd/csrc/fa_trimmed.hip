@@ -29,48 +29,11 @@
 
 #include "fa_device.h"
 #include "fa_internal.h"
+#include "fa_sortnet.h"
 
 namespace fa {
 
 namespace {
-
-// k(x) of fa.h: NaN -> 0xFFFFFFFF, sign set -> ~bits, else bits | 0x80000000.
-__device__ __forceinline__ uint32_t trim_key(float x) {
-    const uint32_t b = __float_as_uint(x);
-    const uint32_t k = b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
-    return (b & 0x7fffffffu) > 0x7f800000u ? 0xffffffffu : k;
-}
-// Its inverse; 0xFFFFFFFF decodes to the quiet NaN 0x7FFFFFFF.
-__device__ __forceinline__ float trim_value(uint32_t k) {
-    return __uint_as_float(k ^ (~(uint32_t)((int32_t)k >> 31) | 0x80000000u));
-}
-
-__device__ __forceinline__ void cmp_exchange(uint32_t& lo, uint32_t& hi) {
-    const uint32_t a = lo < hi ? lo : hi;
-    hi = lo < hi ? hi : lo;
-    lo = a;
-}
-
-// Bitonic sorting network in its all-ascending form: the merge of width w first compares i with its mirror
-// i ^ (w - 1), then halves (i with i ^ j).  P log2(P) (log2(P) + 1) / 4 compare-exchanges: 672 at P = 64.
-template <int P>
-__device__ __forceinline__ void sort_keys(uint32_t (&k)[P]) {
-    // loops over the exponents (w = 2^lw, j = 2^lj): linear trip counts, so every one of them unrolls
-#pragma unroll
-    for (int lw = 1; (1 << lw) <= P; ++lw) {
-        const int w = 1 << lw;
-#pragma unroll
-        for (int i = 0; i < P; ++i)
-            if ((i ^ (w - 1)) > i) cmp_exchange(k[i], k[i ^ (w - 1)]);
-#pragma unroll
-        for (int lj = lw - 2; lj >= 0; --lj) {
-            const int j = 1 << lj;
-#pragma unroll
-            for (int i = 0; i < P; ++i)
-                if ((i ^ j) > i) cmp_exchange(k[i], k[i ^ j]);
-        }
-    }
-}
 
 // fl(sum of the kept positions, ascending, from +0) / div.
 template <int P>
@@ -81,10 +44,6 @@ __device__ __forceinline__ float window_mean(const uint32_t (&k)[P], int lo, int
         if (u >= lo && u < hi) acc = acc + trim_value(k[u]);
     return acc / div;
 }
-
-// Clients per launch are P/2 < nc <= P (nc = 1 takes P = 2), so the first half of the loads needs no guard.
-template <int P>
-__device__ __forceinline__ bool client_live(int u, int nc) { return u < (P + 1) / 2 || u < nc; }
 
 // Vector form: lane-vector v covers elements head + v*V .. + V-1 of every bucket (16-byte aligned there).
 template <typename IN, typename OUT, int P, int SP>
@@ -146,7 +105,6 @@ __global__ __launch_bounds__(256) void trimmed_elem_kernel(const ClientTable t, 
 // no barrier).  The merge takes the lower head (ties: either, equal keys are interchangeable), and a head
 // past its half's end reads as the pad 0xFFFFFFFF: it is taken only when the other head is a pad or NaN key
 // too, and then every key left decodes to the same NaN.
-constexpr int kWideBlock = 64;
 template <typename IN, typename OUT>
 __global__ __launch_bounds__(kWideBlock) void trimmed_wide_kernel(const ClientTable t, int nc, int trim, float div,
                                                                   void* out, int64_t n) {
@@ -185,13 +143,6 @@ __global__ __launch_bounds__(kWideBlock) void trimmed_wide_kernel(const ClientTa
         }
         Out<OUT>::scalar(out, i, acc / div);
     }
-}
-
-constexpr int64_t kElemMaxBlocks = 1 << 16;  // grid-stride beyond it
-int64_t blocks_for(int64_t work, const Tuning& tu, int64_t cap) {
-    int64_t g = (work + tu.block - 1) / tu.block;
-    if (tu.max_blocks > 0) cap = std::min<int64_t>(cap, tu.max_blocks);
-    return std::max<int64_t>(1, std::min(g, cap));
 }
 
 template <typename IN, typename OUT, int P>

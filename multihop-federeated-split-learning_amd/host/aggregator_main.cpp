@@ -32,6 +32,8 @@
 // norm of C before the FedAvg chain (fa.h "Clip stage"); --clip-state FILE carries that model across restarts.
 // --krum-f F [--krum-m M] averages, per bucket, only the M owners (default D - F) whose receipts lie closest to
 // the others' (Krum / Multi-Krum, fa.h "Krum stage"); the stage keeps no state across rounds.
+// --mode bulyan --bulyan-f F picks, per bucket, D - 2F owners by iterated Krum and averages per element the picked
+// values closest to their median (fa.h "Bulyan stage"); the stage keeps no state across rounds.
 // --dp-noise-multiplier Z (with --clip-norm C) adds Gaussian noise of stddev Z C max_k w_k to every bucket's clipped
 // aggregate (fa.h "Noise stage"): DP-FedAvg; the seed is fresh entropy at every start unless --dp-seed fixes it.
 #include <algorithm>
@@ -68,6 +70,10 @@ struct Options {
     // median is its largest trim, (D-1)/2
     int trim = FA_TRIM_MEDIAN;
     bool trim_given = false, median = false;
+    // --mode bulyan --bulyan-f F: FA_TRIMMED buckets with the Bulyan stage (fa_set_bulyan on the context, before
+    // any bucket is defined): iterated Krum, then per element the mean of the values closest to the median
+    int bulyan_f = 0;
+    bool bulyan = false, bulyan_f_given = false;
     bool discover = false, pinned = true;
     bool rs = false;     // --layout rs: clients dealt to the GPUs, RCCL reduce-scatter of fp32 partials
     bool eager = false;  // --eager: accumulate on arrival (the chain advances with the in-order receipts)
@@ -243,8 +249,8 @@ bool write_clip_state(const std::string& path, const ClipState& st) {
 }
 
 void usage() {
-    std::cerr << "usage: fa_aggregator -i ID -d DATA_OWNERS -c COMPUTE_NODES [--mode fedavg|literal|trimmed|median]\n"
-                 "       [--trim T] [--gpus G]\n"
+    std::cerr << "usage: fa_aggregator -i ID -d DATA_OWNERS -c COMPUTE_NODES [--mode fedavg|literal|trimmed|median|bulyan]\n"
+                 "       [--trim T] [--bulyan-f F] [--gpus G]\n"
                  "       [--rounds R] [--port-base P] [--discover] [--link-mbps M] [--samples id:n,...]\n"
                  "       [--divisor K] [--last-layers L] [--no-pinned] [--layout range|rs] [--rs-chunks C]\n"
                  "       [--eager] [--stall-report S] [--receipt-timeout S] [--rx-concurrency K]\n"
@@ -258,6 +264,10 @@ void usage() {
                  "rest averaged (2T < DATA_OWNERS <= 128; without --trim, and with --mode median, the median), so up\n"
                  "to T owners that send NaN, inf or huge values change no reply; --samples is ignored; not with\n"
                  "--layout rs.\n"
+                 "--mode bulyan --bulyan-f F: per bucket DATA_OWNERS - 2F owners are picked by running Krum repeatedly\n"
+                 "over the owners' pairwise distances, then per element the picked values closest to their median are\n"
+                 "averaged (all but 2F of them): F is the number of owners assumed Byzantine, 0 <= F, 4F + 3 <=\n"
+                 "DATA_OWNERS <= 128; --samples is ignored; not with --trim, --clip-norm, --krum-f or --layout rs.\n"
                  "--server-opt: a server optimizer (FedAvgM, FedAdagrad, FedAdam, FedYogi) steps the global model with\n"
                  "the round's aggregate; the model and its moments stay on the GPU in fp32; L finite and >= 0, B in\n"
                  "[0, 1) (defaults 0.9 and 0.99), T finite and > 0 (default 1e-3); --server-state FILE is read at startup\n"
@@ -327,6 +337,7 @@ bool parse_args(int argc, char** argv, Options* o) {
             else if (m == "fedavg") o->mode = FA_FEDAVG;
             else if (m == "trimmed") o->mode = FA_TRIMMED;
             else if (m == "median") o->mode = FA_TRIMMED, o->median = true;
+            else if (m == "bulyan") o->mode = FA_TRIMMED, o->bulyan = true;
             else return false;
         } else if (a == "--server-opt") {
             std::string r = val("--server-opt");
@@ -358,6 +369,9 @@ bool parse_args(int argc, char** argv, Options* o) {
             o->clip_given = true;
         } else if (a == "--clip-state") {
             o->clip_state = val("--clip-state");
+        } else if (a == "--bulyan-f") {
+            o->bulyan_f = std::atoi(val("--bulyan-f"));
+            o->bulyan_f_given = true;
         } else if (a == "--krum-f") {
             o->krum_f = std::atoi(val("--krum-f"));
             o->krum_given = true;
@@ -388,9 +402,29 @@ bool parse_args(int argc, char** argv, Options* o) {
             return false;
         }
     }
-    if (o->trim_given && (o->mode != FA_TRIMMED || o->median)) {
+    if (o->trim_given && (o->mode != FA_TRIMMED || o->median || o->bulyan)) {
         std::cerr << "--trim goes with --mode trimmed\n";
         return false;
+    }
+    if (o->bulyan != o->bulyan_f_given) {
+        std::cerr << "--mode bulyan and --bulyan-f F go together\n";
+        return false;
+    }
+    if (o->bulyan) {
+        if (o->rs) {
+            std::cerr << "--mode bulyan needs every owner's bucket on one GPU: not with --layout rs\n";
+            return false;
+        }
+        if (o->clip_given || o->krum_given) {
+            std::cerr << "--mode bulyan selects and averages by itself: not with "
+                      << (o->clip_given ? "--clip-norm" : "--krum-f") << "\n";
+            return false;
+        }
+        if (o->bulyan_f < 0 || 4 * o->bulyan_f + 3 > o->data_owners || o->data_owners > FA_TRIMMED_MAX_CLIENTS) {
+            std::cerr << "--bulyan-f " << o->bulyan_f << ": 0 <= F and 4F + 3 <= DATA_OWNERS <= " << FA_TRIMMED_MAX_CLIENTS
+                      << ", got " << o->data_owners << " data owners\n";
+            return false;
+        }
     }
     if (o->mode == FA_TRIMMED) {
         if (o->rs) {
@@ -566,6 +600,7 @@ public:
         }
         FA_CHECK(fa_set_literal_divisor(ctx_, -1, o.divisor));
         if (o.mode == FA_TRIMMED) FA_CHECK(fa_set_trim(ctx_, -1, o.trim));
+        if (o.bulyan) FA_CHECK(fa_set_bulyan(ctx_, -1, o.bulyan_f));  // before any bucket
         if (o.server.rule != FA_OPT_NONE) FA_CHECK(fa_set_server_opt(ctx_, -1, &o.server));  // before any bucket
         if (o.clip_given) FA_CHECK(fa_set_clip(ctx_, -1, o.clip_norm));
         if (o.krum_given) FA_CHECK(fa_set_krum(ctx_, -1, o.krum_f, o.krum_m));
@@ -846,6 +881,15 @@ public:
                 std::cerr << "[aggregator] KRUM: part " << mp << ": NO OWNER SELECTED (every score is infinite): the "
                           << "reply of this bucket is all zeros\n";
         }
+        if (o_.bulyan) {  // whom the Bulyan stage picked for this bucket, for the round line
+            std::vector<int>& sel = bulyan_[mp];
+            sel.assign((size_t)o_.data_owners, 0);
+            int kept = 0;
+            FA_CHECK(fa_bulyan_get_round(ctx_, mp, nullptr, nullptr, nullptr, sel.data(), &kept));
+            if (kept == 0)
+                std::cerr << "[aggregator] BULYAN: part " << mp << ": NO OWNER PICKED (every score is infinite): the "
+                          << "reply of this bucket is all zeros\n";
+        }
         b.held.clear();
         b.arrived.clear();
         b.bytes_in = 0;
@@ -940,6 +984,30 @@ public:
         snprintf(buf, sizeof buf, ",\"dp_noise_multiplier\":%.17g,\"dp_stddev\":%.9g,\"dp_round\":%llu", o_.dp_z,
                  (double)dp_stddev_, used);
         return buf;
+    }
+
+    // --mode bulyan: the round line's tail -- per bucket the ids of the owners left out, the owners' ids in slot
+    // order once.
+    std::string bulyan_tail() {
+        std::ostringstream os;
+        os << ",\"bulyan_owners\":[";
+        for (size_t k = 0; k < expected_.size(); ++k) os << (k ? "," : "") << expected_[k];
+        os << "],\"bulyan_left_out\":{";
+        bool first = true;
+        for (auto& kv : bulyan_) {
+            os << (first ? "" : ",") << "\"" << kv.first << "\":[";
+            first = false;
+            bool lead = true;
+            for (size_t k = 0; k < kv.second.size(); ++k) {
+                if (kv.second[k]) continue;
+                os << (lead ? "" : ",") << expected_[k];
+                lead = false;
+            }
+            os << "]";
+        }
+        os << "}";
+        bulyan_.clear();
+        return os.str();
     }
 
     // --krum-f: the round line's tail -- per bucket the ids of the owners left out and every owner's score in
@@ -1156,6 +1224,7 @@ private:
         std::vector<int> selected;
     };
     std::map<int, KrumRound> krum_;
+    std::map<int, std::vector<int>> bulyan_;  // --mode bulyan: this round's pick flags of each bucket, in slot order
     std::map<int, int> slots_;  // client id -> slot
     std::vector<char> claimed_;  // slot -> an arrived client holds it
     std::vector<int> expected_;  // the data owners' ids in slot order
@@ -1271,7 +1340,9 @@ int main(int argc, char** argv) {
 
     // the round line names the rule only where it is not a mean (lines of the other modes stay as they were)
     const std::string mode_tail =
-        o.mode == FA_TRIMMED ? ",\"mode\":\"trimmed\",\"trim\":" + std::to_string(o.trim) : std::string();
+        o.bulyan             ? ",\"mode\":\"bulyan\",\"bulyan_f\":" + std::to_string(o.bulyan_f)
+        : o.mode == FA_TRIMMED ? ",\"mode\":\"trimmed\",\"trim\":" + std::to_string(o.trim)
+                             : std::string();
     for (int round = 0; o.rounds < 0 || round < o.rounds; ++round) {
         // phase 1: model part 1 from every data owner (aggregator.cpp:59-93)
         // Receipt accounting (the reference counts raw receipts, aggregator.cpp:59-92 / :112-149): a phase
@@ -1348,7 +1419,7 @@ int main(int argc, char** argv) {
             server_tail = buf;
         }
         const std::string clip_tail =
-            (o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : std::string()) + (o.dp_given ? agg.dp_tail() : std::string());
+            (o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : o.bulyan ? agg.bulyan_tail() : std::string()) + (o.dp_given ? agg.dp_tail() : std::string());
         printf("{\"round\":%d,\"phase1\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f},"
                "\"phase2\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,\"layers\":%d,"

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""Register, scratch and occupancy table of the FA_TRIMMED kernels, from hipcc's resource-usage remarks.
+"""Register, scratch and occupancy table of the FA_TRIMMED kernels (or, with --kernels centered, of the Bulyan
+stage's centred-mean kernels), from hipcc's resource-usage remarks.
 
     hipcc ... -Rpass-analysis=kernel-resource-usage -c csrc/fa_trimmed.hip 2> remarks.log
     tools/trimmed_resources.py remarks.log [--json out.json]
+    hipcc ... -Rpass-analysis=kernel-resource-usage -c csrc/fa_centered.hip 2> remarks.log
+    tools/trimmed_resources.py remarks.log --kernels centered [--json out.json]
 
 Prints one row per kernel (form, in -> out, P) and exits 1 if any kernel spills VGPRs or uses scratch.
 """
@@ -21,6 +24,7 @@ def demangle(names):
 
 def main():
     log = open(sys.argv[1]).read()
+    family = sys.argv[sys.argv.index("--kernels") + 1] if "--kernels" in sys.argv else "trimmed"
     rows, cur = [], None
     for line in log.splitlines():
         m = re.search(r"remark: .*?(Function Name|VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|"
@@ -33,9 +37,9 @@ def main():
             rows.append(cur)
         elif cur is not None:
             cur[k.split(" [")[0]] = int(v)
-    rows = [r for r in rows if "trimmed_" in r["name"]]
+    rows = [r for r in rows if family + "_" in r["name"]]
     for r, d in zip(rows, demangle([r["name"] for r in rows])):
-        m = re.search(r"trimmed_(vec|elem|wide)_kernel<([^,>]+), ([^,>]+)(?:, (\d+))?", d)
+        m = re.search(family + r"_(vec|elem|wide)_kernel<([^,>]+), ([^,>]+)(?:, (\d+))?", d)
         r["form"], r["in"], r["out"], r["P"] = m.group(1), m.group(2), m.group(3), int(m.group(4) or 128)
     rows.sort(key=lambda r: (r["form"], r["in"], r["out"], r["P"]))
     bad = 0
