@@ -180,6 +180,43 @@
  *                 then the launches, as a Krum part does.
  *              Added without a new FA_ABI_VERSION: fa_centered_device with n == 0 touches no device and answers
  *              FA_OK -- that is how a caller probes for it.
+ *   Geomed stage (fa_set_geomed): the geometric median of the owners of an FA_FEDAVG part by smoothed Weiszfeld
+ *              iterations (Pillutla, Kakade, Harchaoui, "Robust Aggregation for Federated Learning", IEEE TSP 2022,
+ *              "RFA").  It keeps the owners' weights, needs no f and no reference model, has breakdown point 1/2 and
+ *              discards nobody: an owner far from the others is down-weighted, not dropped.  Parameters: iters = T, 1 <=
+ *              T <= FA_GEOMED_MAX_ITERS, and nu, an fp32 value that is finite and > 0: the smoothing floor on a
+ *              distance.  D <= FA_GEOMED_MAX_CLIENTS.  No state across rounds.  Per round, with weights w_k:
+ *              0. Start.  A client whose w_k is not > 0 (zero, negative or NaN) is excluded for the round.  W = the
+ *                 fp64 sum of (double)w_k over the remaining clients, in client order; alpha^0_k = w_k.
+ *              1. Pass t (t = 0 .. T-1), over the currently included clients in ascending client order.  Per element
+ *                 v^t_i is the FA_FEDAVG chain, acc = +0; acc = fmaf(alpha^t_k, x_{k,i}, acc), inputs widened exactly:
+ *                 bit for bit what fa_reduce_device gives for those clients and weights into an f32 output.  For
+ *                 every included k: d = fl32(x_{k,i} - v^t_i), q = (double)d * (double)d, Q^t_k = sum_i q; as in the
+ *                 clip stage the order of the fp64 adds is free within n 2^-53 relative, there are no floating-point
+ *                 atomics and one layout gives the same bits on every run.  For every included k: B_k = the exact
+ *                 count of elements of bucket k that are NaN or +-inf after widening.  One fused kernel does all
+ *                 three: the buckets are read once and v is not stored.  On range shards and range pieces Q and B are
+ *                 added on the host in fp64, in GPU order and then piece order.
+ *              2. Non-finite buckets.  After a pass every included client with B_k > 0 is excluded for the rest of the
+ *                 round.  If that removed anyone the pass's v was poisoned and its distances are void: alpha^t is
+ *                 recomputed by rule 4 over the remaining clients (for t = 0 from w, otherwise from the last valid Q)
+ *                 and the pass is repeated.  Buckets do not change within a round, so this happens at most once, and
+ *                 only at t = 0.
+ *              3. Distances.  N_k = sqrt(Q^t_k) in fp64.  A client whose N_k is NaN or +inf (an fp32 overflow in d or
+ *                 in v) is excluded from now on; the pass is not repeated.
+ *              4. Weights (fa_geomed_weights, pure host arithmetic in fp64).  For included k:
+ *                 beta_k = (double)w_k / max((double)nu, N_k); B = the sum of beta_k in client order.  If B is not > 0,
+ *                 or W / B is not finite: alpha^{t+1}_k = w_k.  Otherwise alpha^{t+1}_k = (float)(beta_k * (W / B)).
+ *                 The round keeps the mass W of the owners that entered it (the Krum stage's convention).
+ *              5. Aggregate.  After pass T-1 and rules 3-4 the aggregate is the plain FA_FEDAVG chain from +0 over the
+ *                 included clients in ascending client order with the weights alpha^T; with nobody included it is +0.
+ *                 It is the part's fp32 aggregate a: it feeds the noise stage and the server optimizer if the part
+ *                 has them, otherwise it is rounded once to the out dtype as for FA_FEDAVG.
+ *              6. Costs.  A reducing call makes T host round trips (T + 1 on a round with a non-finite bucket), then
+ *                 enqueues the final chain without waiting: T fused passes plus one ordinary chain, T + 1 reads of the
+ *                 data.
+ *              Added without a new FA_ABI_VERSION: fa_geomed_pass_device with n == 0 touches no device, writes zeros
+ *              and answers FA_OK -- that is how a caller probes for it.
  *   Noise stage (fa_set_noise, fa_noise_device, fa_noise_host): Gaussian noise on the round's aggregate, the other
  *              half of DP-FedAvg (McMahan et al., "Learning Differentially Private Recurrent Language Models"):
  *              a'_i = a_i + stddev z_i with z_i a standard normal, specified bit for bit.  Parameters: stddev
@@ -268,6 +305,9 @@ typedef enum { FA_FEDAVG = 0, FA_LITERAL = 1, FA_TRIMMED = 2 /* trimmed mean / m
 #define FA_TRIMMED_MAX_CLIENTS 128
 /* Most clients of a part with the Krum stage, and of fa_pairdist_device (more: FA_ERR_ARG). */
 #define FA_KRUM_MAX_CLIENTS 128
+/* Most clients of a part with the geomed stage, and of fa_geomed_pass_device; most Weiszfeld passes per round. */
+#define FA_GEOMED_MAX_CLIENTS 128
+#define FA_GEOMED_MAX_ITERS 64
 
 typedef enum {
     FA_OK = 0,
@@ -615,6 +655,48 @@ int fa_bulyan_select(const double* dist, int D, int f, int* order, double* pick_
  * Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
 int fa_centered_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, void* d_out,
                        fa_dtype out, int keep, void* hip_stream);
+
+/* Geomed stage: the geometric median of an FA_FEDAVG part's owners by smoothed Weiszfeld iterations (the header
+ * comment, "Geomed stage").  Gives a part the stage with T = iters passes and the smoothing floor nu (part_id >= 0;
+ * calling again changes them), or sets the context default that FA_FEDAVG parts defined later take (part_id < 0;
+ * checked against D when such a part is defined, where a misfit makes fa_bucket_define fail).  iters == 0 removes the
+ * stage (nu is then ignored).  FA_ERR_ARG, naming the cause: iters outside 0..FA_GEOMED_MAX_ITERS, nu not finite or
+ * <= 0, D > FA_GEOMED_MAX_CLIENTS, an FA_LITERAL or FA_TRIMMED part, an FA_SHARD_CLIENT_RS context, a part (or context
+ * default) that has the clip or the Krum stage -- and fa_set_clip or fa_set_krum on a geomed part: they do not compose.
+ * The server optimizers and the noise stage compose, in either call order.  Like the other stage parts a geomed part
+ * is never kept host-side (fa_bucket_host_read says 0), FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager, it gets its own
+ * launches in fa_reduce_parts, and a reducing call needs every client submitted (FA_ERR_STATE otherwise);
+ * fa_reduce_part marks the round reduced.  Such a call waits on the host after each of its T passes (T + 1 on a
+ * round with a non-finite bucket) and then enqueues the chain.  Range shards and range pieces work.  The stage keeps
+ * no state across rounds. */
+int fa_set_geomed(fa_ctx* ctx, int part_id, int iters, float nu);
+/* The stage a part has (*iters == 0: none), or with part_id < 0 the context default.  Either pointer may be NULL. */
+int fa_get_geomed(fa_ctx* ctx, int part_id, int* iters, float* nu);
+/* The whole trace of the part's last reducing call.  *n_passes = the valid passes P <= T (a voided pass is not
+ * reported); sumsq[t * D + k] = Q^t_k for t < P (room for FA_GEOMED_MAX_ITERS * D; 0 for a client not in pass t);
+ * weights[t * D + k] = alpha^t_k for t <= P, the last row the final chain's weights (room for
+ * (FA_GEOMED_MAX_ITERS + 1) * D; 0 for a client excluded by then); included[k] = the final flags (D entries);
+ * objective[t] = sum_k (double)w_k N^t_k over the clients included at pass t, in client order (room for
+ * FA_GEOMED_MAX_ITERS).  Any pointer may be NULL.  FA_ERR_STATE on a part without the stage or never reduced with it. */
+int fa_geomed_get_round(fa_ctx* ctx, int part_id, int* n_passes, double* sumsq, float* weights, int* included,
+                        double* objective);
+/* Rules 3-4 of the stage, pure host arithmetic, usable without a device: included (D flags, in and out) loses the
+ * clients whose sqrt(sumsq[k]) is NaN or +inf; w_out[k] = alpha_k for the clients still included, 0 for the others.
+ * w are the round's own weights: a client whose w_k is not > 0 loses its flag too, and W is the fp64 sum of every
+ * w_k > 0 in client order whatever the flags say -- the mass of the owners that entered the round stays W when one
+ * of them is excluded on the way.  Entries of sumsq of clients not included are not read.  The stage's
+ * objective[t] is sum_k (double)w_k N_k over the clients still included after rule 3.  FA_ERR_ARG for a null
+ * pointer, D < 1, nu not finite or <= 0. */
+int fa_geomed_weights(const float* w, const double* sumsq, int* included, int D, float nu, float* w_out);
+/* Rule 1 on raw device pointers: over the D client buckets (n elements of `in`) on device `gpu`, 1 <= D <=
+ * FA_GEOMED_MAX_CLIENTS, with the weights h_weights (D floats, host): h_sumsq[k] = Q_k against the chain v of all D
+ * clients, h_nonfinite[k] = B_k (D doubles each, host), and, if d_v is not NULL, d_v (n fp32, device) = v.  ctx may be
+ * NULL (then `gpu` is the HIP device).  Every argument is checked before any device call: D, the dtype, h_weights,
+ * h_sumsq, h_nonfinite, and for n > 0 null pointers and element alignment (FA_ERR_ALIGN); with n == 0 and valid
+ * arguments it touches no device, writes 2 D zeros and answers FA_OK.  Otherwise it enqueues on hip_stream (NULL = the
+ * ctx's compute stream of `gpu`, or the null stream), waits for it and returns the 2 D numbers. */
+int fa_geomed_pass_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const float* h_weights, int D, size_t n,
+                          fa_dtype in, float* d_v, double* h_sumsq, double* h_nonfinite, void* hip_stream);
 
 /* Noise stage: Gaussian noise on a part's fp32 aggregate (the header comment, "Noise stage").  Gives a part the
  * stage with standard deviation stddev > 0 and the seed (part_id >= 0; the part id is the stream; calling again

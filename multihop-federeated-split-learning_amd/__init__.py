@@ -23,6 +23,7 @@ FEDAVG, LITERAL, TRIMMED = 0, 1, 2
 TRIM_MEDIAN = -1  # FA_TRIM_MEDIAN: the largest valid trim, (D-1)/2
 TRIMMED_MAX_CLIENTS = 128
 KRUM_MAX_CLIENTS = 128  # FA_KRUM_MAX_CLIENTS: the Krum stage and pairdist_device
+GEOMED_MAX_CLIENTS, GEOMED_MAX_ITERS = 128, 64  # FA_GEOMED_MAX_*: the geomed stage and geomed_pass_device
 # fa_opt_rule: the server-optimizer stage (FedAvgM, FedAdagrad, FedAdam, FedYogi; fa.h "Server optimizer")
 OPT_NONE, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 0, 1, 2, 3, 4
 SHARD_RANGE, SHARD_CLIENT_RS, ACCUMULATE_ON_ARRIVAL, TEST_SHARED_DEVICE = 0x1, 0x2, 0x4, 0x100
@@ -102,6 +103,11 @@ def lib():
         "fa_krum_select": (I, [P, I, I, I, P, P, ctypes.POINTER(I)]),
         "fa_krum_weights": (I, [P, P, I, P]),
         "fa_pairdist_device": (I, [P, I, P, I, S, I, P, P]),
+        "fa_set_geomed": (I, [P, I, I, F]),
+        "fa_get_geomed": (I, [P, I, ctypes.POINTER(I), ctypes.POINTER(F)]),
+        "fa_geomed_get_round": (I, [P, I, ctypes.POINTER(I), P, P, P, P]),
+        "fa_geomed_weights": (I, [P, P, P, I, F, P]),
+        "fa_geomed_pass_device": (I, [P, I, P, P, I, S, I, P, P, P, P]),
         "fa_set_bulyan": (I, [P, I, I]),
         "fa_bulyan_get_round": (I, [P, I, P, P, P, P, ctypes.POINTER(I)]),
         "fa_bulyan_select": (I, [P, I, I, P, P, P, ctypes.POINTER(I)]),
@@ -329,6 +335,36 @@ def krum_weights(weights, selected):
     out = np.empty(w.size, np.float32)
     check(lib().fa_krum_weights(w.ctypes.data, sel.ctypes.data, w.size, out.ctypes.data))
     return out
+
+
+def geomed_pass_device(clients, weights, n, in_dtype, v=None, stream=None, gpu=0, ctx=None):
+    """fa_geomed_pass_device: one fused Weiszfeld pass over D device-resident client buckets (fa.h "Geomed stage",
+    rule 1): (sumsq float64[D], nonfinite float64[D]) -- Q_k against the FEDAVG chain of all D clients under
+    `weights`, and the count of NaN / inf elements per bucket; `v` (a device fp32 buffer of n, or None) receives the
+    chain.  Enqueued on `stream` and waited for.  With n == 0 no device is touched and both are zeros: the probe."""
+    D = len(clients)
+    arr = (ctypes.c_void_p * max(1, D))(*[_addr(c) for c in clients])
+    w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+    if w.size != D:
+        raise ValueError("need one weight per client")
+    q, b = np.empty(D, np.float64), np.empty(D, np.float64)
+    check(lib().fa_geomed_pass_device(ctx.handle if ctx is not None else None, gpu, arr, w.ctypes.data, D, n, in_dtype,
+                                      _addr(v), q.ctypes.data, b.ctypes.data, _stream(stream)))
+    return q, b
+
+
+def geomed_weights(weights, sumsq, included, nu=1e-6):
+    """fa_geomed_weights (host arithmetic, rules 3-4): (alpha float32[D], included bool[D]) -- the next pass's
+    weights from the round's weights, the squared distances Q_k and the clients included so far; a client whose
+    distance is NaN or infinite, or whose weight is not > 0, leaves `included` and gets weight 0."""
+    w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+    q = np.ascontiguousarray(np.asarray(sumsq, np.float64).reshape(-1))
+    inc = np.ascontiguousarray(np.asarray(included).reshape(-1).astype(np.intc))
+    if q.size != w.size or inc.size != w.size:
+        raise ValueError("need one distance and one flag per weight")
+    out = np.empty(w.size, np.float32)
+    check(lib().fa_geomed_weights(w.ctypes.data, q.ctypes.data, inc.ctypes.data, w.size, float(nu), out.ctypes.data))
+    return out, inc.astype(bool)
 
 
 def centered_device(clients, n, in_dtype, out, out_dtype=F32, keep=1, stream=None, gpu=0, ctx=None):
@@ -665,6 +701,31 @@ class Aggregator:
         check(lib().fa_krum_get_round(self.handle, part_id, q.ctypes.data, s.ctypes.data, sel.ctypes.data,
                                       ctypes.byref(ns)))
         return q, s, sel.astype(bool)
+
+    def set_geomed(self, iters, nu=1e-6, part=None):
+        """fa_set_geomed: the geometric median (RFA: `iters` smoothed Weiszfeld passes with the distance floor `nu`)
+        on a FEDAVG part (part=None: the default of FEDAVG parts defined later); iters=0 removes the stage."""
+        check(lib().fa_set_geomed(self.handle, -1 if part is None else part, int(iters), float(nu)))
+
+    def geomed(self, part=None):
+        """fa_get_geomed: (iters, nu) of the part's stage (iters 0: none), or of the context default."""
+        it, nu = ctypes.c_int(), ctypes.c_float()
+        check(lib().fa_get_geomed(self.handle, -1 if part is None else part, ctypes.byref(it), ctypes.byref(nu)))
+        return it.value, nu.value
+
+    def geomed_round(self, part):
+        """fa_geomed_get_round: the trace of the part's last reducing call as (sumsq float64[P, D], weights
+        float32[P + 1, D], included bool[D], objective float64[P]) over its P valid passes; the last row of
+        `weights` is the final chain's."""
+        D = self.parts[part][3]
+        q = np.zeros((GEOMED_MAX_ITERS, D), np.float64)
+        w = np.zeros((GEOMED_MAX_ITERS + 1, D), np.float32)
+        inc, obj = np.empty(D, np.intc), np.zeros(GEOMED_MAX_ITERS, np.float64)
+        npass = ctypes.c_int()
+        check(lib().fa_geomed_get_round(self.handle, part, ctypes.byref(npass), q.ctypes.data, w.ctypes.data,
+                                        inc.ctypes.data, obj.ctypes.data))
+        t = npass.value
+        return q[:t].copy(), w[:t + 1].copy(), inc.astype(bool), obj[:t].copy()
 
     def set_bulyan(self, f, part_id=-1):
         """fa_set_bulyan: the Bulyan stage (iterated Krum, then a median-centred mean) on a TRIMMED part with f

@@ -358,6 +358,15 @@ struct Part {
     std::vector<double> krum_q, krum_s;
     std::vector<int> krum_sel;
     int krum_n = 0;
+    // Geomed stage (fa.h "Geomed stage"; geomed_iters == 0: none): T and nu, and the trace of the last reducing
+    // call -- its valid passes, Q^t and alpha^t row by row, the objective per pass, the final flags.  Host state only.
+    int geomed_iters = 0;
+    float geomed_nu = 0.0f;
+    bool geomed_reported = false;
+    int geomed_passes = 0;
+    std::vector<double> geomed_q, geomed_obj;
+    std::vector<float> geomed_w;
+    std::vector<int> geomed_in;
     // Bulyan stage of an FA_TRIMMED part (fa.h "Bulyan stage"; bulyan_f < 0: none): f, and what the last reducing
     // call found -- the D x D matrix, the picks in pick order with their scores, the flags.  Host state only.
     int bulyan_f = -1;
@@ -372,10 +381,11 @@ struct Part {
     uint64_t noise_round = 0;
 };
 
-// A part whose reducing calls are rounds of their own (a server-optimizer, clip, Krum, Bulyan or noise stage):
+// A part whose reducing calls are rounds of their own (a server-optimizer, clip, Krum, geomed, Bulyan or noise stage):
 // never batched, eager or host-read, every client submitted before each.
 inline bool staged(const Part& p) {
-    return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0 || p.bulyan_f >= 0 || p.noise > 0.0f;
+    return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0 || p.geomed_iters != 0 || p.bulyan_f >= 0 ||
+           p.noise > 0.0f;
 }
 // A part that gets its first stage: what this round chained or kept host-side so far goes back to the plain path.
 inline void restart_round_plain(Part& p) {
@@ -393,6 +403,8 @@ struct fa_ctx {
     fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};  // default stage of FedAvg / trimmed parts defined later
     float clip = 0.0f;          // default clip bound of FedAvg parts defined later (0: none)
     int krum_f = 0, krum_m = 0; // default Krum stage of FedAvg parts defined later (m == 0: none, -1: D - f)
+    int geomed_iters = 0;       // default geomed stage of FedAvg parts defined later (0: none)
+    float geomed_nu = 0.0f;
     int bulyan_f = -1;          // default Bulyan stage of trimmed parts defined later (< 0: none)
     float noise = 0.0f;         // default noise stage of FedAvg / trimmed parts defined later (0: none)
     uint64_t noise_seed = 0;
@@ -740,6 +752,79 @@ int pairdist_on(const fa::Tuning& tu, const void* const* clients, int D, size_t 
     for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
     const fa::ClientTable t = client_table(clients, nullptr, 0, D);
     FA_HIP(fa::launch_pairdist(t, D, in, sp, d_part, d_dist, tu, s));
+    return FA_OK;
+}
+
+// ------------------------------------------------------------------ geomed stage
+
+// The refusals of T and nu, and of D clients when D > 0 (fa.h "Geomed stage"), naming the cause.
+int check_geomed(int D, int iters, float nu) {
+    if (iters < 0 || iters > FA_GEOMED_MAX_ITERS)
+        return fail(FA_ERR_ARG, "geomed: iters = %d outside 0..%d (0 removes the stage)", iters, FA_GEOMED_MAX_ITERS);
+    if (iters != 0 && (!finite_f(nu) || !(nu > 0.0f))) return fail(FA_ERR_ARG, "geomed: nu %g must be finite and > 0", (double)nu);
+    if (iters != 0 && D > FA_GEOMED_MAX_CLIENTS)
+        return fail(FA_ERR_ARG, "geomed: D = %d clients (at most %d)", D, FA_GEOMED_MAX_CLIENTS);
+    return FA_OK;
+}
+
+// Rules 3-4 of fa.h "Geomed stage": volatile keeps each step one rounded fp64 operation.  W is the mass of the owners
+// that entered the round: every k with w_k > 0, whatever `included` says by now.  *objective (nullable) = sum_k
+// (double)w_k N_k over the clients still included after rule 3.
+void geomed_weights(const float* w, const double* sumsq, int* included, int D, float nu, float* w_out, double* objective) {
+    volatile double W = 0.0, B = 0.0, obj = 0.0;
+    std::vector<double> beta((size_t)D, 0.0);
+    for (int k = 0; k < D; ++k) {
+        if (!(w[k] > 0.0f)) {
+            included[k] = 0;
+            continue;
+        }
+        W = W + (double)w[k];
+        if (!included[k]) continue;
+        volatile double nrm = std::sqrt(sumsq[k]);
+        const double N = nrm;
+        if (N != N || N == HUGE_VAL) {
+            included[k] = 0;
+            continue;
+        }
+        volatile double term = (double)w[k] * N;
+        obj = obj + term;
+        const double floor_ = (double)nu;
+        volatile double b = (double)w[k] / (floor_ > N ? floor_ : N);
+        beta[(size_t)k] = b;
+        B = B + b;
+    }
+    volatile double ratio = 0.0;
+    bool plain = !(B > 0.0);
+    if (!plain) {
+        ratio = W / B;
+        const double r = ratio;
+        plain = r != r || r == HUGE_VAL || r == -HUGE_VAL;
+    }
+    for (int k = 0; k < D; ++k) {
+        if (!included[k]) {
+            w_out[k] = 0.0f;
+        } else if (plain) {
+            w_out[k] = w[k];
+        } else {
+            volatile double prod = beta[(size_t)k] * ratio;
+            w_out[k] = (float)prod;
+        }
+    }
+    if (objective) *objective = obj;
+}
+
+constexpr size_t kGeomedParts = 2 * kClipParts;  // the fused pass's partials: Q and B of every client
+
+// Enqueues the fused pass on the current device: d_out[k] = Q_k and d_out[nc + k] = B_k of clients[0..nc) (n > 0
+// elements of `in`) under the weights w, d_v (nullable, n fp32) = the chain; d_part: kGeomedParts doubles of scratch.
+// The vector form where every client (and d_v) allows it (fa_split.h).
+int geomed_pass_on(const fa::Tuning& tu, const void* const* clients, const float* w, int nc, size_t n, fa_dtype in,
+                   float* d_v, double* d_part, double* d_out, hipStream_t s) {
+    fa::Split sp = fa::split_at(clients[0], dsize(in), n);
+    for (int k = 0; k < nc; ++k) sp.require_input(clients[k]);
+    if (d_v) sp.require(d_v, 4);
+    const fa::ClientTable t = client_table(clients, w, 0, nc);
+    FA_HIP(fa::launch_geomed_pass(t, nc, in, d_v, sp, d_part, d_out, tu, s));
     return FA_OK;
 }
 
@@ -1512,6 +1597,79 @@ int krum_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* p
     return FA_OK;
 }
 
+// Rules 0-4 for part p (range layout): T fused passes (measure_pass over the included clients alone, 2 m results: Q
+// then B), each followed by the host arithmetic; a pass that finds a non-finite bucket is void and repeated without
+// its owner.  The plan is the final chain's: the included clients and alpha^T.  Leaves the round's trace in the part.
+int geomed_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* plan) {
+    const size_t D = (size_t)p.D;
+    const int T = p.geomed_iters;
+    p.geomed_q.assign((size_t)T * D, 0.0);
+    p.geomed_w.assign((size_t)(T + 1) * D, 0.0f);
+    p.geomed_obj.assign((size_t)T, 0.0);
+    p.geomed_in.assign(D, 0);
+    p.geomed_passes = 0;
+    std::vector<int>& inc = p.geomed_in;
+    std::vector<float> alpha(D, 0.0f);
+    for (size_t k = 0; k < D; ++k) {
+        inc[k] = w[k] > 0.0f ? 1 : 0;
+        if (inc[k]) alpha[k] = w[k];
+    }
+    std::vector<int> idx;
+    std::vector<float> wsub;
+    std::vector<const void*> sub;
+    std::vector<double> res;
+    const double* last_q = nullptr;  // the last valid pass's row
+    int t = 0;
+    while (t < T) {
+        idx.clear();
+        wsub.clear();
+        for (size_t k = 0; k < D; ++k)
+            if (inc[k]) {
+                idx.push_back((int)k);
+                wsub.push_back(alpha[k]);
+            }
+        const size_t m = idx.size();
+        if (m == 0) break;  // nobody left: the aggregate is +0
+        res.assign(2 * m, 0.0);
+        if (int rc = measure_pass(ctx, p, s, 2 * m, kGeomedParts, "geomed: fused pass", res.data(),
+                                  [&](int, int, const void* const* clients, size_t cnt, double* d_part, double* d_out,
+                                      hipStream_t st) {
+                                      sub.resize(m);
+                                      for (size_t i = 0; i < m; ++i) sub[i] = clients[idx[i]];
+                                      return geomed_pass_on(ctx->tuning.tu, sub.data(), wsub.data(), (int)m, cnt, p.in, nullptr,
+                                                            d_part, d_out, st);
+                                  }))
+            return rc;
+        bool removed = false;
+        for (size_t i = 0; i < m; ++i)
+            if (res[m + i] > 0.0) {  // rule 2: a non-finite bucket poisons v; the pass is void
+                inc[(size_t)idx[i]] = 0;
+                removed = true;
+            }
+        if (removed) {
+            for (size_t k = 0; k < D; ++k) alpha[k] = inc[k] ? w[k] : 0.0f;
+            if (last_q) geomed_weights(w, last_q, inc.data(), p.D, p.geomed_nu, alpha.data(), nullptr);
+            continue;
+        }
+        double* qrow = &p.geomed_q[(size_t)t * D];
+        for (size_t i = 0; i < m; ++i) qrow[(size_t)idx[i]] = res[i];
+        std::copy(alpha.begin(), alpha.end(), p.geomed_w.begin() + (ptrdiff_t)((size_t)t * D));
+        geomed_weights(w, qrow, inc.data(), p.D, p.geomed_nu, alpha.data(), &p.geomed_obj[(size_t)t]);
+        last_q = qrow;
+        p.geomed_passes = ++t;
+    }
+    for (size_t k = 0; k < D; ++k)
+        if (!inc[k]) alpha[k] = 0.0f;
+    std::copy(alpha.begin(), alpha.end(), p.geomed_w.begin() + (ptrdiff_t)((size_t)p.geomed_passes * D));
+    for (size_t k = 0; k < D; ++k)
+        if (inc[k]) {
+            plan->inc.push_back((int)k);
+            plan->w.push_back(alpha[k]);
+        }
+    p.geomed_reported = true;
+    return FA_OK;
+}
+
 // Rules 1-2 of the Bulyan stage for part p (range layout): the distance pass (measure_pass), then the iterated
 // selection.  The plan's clients are the picks in ascending client order; its weights stay empty (the rule has
 // none).  Leaves the round's report in the part.
@@ -1581,7 +1739,11 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
         const bool krum = p.krum_m != 0;  // never with a clip stage
         if (krum)
             if (int rc = krum_plan(ctx, p, w, s, &plan)) return rc;
-        // a Bulyan stage (an FA_TRIMMED part: never with the two above): the same pass and wait, then the picks
+        // a geomed stage (never with the two above): T fused passes, a host wait and the new weights after each
+        const bool geomed = p.geomed_iters != 0;
+        if (geomed)
+            if (int rc = geomed_plan(ctx, p, w, s, &plan)) return rc;
+        // a Bulyan stage (an FA_TRIMMED part: never with the three above): the same pass and wait, then the picks
         const bool bulyan = p.bulyan_f >= 0;
         if (bulyan)
             if (int rc = bulyan_plan(ctx, p, s, &plan)) return rc;
@@ -1607,7 +1769,7 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
                 if (p.mode == FA_LITERAL) {
                     const void* last = piece_ptr(p, g, p.last_slot >= 0 ? p.last_slot : p.D - 1, j);
                     rc = reduce_on(ctx, g, tu, &last, w, 1, cnt, p.in, dst, p.out, FA_LITERAL, p.divisor, nullptr, st);
-                } else if (clipping || krum)
+                } else if (clipping || krum || geomed)
                     rc = subset_chain(ctx, p, g, j, plan, adst, adt, st);
                 else if (bulyan)
                     rc = bulyan_piece(ctx, p, g, j, plan, adst, adt, st);
@@ -2538,6 +2700,9 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     int krum_m = 0;
     if (krummed)
         if (int rc = check_krum(n_clients, ctx->krum_f, ctx->krum_m, &krum_m)) return rc;
+    const bool geomedded = ctx->geomed_iters != 0 && mode == FA_FEDAVG && !rs;  // takes the context's geomed stage
+    if (geomedded)
+        if (int rc = check_geomed(n_clients, ctx->geomed_iters, ctx->geomed_nu)) return rc;
     const bool bulyaned = ctx->bulyan_f >= 0 && mode == FA_TRIMMED;  // takes the context's Bulyan stage
     if (bulyaned)
         if (int rc = check_bulyan(n_clients, ctx->bulyan_f)) return rc;
@@ -2564,7 +2729,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     const bool clipped = ctx->clip > 0.0f && mode == FA_FEDAVG && !rs;  // takes the context's clip bound
     const bool noisy = ctx->noise > 0.0f && mode != FA_LITERAL && !rs;  // takes the context's noise stage
     const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged && !clipped &&
-                       !krummed && !noisy;
+                       !krummed && !geomedded && !noisy;
     if (rs) {
         const size_t unit = G * kShardUnit;
         p.npad = (n_elems + unit - 1) / unit * unit;
@@ -2662,6 +2827,10 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     if (krummed) {
         p.krum_f = ctx->krum_f;
         p.krum_m = krum_m;
+    }
+    if (geomedded) {
+        p.geomed_iters = ctx->geomed_iters;
+        p.geomed_nu = ctx->geomed_nu;
     }
     if (bulyaned) p.bulyan_f = ctx->bulyan_f;
     if (noisy) {
@@ -2782,6 +2951,8 @@ int fa_set_clip(fa_ctx* ctx, int part_id, float max_norm) {
     if (part_id < 0) {
         if (max_norm > 0.0f && ctx->krum_m != 0)
             return fail(FA_ERR_ARG, "clip: the context default has a Krum stage (the two stages do not compose)");
+        if (max_norm > 0.0f && ctx->geomed_iters != 0)
+            return fail(FA_ERR_ARG, "clip: the context default has a geomed stage (the two stages do not compose)");
         ctx->clip = max_norm;
         return FA_OK;
     }
@@ -2793,6 +2964,8 @@ int fa_set_clip(fa_ctx* ctx, int part_id, float max_norm) {
                     p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_TRIMMED");
     if (max_norm > 0.0f && p->krum_m != 0)
         return fail(FA_ERR_ARG, "clip: part %d has a Krum stage (the two stages do not compose)", part_id);
+    if (max_norm > 0.0f && p->geomed_iters != 0)
+        return fail(FA_ERR_ARG, "clip: part %d has a geomed stage (the two stages do not compose)", part_id);
     return set_part_clip(ctx, *p, max_norm);
 }
 
@@ -2879,6 +3052,8 @@ int fa_set_krum(fa_ctx* ctx, int part_id, int f, int m) {
     if (part_id < 0) {
         if (m != 0 && ctx->clip > 0.0f)
             return fail(FA_ERR_ARG, "krum: the context default has a clip stage (the two stages do not compose)");
+        if (m != 0 && ctx->geomed_iters != 0)
+            return fail(FA_ERR_ARG, "krum: the context default has a geomed stage (the two stages do not compose)");
         ctx->krum_f = m != 0 ? f : 0;
         ctx->krum_m = m;
         return FA_OK;
@@ -2899,6 +3074,8 @@ int fa_set_krum(fa_ctx* ctx, int part_id, int f, int m) {
                     p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_TRIMMED");
     if (p->clip > 0.0f)
         return fail(FA_ERR_ARG, "krum: part %d has a clip stage (the two stages do not compose)", part_id);
+    if (p->geomed_iters != 0)
+        return fail(FA_ERR_ARG, "krum: part %d has a geomed stage (the two stages do not compose)", part_id);
     int mm = 0;
     if ((rc = check_krum(p->D, f, m, &mm))) return rc;
     const bool fresh = p->krum_m == 0;
@@ -2964,6 +3141,123 @@ int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D
                           [&](const DeviceCall& c, double* d_part, double* d_out) {
                               return pairdist_on(c.tu, d_clients, D, n, in, d_part, d_out, c.s);
                           });
+}
+
+int fa_set_geomed(fa_ctx* ctx, int part_id, int iters, float nu) {
+    g_err.clear();
+    if (int rc = check_geomed(0, iters, nu)) return rc;
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (iters != 0 && (ctx->flags & FA_SHARD_CLIENT_RS))
+        return fail(FA_ERR_ARG, "geomed: not on an FA_SHARD_CLIENT_RS context (a distance needs every client of an element "
+                                "on one GPU; use FA_SHARD_RANGE)");
+    if (part_id < 0) {
+        if (iters != 0 && ctx->clip > 0.0f)
+            return fail(FA_ERR_ARG, "geomed: the context default has a clip stage (the two stages do not compose)");
+        if (iters != 0 && ctx->krum_m != 0)
+            return fail(FA_ERR_ARG, "geomed: the context default has a Krum stage (the two stages do not compose)");
+        ctx->geomed_iters = iters;
+        ctx->geomed_nu = iters != 0 ? nu : 0.0f;
+        return FA_OK;
+    }
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (iters == 0) {  // the stage and its trace go
+        p->geomed_iters = 0;
+        p->geomed_nu = 0.0f;
+        p->geomed_reported = false;
+        p->geomed_passes = 0;
+        p->geomed_q.clear();
+        p->geomed_w.clear();
+        p->geomed_obj.clear();
+        p->geomed_in.clear();
+        return FA_OK;
+    }
+    if (p->mode != FA_FEDAVG)
+        return fail(FA_ERR_ARG, "geomed: part %d is an %s part (the stage re-weights the owners of an FA_FEDAVG average)",
+                    part_id, p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_TRIMMED");
+    if (p->clip > 0.0f) return fail(FA_ERR_ARG, "geomed: part %d has a clip stage (the two stages do not compose)", part_id);
+    if (p->krum_m != 0) return fail(FA_ERR_ARG, "geomed: part %d has a Krum stage (the two stages do not compose)", part_id);
+    if ((rc = check_geomed(p->D, iters, nu))) return rc;
+    const bool fresh = p->geomed_iters == 0;
+    p->geomed_iters = iters;
+    p->geomed_nu = nu;
+    if (fresh) {
+        p->geomed_reported = false;
+        restart_round_plain(*p);
+    }
+    return FA_OK;
+}
+
+int fa_get_geomed(fa_ctx* ctx, int part_id, int* iters, float* nu) {
+    g_err.clear();
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    int it = ctx->geomed_iters;
+    float v = ctx->geomed_nu;
+    if (part_id >= 0) {
+        Part* p;
+        int rc = check_part(ctx, part_id, &p);
+        if (rc) return rc;
+        it = p->geomed_iters;
+        v = p->geomed_nu;
+    }
+    if (iters) *iters = it;
+    if (nu) *nu = v;
+    return FA_OK;
+}
+
+int fa_geomed_get_round(fa_ctx* ctx, int part_id, int* n_passes, double* sumsq, float* weights, int* included,
+                        double* objective) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (p->geomed_iters == 0) return fail(FA_ERR_STATE, "part %d has no geomed stage", part_id);
+    if (!p->geomed_reported) return fail(FA_ERR_STATE, "part %d: no round reduced with the geomed stage yet", part_id);
+    const size_t D = (size_t)p->D, np = (size_t)p->geomed_passes;
+    if (n_passes) *n_passes = p->geomed_passes;
+    if (sumsq) std::copy(p->geomed_q.begin(), p->geomed_q.begin() + (ptrdiff_t)(np * D), sumsq);
+    if (weights) std::copy(p->geomed_w.begin(), p->geomed_w.begin() + (ptrdiff_t)((np + 1) * D), weights);
+    if (included) std::copy(p->geomed_in.begin(), p->geomed_in.end(), included);
+    if (objective) std::copy(p->geomed_obj.begin(), p->geomed_obj.begin() + (ptrdiff_t)np, objective);
+    return FA_OK;
+}
+
+int fa_geomed_weights(const float* w, const double* sumsq, int* included, int D, float nu, float* w_out) {
+    g_err.clear();
+    if (!w || !sumsq || !included || !w_out) return fail(FA_ERR_ARG, "geomed: w, sumsq, included or w_out is null");
+    if (D < 1) return fail(FA_ERR_ARG, "geomed: D must be >= 1");
+    if (!finite_f(nu) || !(nu > 0.0f)) return fail(FA_ERR_ARG, "geomed: nu %g must be finite and > 0", (double)nu);
+    geomed_weights(w, sumsq, included, D, nu, w_out, nullptr);
+    return FA_OK;
+}
+
+int fa_geomed_pass_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const float* h_weights, int D, size_t n,
+                          fa_dtype in, float* d_v, double* h_sumsq, double* h_nonfinite, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (D < 1 || D > FA_GEOMED_MAX_CLIENTS)
+        return fail(FA_ERR_ARG, "geomed: D = %d outside 1..%d", D, FA_GEOMED_MAX_CLIENTS);
+    if (!dvalid(in)) return fail(FA_ERR_ARG, "bad dtype");
+    if (!h_weights) return fail(FA_ERR_ARG, "geomed: h_weights is null");
+    if (!h_sumsq || !h_nonfinite) return fail(FA_ERR_ARG, "geomed: %s is null", !h_sumsq ? "h_sumsq" : "h_nonfinite");
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) {
+        std::fill(h_sumsq, h_sumsq + D, 0.0);
+        std::fill(h_nonfinite, h_nonfinite + D, 0.0);
+        return FA_OK;
+    }
+    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
+    if (d_v && !aligned(d_v, 4)) return fail(FA_ERR_ALIGN, "geomed: d_v not 4-byte aligned");
+    std::vector<double> res(2 * (size_t)D);
+    if (int rc = measure_device(ctx, gpu, hip_stream, 2 * (size_t)D, kGeomedParts, "geomed: fused pass", res.data(),
+                                [&](const DeviceCall& c, double* d_part, double* d_out) {
+                                    return geomed_pass_on(c.tu, d_clients, h_weights, D, n, in, d_v, d_part, d_out, c.s);
+                                }))
+        return rc;
+    std::copy(res.begin(), res.begin() + D, h_sumsq);
+    std::copy(res.begin() + D, res.end(), h_nonfinite);
+    return FA_OK;
 }
 
 int fa_set_bulyan(fa_ctx* ctx, int part_id, int f) {

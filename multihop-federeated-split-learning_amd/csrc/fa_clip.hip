@@ -32,31 +32,12 @@ namespace fa {
 
 namespace {
 
-constexpr int kClipThreads = 256, kClipWaves = kClipThreads / 64;
+constexpr int kClipThreads = kMeasureThreads;
 constexpr int kClipLaneElems = 16;                                  // elements of g a lane keeps in registers
 constexpr int64_t kClipTile = (int64_t)kClipThreads * kClipLaneElems;  // elements per tile
 
-// LDS: one fp64 sum per (wave, client), touched only by lane 0 of its wave between the two barriers.
-struct ClipLds {
-    double acc[kClipWaves][kMaxClients];
-};
-
-__device__ __forceinline__ void lds_zero(ClipLds& l) {
-    double* a = &l.acc[0][0];
-    for (int i = threadIdx.x; i < kClipWaves * kMaxClients; i += kClipThreads) a[i] = 0.0;
-    __syncthreads();
-}
-
-// partials[k * pstride + slot] = the workgroup's sum for client k, the waves added in wave order.
-__device__ __forceinline__ void lds_flush(ClipLds& l, int nc, double* partials, int64_t pstride, int64_t slot) {
-    __syncthreads();
-    for (int k = threadIdx.x; k < nc; k += kClipThreads) {
-        double a = l.acc[0][k];
-#pragma unroll
-        for (int w = 1; w < kClipWaves; ++w) a += l.acc[w][k];
-        partials[(int64_t)k * pstride + slot] = a;
-    }
-}
+// LDS: one fp64 sum per (wave, client) (MeasureLds, lds_zero and lds_flush of fa_device.h).
+using ClipLds = MeasureLds<kMaxClients>;
 
 // Vector form: vector v of a bucket is elements head + V v .. + V - 1 (16-byte aligned in every client, and in
 // ref for its 4-element vectors).  Tile `tile` is vectors [tile * 256 R, + 256 R), lane-interleaved.
@@ -184,11 +165,15 @@ hipError_t launch_sumsq_t(const ClientTable& t, int nc, const float* ref, const 
         hipLaunchKernelGGL((clip_sumsq_elem_kernel<T>), dim3((unsigned)gr.elem_blocks), dim3(kClipThreads), 0, s, t, nc,
                            ref, sp.n, sp.n, sp.n, partials, np, (int64_t)0);
     }
-    hipLaunchKernelGGL(clip_finish_kernel, dim3((unsigned)nc), dim3(64), 0, s, partials, np, np, sums);
-    return hipGetLastError();
+    return launch_measure_finish(partials, np, nc, sums, s);
 }
 
 }  // namespace
+
+hipError_t launch_measure_finish(const double* partials, int64_t np, int rows, double* sums, hipStream_t s) {
+    hipLaunchKernelGGL(clip_finish_kernel, dim3((unsigned)rows), dim3(64), 0, s, partials, np, np, sums);
+    return hipGetLastError();
+}
 
 hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const float* ref, const Split& sp,
                              double* partials, double* sums, const Tuning& tu, hipStream_t s) {

@@ -78,6 +78,31 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// The workgroup half of a measure pass's reduction (fa_clip.hip, fa_geomed.hip): 256 lanes, one fp64 sum per
+// (wave, row) in LDS, touched only by lane 0 of its wave between the two barriers.
+constexpr int kMeasureThreads = 256, kMeasureWaves = kMeasureThreads / 64;
+template <int ROWS>
+struct MeasureLds {
+    double acc[kMeasureWaves][ROWS];
+};
+template <int ROWS>
+__device__ __forceinline__ void lds_zero(MeasureLds<ROWS>& l) {
+    double* a = &l.acc[0][0];
+    for (int i = threadIdx.x; i < kMeasureWaves * ROWS; i += kMeasureThreads) a[i] = 0.0;
+    __syncthreads();
+}
+// partials[k * pstride + slot] = the workgroup's sum for row k < rows, the waves added in wave order.
+template <int ROWS>
+__device__ __forceinline__ void lds_flush(MeasureLds<ROWS>& l, int rows, double* partials, int64_t pstride, int64_t slot) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < rows; k += kMeasureThreads) {
+        double a = l.acc[0][k];
+#pragma unroll
+        for (int w = 1; w < kMeasureWaves; ++w) a += l.acc[w][k];
+        partials[(int64_t)k * pstride + slot] = a;
+    }
+}
+
 // Element-type traits: a lane owns 16 bytes of every input bucket.
 template <typename T> struct In;
 template <> struct In<float> {

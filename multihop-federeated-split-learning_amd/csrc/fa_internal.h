@@ -122,6 +122,18 @@ constexpr int64_t kClipMaxBlocks = 2048;  // 8 workgroups per CU on 256 CUs; til
 constexpr int64_t kClipMaxPartials = kClipMaxBlocks + 1;  // per client: the grid's, plus one for head and tail
 hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const float* ref, const Split& sp,
                              double* partials, double* sums, const Tuning& tu, hipStream_t s);
+// The second launch of a measure pass (fa_clip.hip; shared with fa_geomed.hip): sums[r] = the np partials of row r <
+// rows, stored np apart, one wave per row, lane l adding partials l, l + 64, ... in ascending order.
+hipError_t launch_measure_finish(const double* partials, int64_t np, int rows, double* sums, hipStream_t s);
+// The geomed stage's fused Weiszfeld pass (fa.h "Geomed stage", rule 1), fa_geomed.hip.  Per element v_i = the
+// FA_FEDAVG chain over clients t.src[0..nc) with weights t.w, 1 <= nc <= kMaxClients, held in registers; sums[k] =
+// Q_k = sum_i ((double)fl32(x_{k,i} - v_i))^2 and sums[nc + k] = B_k = the count of elements of client k that are
+// NaN or +-inf, over the n elements.  The buckets are read once; v is stored only if v_out (fp32, n elements) is
+// given.  One launch writes one fp64 partial per (row, workgroup) into `partials` (room for 2 nc *
+// kClipMaxPartials doubles, laid out as the clip pass's), launch_measure_finish adds them.  No atomics.  sp: the
+// Split (fa_split.h) led by the first client, v_out required as well if given.
+hipError_t launch_geomed_pass(const ClientTable& t, int nc, fa_dtype in, float* v_out, const Split& sp, double* partials,
+                              double* sums, const Tuning& tu, hipStream_t s);
 // dst[i] = src[i] widened to fp32 exactly (the part's output into its reference; signed zeros kept).
 hipError_t launch_clip_widen(const void* src, fa_dtype dt, float* dst, int64_t n, hipStream_t s);
 // The Krum stage's distance pass (fa.h "Krum stage", rule 1), fa_krum.hip.  dist (device, D * D doubles, row-major)

@@ -32,6 +32,9 @@
 // norm of C before the FedAvg chain (fa.h "Clip stage"); --clip-state FILE carries that model across restarts.
 // --krum-f F [--krum-m M] averages, per bucket, only the M owners (default D - F) whose receipts lie closest to
 // the others' (Krum / Multi-Krum, fa.h "Krum stage"); the stage keeps no state across rounds.
+// --geomed-iters T [--geomed-nu NU] replaces, per bucket, the weighted mean by the weighted geometric median of the
+// owners' receipts, found by T smoothed Weiszfeld passes (RFA, fa.h "Geomed stage"): nobody is left out, an owner far
+// from the others is down-weighted; the stage keeps no state across rounds.
 // --mode bulyan --bulyan-f F picks, per bucket, D - 2F owners by iterated Krum and averages per element the picked
 // values closest to their median (fa.h "Bulyan stage"); the stage keeps no state across rounds.
 // --dp-noise-multiplier Z (with --clip-norm C) adds Gaussian noise of stddev Z C max_k w_k to every bucket's clipped
@@ -110,6 +113,11 @@ struct Options {
     // defined); M defaults to DATA_OWNERS - F
     int krum_f = 0, krum_m = -1;
     bool krum_given = false, krum_m_given = false;
+    // --geomed-iters T [--geomed-nu NU]: the geomed stage of every bucket (fa_set_geomed on the context, before any
+    // bucket is defined); NU defaults to 1e-6
+    int geomed_iters = 0;
+    float geomed_nu = 1e-6f;
+    bool geomed_given = false, geomed_nu_given = false;
     // --dp-noise-multiplier Z [--dp-seed S]: the noise stage of every bucket (fa_set_noise on the context, before any
     // bucket is defined) with stddev = Z * C * max_k w_k, C the --clip-norm; the seed comes from the operating
     // system's entropy at every start unless --dp-seed fixes it
@@ -259,6 +267,7 @@ void usage() {
                  "        [--server-tau T] [--server-state FILE]]\n"
                  "       [--clip-norm C [--clip-state FILE]]\n"
                  "       [--krum-f F [--krum-m M]]\n"
+                 "       [--geomed-iters T [--geomed-nu NU]]\n"
                  "       [--dp-noise-multiplier Z [--dp-seed S]]\n"
                  "--mode trimmed: per element the T lowest and T highest of the owners' values are dropped and the\n"
                  "rest averaged (2T < DATA_OWNERS <= 128; without --trim, and with --mode median, the median), so up\n"
@@ -267,7 +276,8 @@ void usage() {
                  "--mode bulyan --bulyan-f F: per bucket DATA_OWNERS - 2F owners are picked by running Krum repeatedly\n"
                  "over the owners' pairwise distances, then per element the picked values closest to their median are\n"
                  "averaged (all but 2F of them): F is the number of owners assumed Byzantine, 0 <= F, 4F + 3 <=\n"
-                 "DATA_OWNERS <= 128; --samples is ignored; not with --trim, --clip-norm, --krum-f or --layout rs.\n"
+                 "DATA_OWNERS <= 128; --samples is ignored; not with --trim, --clip-norm, --krum-f, --geomed-iters or\n"
+                 "--layout rs.\n"
                  "--server-opt: a server optimizer (FedAvgM, FedAdagrad, FedAdam, FedYogi) steps the global model with\n"
                  "the round's aggregate; the model and its moments stay on the GPU in fp32; L finite and >= 0, B in\n"
                  "[0, 1) (defaults 0.9 and 0.99), T finite and > 0 (default 1e-3); --server-state FILE is read at startup\n"
@@ -282,6 +292,11 @@ void usage() {
                  "lie closest to the others' are averaged, with their own weights scaled up to the round's mass; F is\n"
                  "the number of owners assumed Byzantine, 0 <= F, 2F + 2 < DATA_OWNERS <= 128, 1 <= M <= DATA_OWNERS - F;\n"
                  "not with --clip-norm, --mode literal|trimmed|median or --layout rs.\n"
+                 "--geomed-iters T: per bucket the owners' weighted geometric median instead of their weighted mean, by T\n"
+                 "smoothed Weiszfeld passes (RFA): an owner is down-weighted by its distance from the running estimate,\n"
+                 "with NU (--geomed-nu, default 1e-6, finite and > 0) as the floor on a distance; nobody is left out but\n"
+                 "an owner that sends a NaN or an inf; 1 <= T <= 64, DATA_OWNERS <= 128; not with --clip-norm, --krum-f,\n"
+                 "--mode literal|trimmed|median|bulyan or --layout rs.\n"
                  "--dp-noise-multiplier Z (with --clip-norm C): Gaussian noise of standard deviation Z * C * max_k w_k (w_k\n"
                  "the round's weights: the sensitivity of the clipped weighted sum to one owner) is added to every bucket's\n"
                  "aggregate before it is stepped or replied: DP-FedAvg.  The seed is drawn from the operating system at\n"
@@ -378,6 +393,12 @@ bool parse_args(int argc, char** argv, Options* o) {
         } else if (a == "--krum-m") {
             o->krum_m = std::atoi(val("--krum-m"));
             o->krum_m_given = true;
+        } else if (a == "--geomed-iters") {
+            o->geomed_iters = std::atoi(val("--geomed-iters"));
+            o->geomed_given = true;
+        } else if (a == "--geomed-nu") {
+            o->geomed_nu = (float)std::atof(val("--geomed-nu"));
+            o->geomed_nu_given = true;
         } else if (a == "--dp-noise-multiplier") {
             o->dp_z = std::atof(val("--dp-noise-multiplier"));
             o->dp_given = true;
@@ -551,6 +572,37 @@ bool parse_args(int argc, char** argv, Options* o) {
             return false;
         }
     }
+    if (!o->geomed_given && o->geomed_nu_given) {
+        std::cerr << "--geomed-nu goes with --geomed-iters\n";
+        return false;
+    }
+    if (o->geomed_given) {
+        if (o->clip_given || o->krum_given) {
+            std::cerr << "--geomed-iters and " << (o->clip_given ? "--clip-norm" : "--krum-f") << " do not compose: one of them\n";
+            return false;
+        }
+        if (o->mode != FA_FEDAVG) {
+            std::cerr << "--geomed-iters re-weights the owners of a weighted average: not with --mode "
+                      << (o->mode == FA_LITERAL ? "literal" : o->bulyan ? "bulyan" : o->median ? "median" : "trimmed") << "\n";
+            return false;
+        }
+        if (o->rs) {
+            std::cerr << "--geomed-iters needs every owner's value of an element on one GPU: not with --layout rs\n";
+            return false;
+        }
+        if (o->data_owners > FA_GEOMED_MAX_CLIENTS) {
+            std::cerr << "--geomed-iters takes at most " << FA_GEOMED_MAX_CLIENTS << " data owners\n";
+            return false;
+        }
+        if (o->geomed_iters < 1 || o->geomed_iters > FA_GEOMED_MAX_ITERS) {
+            std::cerr << "--geomed-iters " << o->geomed_iters << ": 1 <= T <= " << FA_GEOMED_MAX_ITERS << "\n";
+            return false;
+        }
+        if (!std::isfinite(o->geomed_nu) || !(o->geomed_nu > 0)) {
+            std::cerr << "--geomed-nu " << o->geomed_nu << ": finite and > 0\n";
+            return false;
+        }
+    }
     return o->data_owners >= 1 && o->stall_report_s > 0 && o->receipt_timeout_s >= 0;
 }
 
@@ -604,6 +656,7 @@ public:
         if (o.server.rule != FA_OPT_NONE) FA_CHECK(fa_set_server_opt(ctx_, -1, &o.server));  // before any bucket
         if (o.clip_given) FA_CHECK(fa_set_clip(ctx_, -1, o.clip_norm));
         if (o.krum_given) FA_CHECK(fa_set_krum(ctx_, -1, o.krum_f, o.krum_m));
+        if (o.geomed_given) FA_CHECK(fa_set_geomed(ctx_, -1, o.geomed_iters, o.geomed_nu));
         if (o.rs_chunks > 0) {
             fa_tuning t{};
             t.rs_chunks = o.rs_chunks;
@@ -881,6 +934,20 @@ public:
                 std::cerr << "[aggregator] KRUM: part " << mp << ": NO OWNER SELECTED (every score is infinite): the "
                           << "reply of this bucket is all zeros\n";
         }
+        if (o_.geomed_given) {  // what the geomed stage made of this bucket's receipts, for the round line
+            const size_t D = (size_t)o_.data_owners;
+            GeomedRound& gr = geomed_[mp];
+            std::vector<double> q((size_t)FA_GEOMED_MAX_ITERS * D, 0.0);
+            std::vector<float> w((size_t)(FA_GEOMED_MAX_ITERS + 1) * D, 0.0f);
+            gr.included.assign(D, 0);
+            FA_CHECK(fa_geomed_get_round(ctx_, mp, &gr.passes, q.data(), w.data(), gr.included.data(), nullptr));
+            const size_t last = gr.passes > 0 ? (size_t)gr.passes - 1 : 0;
+            gr.sumsq.assign(q.begin() + (ptrdiff_t)(last * D), q.begin() + (ptrdiff_t)((last + 1) * D));
+            gr.weights.assign(w.begin() + (ptrdiff_t)((size_t)gr.passes * D), w.begin() + (ptrdiff_t)(((size_t)gr.passes + 1) * D));
+            if (std::find(gr.included.begin(), gr.included.end(), 1) == gr.included.end())
+                std::cerr << "[aggregator] GEOMED: part " << mp << ": NO OWNER LEFT (every weight is zero or every "
+                          << "receipt holds a NaN or an inf): the reply of this bucket is all zeros\n";
+        }
         if (o_.bulyan) {  // whom the Bulyan stage picked for this bucket, for the round line
             std::vector<int>& sel = bulyan_[mp];
             sel.assign((size_t)o_.data_owners, 0);
@@ -1007,6 +1074,54 @@ public:
         }
         os << "}";
         bulyan_.clear();
+        return os.str();
+    }
+
+    // --geomed-iters: the round line's tail -- T and NU, the owners' ids in slot order once, and per bucket the valid
+    // passes, the ids of the owners excluded, the last pass's squared distances (17 significant digits: they read back
+    // to the same doubles; 0 for an excluded owner) and the final chain's weights (9 digits: the same floats).
+    std::string geomed_tail() {
+        std::ostringstream os;
+        char buf[64];
+        snprintf(buf, sizeof buf, "%.9g", (double)o_.geomed_nu);
+        os << ",\"geomed_iters\":" << o_.geomed_iters << ",\"geomed_nu\":" << buf << ",\"geomed_owners\":[";
+        for (size_t k = 0; k < expected_.size(); ++k) os << (k ? "," : "") << expected_[k];
+        os << "]";
+        for (int what = 0; what < 4; ++what) {
+            os << (what == 0 ? ",\"geomed_passes\":{" : what == 1 ? ",\"geomed_excluded\":{" : what == 2 ? ",\"geomed_sumsq\":{"
+                                                                                                      : ",\"geomed_weights\":{");
+            bool first = true;
+            for (auto& kv : geomed_) {
+                os << (first ? "" : ",") << "\"" << kv.first << "\":";
+                first = false;
+                if (what == 0) {
+                    os << kv.second.passes;
+                    continue;
+                }
+                os << "[";
+                bool lead = true;
+                for (size_t k = 0; k < kv.second.included.size(); ++k) {
+                    if (what == 1) {
+                        if (kv.second.included[k]) continue;
+                        os << (lead ? "" : ",") << expected_[k];
+                    } else if (what == 2) {
+                        const double v = kv.second.sumsq[k];
+                        if (std::isfinite(v)) snprintf(buf, sizeof buf, "%.17g", v);
+                        else snprintf(buf, sizeof buf, "\"%s\"", std::isnan(v) ? "nan" : "inf");
+                        os << (lead ? "" : ",") << buf;
+                    } else {
+                        const double v = (double)kv.second.weights[k];
+                        if (std::isfinite(v)) snprintf(buf, sizeof buf, "%.9g", v);
+                        else snprintf(buf, sizeof buf, "\"%s\"", std::isnan(v) ? "nan" : "inf");
+                        os << (lead ? "" : ",") << buf;
+                    }
+                    lead = false;
+                }
+                os << "]";
+            }
+            os << "}";
+        }
+        geomed_.clear();
         return os.str();
     }
 
@@ -1224,6 +1339,15 @@ private:
         std::vector<int> selected;
     };
     std::map<int, KrumRound> krum_;
+    // --geomed-iters: this round's valid passes, final flags, last-pass distances and final weights of each bucket, in
+    // slot order (geomed_tail)
+    struct GeomedRound {
+        int passes = 0;
+        std::vector<int> included;
+        std::vector<double> sumsq;
+        std::vector<float> weights;
+    };
+    std::map<int, GeomedRound> geomed_;
     std::map<int, std::vector<int>> bulyan_;  // --mode bulyan: this round's pick flags of each bucket, in slot order
     std::map<int, int> slots_;  // client id -> slot
     std::vector<char> claimed_;  // slot -> an arrived client holds it
@@ -1419,7 +1543,7 @@ int main(int argc, char** argv) {
             server_tail = buf;
         }
         const std::string clip_tail =
-            (o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : o.bulyan ? agg.bulyan_tail() : std::string()) + (o.dp_given ? agg.dp_tail() : std::string());
+            (o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : o.geomed_given ? agg.geomed_tail() : o.bulyan ? agg.bulyan_tail() : std::string()) + (o.dp_given ? agg.dp_tail() : std::string());
         printf("{\"round\":%d,\"phase1\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f},"
                "\"phase2\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,\"layers\":%d,"
