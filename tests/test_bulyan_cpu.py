@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import bulyan_ref as B
+import sort_cols as S
 import trimmed_ref as T
 
 F32, F64 = np.float32, np.float64
@@ -121,6 +122,37 @@ def test_a_16_bit_output_is_rounded_once():
     xs = [np.asarray([1.0], F32), np.asarray([1.0 + 2.0 ** -8], F32), np.asarray([1.0 + 2.0 ** -7], F32)]
     assert B.centered(xs, 3, "f32", "bf16").tolist() == T.f32_to_bf16(B.centered_f32(xs, 3)[0]).tolist()
     assert B.centered(xs, 3, "f32", "f16").dtype == np.float16
+
+
+# ------------------------------------------------------------------ rule 4 on the structured columns (sort_cols.py)
+
+@pytest.mark.parametrize("theta", S.SLIDE_THETAS)
+def test_slide_columns_reach_every_window_start_and_no_other(theta):
+    """Through the j the helper returns: at every keep the GPU module runs (all of 1..theta), column `target`
+    starts at min(target, theta - keep), so the starts are exactly 0..min(theta - keep, (theta - 1) // 2)."""
+    x, target = S.slide_columns(theta)
+    assert sorted(set(target.tolist())) == list(range((theta - 1) // 2 + 1))
+    for kind in ("bf16", "f16"):  # the 16-bit runs see the same values
+        assert bits32(B.widen(B.round_out(x.ravel(), kind), kind)) == bits32(x.ravel())
+    for keep in range(1, theta + 1):
+        _, j = B.centered_f32(list(x), keep)
+        assert np.array_equal(j, np.minimum(target, theta - keep)), (theta, keep)
+        assert sorted(set(j.tolist())) == S.slide_targets(theta, keep), (theta, keep)
+
+
+def test_slide_targets_by_hand():
+    assert S.slide_targets(7, 7) == [0] and S.slide_targets(7, 5) == [0, 1, 2] and S.slide_targets(7, 1) == [0, 1, 2, 3]
+    assert S.slide_targets(64, 1) == list(range(32)) and S.slide_targets(64, 40) == list(range(25))
+    assert one([-1024, 1, -1032, 1, 1, 1, 1], 3) == (F32(1.0), 2)
+
+
+@pytest.mark.parametrize("D", [5, 16, 23, 64, 65, 128])
+def test_two_valued_columns_with_keep_theta_have_the_trim_0_closed_form(D):
+    mask, z = S.zero_one(D)
+    for pair in S.PAIRS01:
+        r, j = B.centered_f32(list(S.values(mask, pair)), D)
+        assert not j.any()
+        T.assert_bits(r, S.closed_form(D, 0, z, pair), "D %d %s" % (D, pair))
 
 
 # ------------------------------------------------------------------ rule 2: the helper and fa_bulyan_select

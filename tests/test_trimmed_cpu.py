@@ -6,6 +6,7 @@ the library through its constants, fa_version and the no-device probe (fa_trimme
 import numpy as np
 import pytest
 
+import sort_cols as S
 import trimmed_ref as T
 
 F32 = np.float32
@@ -86,6 +87,72 @@ def test_helper_16_bit_types():
     b = [np.array([0x3F80], np.uint16), np.array([0x4040], np.uint16)]
     assert T.trimmed(b, 0, in_bf16=True, out="bf16")[0] == 0x4000
     assert T.f32_to_bf16(np.array([1.00390625], F32))[0] == 0x3F80  # tie to even
+
+
+# ------------------------------------------------------------------ the structured columns (tests/sort_cols.py)
+
+def test_the_column_families_hold_what_they_name():
+    assert 16 in S.DS_EXHAUSTIVE and {2, 4, 8}.issubset(S.DS_EXHAUSTIVE)
+    assert {23, 32, 47, 64}.issubset(S.DS_NETWORK) and {65, 66, 96, 127, 128}.issubset(S.DS_WIDE)
+    for D in (1, 2, 5, 16):  # every pattern once
+        m = S.exhaustive(D)
+        assert m.shape == (D, 1 << D) and np.unique(m, axis=1).shape[1] == 1 << D
+    for D in (23, 64):
+        m = S.few(D)
+        z = m.sum(axis=0)
+        pairs = D * (D - 1) // 2
+        assert m.shape[1] == 2 * (1 + D + pairs) == np.unique(m, axis=1).shape[1]
+        assert [(z == v).sum() for v in (0, 1, 2, D - 2, D - 1, D)] == [1, D, pairs, pairs, D, 1]
+        p = S.permutations(D, S.n_perms(D))
+        assert all(sorted(p[:, r].tolist()) == list(range(D)) for r in range(p.shape[1]))
+        th = S.thresholds(p)
+        assert th.shape == (D, p.shape[1] * (D + 1))
+        assert th.sum(axis=0).tolist() == list(range(D + 1)) * p.shape[1]
+        assert np.array_equal(th[:, 5], p[:, 0] < 5)
+    for D in S.DS_WIDE:  # every split of the lows between the halves, once
+        m = S.wide_split(D)
+        got = sorted(zip(m[:64].sum(axis=0).tolist(), m[64:].sum(axis=0).tolist()))
+        assert got == [(a, b) for a in range(65) for b in range(D - 64 + 1)]
+    for D in S.DS_EXHAUSTIVE + S.DS_NETWORK + S.DS_WIDE:
+        m, z = S.zero_one(D)
+        assert m.shape[1] % 8 == 3 and m.shape[1] < (1 << 16) + 8 and np.array_equal(z, m.sum(axis=0))
+        for t in S.trims_for(D):
+            assert t == T.TRIM_MEDIAN or 2 * t < D
+    assert S.trims_for(128) == [0, 1, 2, 31, 62, 63, T.TRIM_MEDIAN] and S.trims_for(5) == [0, 1, 2, T.TRIM_MEDIAN]
+
+
+@pytest.mark.parametrize("D", S.DS_EXHAUSTIVE + S.DS_NETWORK + S.DS_WIDE)
+def test_closed_form_of_the_two_valued_columns_is_the_helper(D):
+    """The closed form needs no sort; the helper sorts.  Every family, every pair, every trim (the GPU module runs
+    them all on these columns)."""
+    mask, z = S.zero_one(D)
+    assert set(S.trims_for(D)) <= set(range((D - 1) // 2 + 1)) | {T.TRIM_MEDIAN}
+    for pair in S.PAIRS01:
+        xs = list(S.values(mask, pair))
+        for trim in list(range((D - 1) // 2 + 1)) + [T.TRIM_MEDIAN]:
+            cf = S.closed_form(D, trim, z, pair)
+            assert cf.dtype == F32
+            T.assert_bits(cf, T.trimmed_f32(xs, trim), "D %d %s trim %d" % (D, pair, trim))
+            if pair == "nan":  # NaN exactly where a high is kept, 1.0 elsewhere
+                t = T.resolve(trim, D)
+                assert np.array_equal(np.isnan(cf), z < D - t) and np.all(cf[z >= D - t] == 1.0)
+
+
+def test_closed_form_by_hand():
+    # D = 5, trim 1: the window holds sorted positions 1..3
+    z = np.arange(6)
+    assert S.closed_form(5, 1, z, "01").tolist() == [1.0, 1.0, F32(2) / F32(3), F32(1) / F32(3), 0.0, 0.0]
+    assert S.closed_form(5, 1, z, "pm1").tolist() == [1.0, 1.0, F32(1) / F32(3), F32(-1) / F32(3), -1.0, -1.0]
+    assert np.isnan(S.closed_form(5, 1, z, "nan")).tolist() == [True, True, True, True, False, False]
+    assert S.closed_form(4, 1, [2], "pm1").view(np.uint32).tolist() == [0]  # -1 + 1 = +0
+    assert S.closed_form(128, T.TRIM_MEDIAN, [63, 64, 65], "01").tolist() == [1.0, 0.5, 0.0]
+
+
+def test_the_structured_values_are_exact_in_16_bits():
+    for D in (16, 128):
+        for x in (S.perm_values(D), S.slide_columns(D)[0], S.values(S.zero_one(D)[0], "pm1")):
+            assert np.array_equal(T.bf16_to_f32(T.f32_to_bf16(x.ravel())), x.ravel())
+            assert np.array_equal(x.astype(np.float16).astype(F32), x)
 
 
 # ------------------------------------------------------------------ the library, no device
