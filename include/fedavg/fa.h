@@ -270,6 +270,39 @@
  *              cryptographic generator: the privacy of the result rests on the seed staying secret and on a
  *              (seed, stream, round) triple never being used twice.  Added without a new FA_ABI_VERSION:
  *              fa_noise_device with n == 0 touches no device and answers FA_OK -- that is how a caller probes for it.
+ *   MX8 receipts (fa_set_mx8, fa_submit_mx8, fa_mx8_expand_device, fa_mx8_encode, fa_mx8_decode): a client sends
+ *              its update x_k - g against the model g it was last sent, as 8-bit integers with one power-of-two
+ *              scale per 32 elements (the MXINT8 layout): 33 bytes per 32 elements where fp32 takes 128.  The
+ *              compressed bytes cross the wire and PCIe; a kernel rebuilds the ordinary slot x = g + d, and
+ *              everything downstream (every mode, stage, layout) sees an ordinary receipt.
+ *              Format.  A compressed bucket of n elements is two arrays: q, n bytes, q_i an int8 in two's
+ *              complement, all 256 codes valid; e, ceil(n / 32) bytes, e_b the scale of block b = elements
+ *              [32 b, 32 b + 32).  The block of element i is i >> 5 with i the element's index in the whole
+ *              bucket, never the index within a shard or a piece.
+ *              Decode (fa_mx8_decode; the kernel does the same steps):
+ *              1. If E = e_b is 255, every d_i of the block is a quiet NaN (payload unspecified).
+ *              2. Otherwise s = 2^(E - 133) and d_i = fl32((float)q_i * s), one IEEE fp32 multiply.  s is an fp32
+ *                 value for every E in 0 .. 254, subnormal below E = 7; subnormals are kept.  The product is exact
+ *                 for every (q, E) but one: q = -128 at E = 254 is -2^128 and rounds to -inf.
+ *              3. Expansion into a slot of dtype `in` against a reference of dtype `ref`:
+ *                 x_i = fl32(widen(g_i) + d_i), one rounding, g widened exactly (bf16; fp16 with its subnormals).  A
+ *                 16-bit slot stores x_i rounded once more to nearest-even, as every 16-bit output here.  Without
+ *                 a reference (absolute mode) x_i = d_i, rounded the same way for a 16-bit slot.  NaN and inf in g
+ *                 propagate; -0 + +0 is +0.  (slot, ref) pairs are the (in, out) pairs below.
+ *              Encode (fa_mx8_encode, pure host arithmetic, the owner's side).  Per block, over its (at most 32)
+ *              fp32 deltas:
+ *              1. If any is NaN or +-inf: E = 255, every q = 0.
+ *              2. m = max |delta|.  If m is 0: E = 0, every q = 0.
+ *              3. Otherwise m = f 2^k with f in [0.5, 1) (frexp); t = k - 7 if f <= 127/128, else k - 6: the
+ *                 smallest t with m 2^-t <= 127.  E = min(max(t + 133, 0), 254) and t = E - 133.
+ *                 q_i = clamp(rint(delta_i 2^-t), -127, 127), computed in fp64 where the scaling is exact, ties to
+ *                 even.  The encoder never emits -128.
+ *              4. Error: for a block without E = 255, |delta_i - d_i| <= max(m / 127, 2^-134): the minimal t makes
+ *                 the step below 2 m / 127, and saturation at E = 254 costs less than m / 128.
+ *              5. Rounding to nearest is the library's encoder.  An owner may round stochastically: any (q, e) is
+ *                 valid input to the decoder.
+ *              Added without a new FA_ABI_VERSION: fa_mx8_expand_device with n == 0 touches no device and answers
+ *              FA_OK -- that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -729,6 +762,53 @@ int fa_noise_device(fa_ctx* ctx, int gpu, const float* d_avg, size_t n, void* d_
  * idx0 + n - 1 under (seed, stream, round), the bits the kernel adds (built without contraction: also on a host
  * with FMA units).  To audit a round: out == fl(a + fl(stddev z)). */
 int fa_noise_host(uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, size_t n, float* z);
+
+/* MX8 receipts (the header comment, "MX8 receipts"): block-scaled int8 updates, expanded on the GPU. */
+#define FA_MX8_BLOCK 32
+/* ceil(n / 32): the bytes of e for a bucket of n elements. */
+size_t fa_mx8_scale_bytes(size_t n);
+/* The library's encoder, pure host arithmetic, usable without a device: the n fp32 deltas into q (n bytes) and e
+ * (fa_mx8_scale_bytes(n) bytes), block b = elements [32 b, 32 b + 32). */
+int fa_mx8_encode(const float* delta, size_t n, int8_t* q, uint8_t* e);
+/* The decoder, pure host arithmetic: d[i] = the delta of bucket element idx0 + i, q[i] its code and e[0] the scale of
+ * block idx0 >> 5 (e holds the scales of blocks idx0 >> 5 .. (idx0 + n - 1) >> 5).  The kernel's own arithmetic. */
+int fa_mx8_decode(const int8_t* q, const uint8_t* e, size_t n, uint64_t idx0, float* d);
+/* Decode rule 3 on raw device pointers: d_dst[i] (n of dst_dtype) = fl(widen(d_ref[i]) + d_i), or d_i with d_ref NULL
+ * (absolute mode), d_q, d_e and idx0 as for fa_mx8_decode, on device `gpu`.  ctx may be NULL (then `gpu` is the HIP
+ * device).  Every argument is checked before any device call: the dtypes and their pair ((dst, ref) as (in, out)),
+ * idx0 + n < 2^64, and for n > 0 null pointers and element alignment of d_ref and d_dst (FA_ERR_ALIGN); with n == 0
+ * and valid arguments it returns FA_OK without touching a device.  Any byte phase of d_q and d_e and any element
+ * phase of d_ref and d_dst is correct; 16-byte loads and stores are used where the three phases allow a common
+ * head.  d_dst must not overlap d_ref.  Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null
+ * stream). */
+int fa_mx8_expand_device(fa_ctx* ctx, int gpu, const int8_t* d_q, const uint8_t* d_e, size_t n, uint64_t idx0,
+                         const void* d_ref, fa_dtype ref_dtype, void* d_dst, fa_dtype dst_dtype, void* hip_stream);
+/* Lets a part take MX8 receipts (part_id >= 0), or sets the context default for parts defined later (part_id < 0;
+ * FA_LITERAL parts ignore it).  A part with it on keeps its device output as the reference g across rounds -- what
+ * the last reducing call left there, after a server optimizer or the noise stage the stepped, noisy output: the
+ * model the owners were sent -- is never kept host-side (fa_bucket_host_read says 0) and is left non-eager by
+ * FA_ACCUMULATE_ON_ARRIVAL.  FA_ERR_ARG, naming the cause: an FA_LITERAL part, an FA_SHARD_CLIENT_RS context (a GPU
+ * holding a whole slot does not hold the matching output).  Everything else composes, in any call order: FA_FEDAVG,
+ * FA_TRIMMED, every stage, the server optimizers, range shards, range pieces, fa_reduce_parts.  on == 0 frees what it
+ * allocated.  Memory: per GPU and client slot a shadow of cnt bytes (cnt the GPU's elements of the bucket; rounded up
+ * to 16) plus the scale bytes of the blocks they touch, rounded up to 256, allocated at the part's first fa_submit_mx8 -- about 1/3.9 of an fp32 part's slots
+ * on top of them; it keeps a submit fully asynchronous. */
+int fa_set_mx8(fa_ctx* ctx, int part_id, int on);
+/* An MX8 receipt of client `client_slot`: q (n bytes) and e (fa_mx8_scale_bytes(n) bytes).  flags: FA_HOST_PINNED = q
+ * and e are pinned and stay unchanged until fa_finalize* returns, the DMA runs from them; without it they go through
+ * the pinned staging chunks and are reusable on return.  FA_MX8_ABSOLUTE = absolute mode (x = d).  Enqueues the H2D of
+ * each GPU's bytes of q and of the scale bytes its element range touches, then the expansion into the slot, piece by
+ * piece on a part held in pieces, ordered after the part's last reducing call and before the next.  The slot then
+ * counts as the client's receipt exactly as after fa_submit (weight, overwriting, fa_bucket_progress).  The reference
+ * of a relative submit is the part's device output as the last reducing call left it; FA_ERR_STATE, naming the part,
+ * when there is none (the part was never reduced, or fa_set_mx8 was not on when it was, and no
+ * fa_mx8_set_reference).  FA_ERR_STATE on a part without fa_set_mx8. */
+#define FA_MX8_ABSOLUTE 0x2
+int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags);
+/* Writes the part's device output on every GPU from host_src (n elements of the out dtype), as if a round had
+ * produced it: the reference of the next relative submits (a restarted aggregator; tests).  Waits for the part's
+ * pending work.  FA_ERR_STATE on a part without fa_set_mx8. */
+int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

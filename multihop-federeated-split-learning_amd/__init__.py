@@ -118,6 +118,13 @@ def lib():
         "fa_noise_set_round": (I, [P, I, U64]),
         "fa_noise_device": (I, [P, I, P, S, P, I, F, U64, U32, U32, U64, P]),
         "fa_noise_host": (I, [U64, U32, U32, U64, S, P]),
+        "fa_mx8_scale_bytes": (S, [S]),
+        "fa_mx8_encode": (I, [P, S, P, P]),
+        "fa_mx8_decode": (I, [P, P, S, U64, P]),
+        "fa_mx8_expand_device": (I, [P, I, P, P, S, U64, P, I, P, I, P]),
+        "fa_set_mx8": (I, [P, I, I]),
+        "fa_submit_mx8": (I, [P, I, I, P, P, F, I]),
+        "fa_mx8_set_reference": (I, [P, I, P]),
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
         "fa_submit_gather": (I, [P, I, I, I, P, P, F]),
@@ -408,6 +415,43 @@ def noise_host(seed, stream_id, round, idx0, n):
     z = np.empty(n, np.float32)
     check(lib().fa_noise_host(int(seed), int(stream_id), int(round), int(idx0), n, z.ctypes.data))
     return z
+
+
+MX8_BLOCK = 32  # FA_MX8_BLOCK: elements per scale byte of an MX8 receipt (fa.h "MX8 receipts")
+MX8_ABSOLUTE = 0x2  # FA_MX8_ABSOLUTE
+
+
+def mx8_scale_bytes(n):
+    """fa_mx8_scale_bytes: ceil(n / 32)."""
+    return lib().fa_mx8_scale_bytes(n)
+
+
+def mx8_encode(delta):
+    """fa_mx8_encode (host arithmetic, the owner's side): the fp32 deltas as (q int8[n], e uint8[ceil(n / 32)])."""
+    delta = np.ascontiguousarray(np.asarray(delta, np.float32).reshape(-1))
+    q, e = np.empty(delta.size, np.int8), np.empty(mx8_scale_bytes(delta.size), np.uint8)
+    check(lib().fa_mx8_encode(delta.ctypes.data, delta.size, q.ctypes.data, e.ctypes.data))
+    return q, e
+
+
+def mx8_decode(q, e, idx0=0):
+    """fa_mx8_decode (host arithmetic): the fp32 deltas of bucket elements idx0 .. idx0 + len(q) - 1; e[0] is the
+    scale of block idx0 >> 5."""
+    q = np.ascontiguousarray(np.asarray(q, np.int8).reshape(-1))
+    e = np.ascontiguousarray(np.asarray(e, np.uint8).reshape(-1))
+    if q.size and e.size < ((idx0 + q.size - 1) >> 5) - (idx0 >> 5) + 1:
+        raise ValueError("e holds %d scales, elements [%d, %d) touch more blocks" % (e.size, idx0, idx0 + q.size))
+    d = np.empty(q.size, np.float32)
+    check(lib().fa_mx8_decode(q.ctypes.data, e.ctypes.data, q.size, int(idx0), d.ctypes.data))
+    return d
+
+
+def mx8_expand_device(q, e, n, dst, dst_dtype=F32, ref=None, ref_dtype=F32, idx0=0, stream=None, gpu=0, ctx=None):
+    """fa_mx8_expand_device: dst[i] = ref[i] + d_i over n device-resident elements (ref None: absolute mode, dst[i] =
+    d_i), q / e / idx0 as for mx8_decode, device pointers of any byte (q, e) or element (ref, dst) phase.  Enqueued,
+    not synchronized.  With n == 0 no device is touched: the feature probe."""
+    check(lib().fa_mx8_expand_device(ctx.handle if ctx is not None else None, gpu, _addr(q), _addr(e), n, int(idx0),
+                                     _addr(ref), ref_dtype, _addr(dst), dst_dtype, _stream(stream)))
 
 
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
@@ -774,6 +818,36 @@ class Aggregator:
             raise ValueError("bucket %d expects %d bytes, got %d" % (part_id, n * DTYPE_SIZE[in_dtype], host.nbytes))
         fn = lib().fa_submit_pinned if pinned else lib().fa_submit
         check(fn(self.handle, part_id, slot, host.ctypes.data, float(weight)))
+
+    def set_mx8(self, on=True, part_id=-1):
+        """fa_set_mx8: the part takes MX8 receipts and keeps its device output as their reference (part_id < 0: the
+        default of parts defined later); on=False frees what it allocated."""
+        check(lib().fa_set_mx8(self.handle, part_id, 1 if on else 0))
+
+    def submit_mx8(self, part_id, slot, q, e, weight=1.0, pinned=False, absolute=False):
+        """fa_submit_mx8: the client's update against the part's last output as (q int8[n], e uint8[ceil(n / 32)]),
+        expanded into the slot on the GPU.  pinned: views of PinnedBuffers the caller keeps unchanged until finalize
+        returns.  absolute: the values themselves, no reference."""
+        q, e = np.ascontiguousarray(q), np.ascontiguousarray(e)
+        if q.dtype != np.int8 or e.dtype != np.uint8:
+            raise ValueError("need q int8 and e uint8")
+        if part_id in self.parts:
+            n = self.parts[part_id][0]
+            if q.size != n or e.size != mx8_scale_bytes(n):
+                raise ValueError("bucket %d expects %d codes and %d scales, got %d and %d"
+                                 % (part_id, n, mx8_scale_bytes(n), q.size, e.size))
+        flags = (HOST_PINNED if pinned else 0) | (MX8_ABSOLUTE if absolute else 0)
+        check(lib().fa_submit_mx8(self.handle, part_id, slot, q.ctypes.data, e.ctypes.data, float(weight), flags))
+
+    def set_mx8_reference(self, part_id, g):
+        """fa_mx8_set_reference: the part's device output := g (n elements of the out dtype; bf16 as uint16 bits), the
+        reference of the next relative submits."""
+        g = np.ascontiguousarray(g)
+        if part_id in self.parts:
+            n, _, out_dtype = self.parts[part_id][:3]
+            if g.nbytes != n * DTYPE_SIZE[out_dtype]:
+                raise ValueError("bucket %d's output holds %d bytes, got %d" % (part_id, n * DTYPE_SIZE[out_dtype], g.nbytes))
+        check(lib().fa_mx8_set_reference(self.handle, part_id, g.ctypes.data))
 
     def submit_gather(self, part_id, slot, pieces, weight=1.0, pinned=False):
         """fa_submit_gather(_pinned): `pieces` (host arrays) concatenate to the bucket.  pinned: views of

@@ -379,6 +379,13 @@ struct Part {
     float noise = 0.0f;
     uint64_t noise_seed = 0;
     uint64_t noise_round = 0;
+    // MX8 receipts (fa.h "MX8 receipts"; fa_set_mx8).  mx8_ref: the device output holds a reference -- a reducing
+    // call left it there while mx8 was on, or fa_mx8_set_reference wrote it.  mx8_buf: per GPU the compressed
+    // shadows of its held slots, mx8_stride[g] bytes apart (q: cnt bytes, then from mx8_eoff[g] on the scale bytes
+    // of the blocks its range touches), one allocation at the part's first fa_submit_mx8.
+    bool mx8 = false, mx8_ref = false;
+    std::vector<char*> mx8_buf;
+    std::vector<size_t> mx8_stride, mx8_eoff;
 };
 
 // A part whose reducing calls are rounds of their own (a server-optimizer, clip, Krum, geomed, Bulyan or noise stage):
@@ -408,6 +415,7 @@ struct fa_ctx {
     int bulyan_f = -1;          // default Bulyan stage of trimmed parts defined later (< 0: none)
     float noise = 0.0f;         // default noise stage of FedAvg / trimmed parts defined later (0: none)
     uint64_t noise_seed = 0;
+    bool mx8 = false;           // parts defined later (not FA_LITERAL) take MX8 receipts
     CtxTuning tuning;
     std::vector<GpuRes> gpu;
     std::map<int, Part> parts;
@@ -1089,8 +1097,22 @@ void free_clip(fa_ctx* ctx, Part& p) {
     p.clip_reported = false;
 }
 
+// The compressed shadows go (hipFree waits for the device's pending work); the part takes full receipts only.
+void free_mx8(fa_ctx* ctx, Part& p) {
+    for (size_t g = 0; g < p.mx8_buf.size(); ++g) {
+        DeviceGuard dg(ctx->gpu[g].dev);
+        if (p.mx8_buf[g]) (void)hipFree(p.mx8_buf[g]);
+    }
+    p.mx8_buf.clear();
+    p.mx8_stride.clear();
+    p.mx8_eoff.clear();
+    p.mx8 = false;
+    p.mx8_ref = false;
+}
+
 void free_part(fa_ctx* ctx, Part& p) {
     p.noise = 0.0f;
+    free_mx8(ctx, p);
     free_opt(ctx, p);
     free_clip(ctx, p);
     for (size_t g = 0; g < p.pool.size(); ++g) {
@@ -1121,8 +1143,10 @@ int wait_copies(fa_ctx* ctx, int g, hipStream_t s) {
     return FA_OK;
 }
 
-// Copy-out runs of a range part: GPU g's output holds its shard.
+// Copy-out runs of a range part: GPU g's output holds its shard -- every reduction of a range part into its device
+// output ends here, so this is also where an MX8 part's output becomes the next round's reference.
 void set_range_runs(Part& p, int G) {
+    p.mx8_ref = p.mx8;
     for (int g = 0; g < G; ++g) {
         p.runs[(size_t)g] = {Run{0, p.off[(size_t)g], p.cnt[(size_t)g]}};
         p.run_src[(size_t)g] = p.dout[(size_t)g];
@@ -1285,7 +1309,8 @@ const char* device_visible(const void* ptr) {
 bool host_read_part(const fa_ctx* ctx, const Part& p) {
     // trimmed parts are never kept host-side (fa.h): D PCIe reads per element feed a sort, not a chain
     // nor parts with a server-optimizer or clip stage: their round reads or ends in device state
-    return host_read_enabled() && p.mode != FA_TRIMMED && !staged(p) && ctx->G == 1 && !p.rs &&
+    // nor MX8 parts: their output must land on the device, where it is the next round's reference
+    return host_read_enabled() && p.mode != FA_TRIMMED && !staged(p) && !p.mx8 && ctx->G == 1 && !p.rs &&
            !(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) &&
            p.npiece[0] == 1 && p.n > 0 && (size_t)p.D * p.n * dsize(p.in) <= kHostReadMax;
 }
@@ -1891,7 +1916,7 @@ int advance_prefix(fa_ctx* ctx, Part& p) {
     // that took the context's stage at its definition has none and stays non-eager when the stage goes; a part
     // with a stage is non-eager while it has one.
     if (!(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) || p.rs || p.mode != FA_FEDAVG || p.ready || !p.acc[0] ||
-        staged(p))
+        staged(p) || p.mx8)
         return FA_OK;
     int j = p.reduced;
     while (j < p.D && p.submitted[(size_t)j]) ++j;
@@ -2451,6 +2476,102 @@ int reduce_parts_impl(fa_ctx* ctx, int n_parts, const int* ids, const float* con
     return FA_OK;
 }
 
+// ------------------------------------------------------------------ MX8 receipts (fa.h "MX8 receipts")
+
+// The scale bytes GPU g's range [off, off + cnt) touches: blocks off >> 5 .. (off + cnt - 1) >> 5.
+inline size_t mx8_scales(size_t off, size_t cnt) { return cnt ? ((off + cnt - 1) >> 5) - (off >> 5) + 1 : 0; }
+
+// The shadows of an MX8 part, allocated once: per GPU held x stride bytes.  q lies at the shadow's start, which
+// keeps the 16-byte phase of the slots and the output (all 16-byte aligned: the vector form applies).
+int ensure_mx8_buf(fa_ctx* ctx, Part& p) {
+    const size_t G = (size_t)ctx->G;
+    if (p.mx8_buf.size() == G) return FA_OK;
+    p.mx8_buf.assign(G, nullptr);
+    p.mx8_stride.assign(G, 0);
+    p.mx8_eoff.assign(G, 0);
+    for (size_t g = 0; g < G; ++g) {
+        const size_t held = (size_t)(p.c1[g] - p.c0[g]);
+        p.mx8_eoff[g] = (p.cnt[g] + 15) / 16 * 16;
+        p.mx8_stride[g] = (p.mx8_eoff[g] + mx8_scales(p.off[g], p.cnt[g]) + 255) / 256 * 256;
+        const size_t bytes = std::max<size_t>(256, held * p.mx8_stride[g]);
+        DeviceGuard dg(ctx->gpu[g].dev);
+        if (hipMalloc((void**)&p.mx8_buf[g], bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p.mx8_buf[g] = nullptr;
+            const bool on = p.mx8, ref = p.mx8_ref;
+            free_mx8(ctx, p);  // what this attempt did allocate; the part stays an MX8 part
+            p.mx8 = on;
+            p.mx8_ref = ref;
+            return fail(FA_ERR_NOMEM, "mx8: shadow alloc of %zu B failed on GPU %zu", bytes, g);
+        }
+    }
+    return FA_OK;
+}
+
+// H2D of `bytes` host bytes into dev on GPU r's copy stream: straight from pinned memory, else through the pinned
+// chunks, double-buffered as a pageable submit.
+int mx8_h2d(GpuRes& r, char* dev, const char* src, size_t bytes, bool pinned) {
+    if (pinned) {
+        if (bytes) FA_HIP(hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, r.copy));
+        return FA_OK;
+    }
+    for (size_t o = 0; o < bytes; o += kStageBytes) {
+        const size_t b = std::min(kStageBytes, bytes - o);
+        const int i = r.stage_i;
+        r.stage_i ^= 1;
+        FA_HIP(hipEventSynchronize(r.stage_ev[i]));
+        r.pool->copy(r.stage[i], b, [&](size_t lo, size_t len, char* d) { std::memcpy(d, src + o + lo, len); });
+        FA_HIP(hipMemcpyAsync(dev + o, r.stage[i], b, hipMemcpyHostToDevice, r.copy));
+        FA_HIP(hipEventRecord(r.stage_ev[i], r.copy));
+    }
+    return FA_OK;
+}
+
+int submit_mx8_impl(fa_ctx* ctx, int part_id, int slot, const int8_t* q, const uint8_t* e, float weight, int flags) {
+    Trace tr("fa_submit_mx8 part %d slot %d", part_id, slot);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (flags & ~(FA_HOST_PINNED | FA_MX8_ABSOLUTE)) return fail(FA_ERR_ARG, "mx8: unknown flags 0x%x", flags);
+    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    if (!p->mx8) return fail(FA_ERR_STATE, "mx8: part %d does not take MX8 receipts (fa_set_mx8)", part_id);
+    if (p->n > 0 && (!q || !e)) return fail(FA_ERR_ARG, "mx8: %s is null", !q ? "q" : "e");
+    const bool pinned = (flags & FA_HOST_PINNED) != 0, absolute = (flags & FA_MX8_ABSOLUTE) != 0;
+    if (!absolute && !p->mx8_ref)
+        return fail(FA_ERR_STATE, "mx8: part %d has no reference (no round reduced with fa_set_mx8 on, no "
+                                  "fa_mx8_set_reference): send a full receipt, or FA_MX8_ABSOLUTE", part_id);
+    if ((rc = ensure_mx8_buf(ctx, *p))) return rc;
+    if ((rc = host_flush(ctx, *p))) return rc;  // none is kept while mx8 is on; the plain path from here on
+    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        const size_t off = p->off[(size_t)g], cnt = p->cnt[(size_t)g];
+        if (cnt == 0) return FA_OK;
+        // after the part's last reducing call: it read the slot and wrote the reference
+        if (hipStream_t ds = p->done_stream[(size_t)g]) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(r.copy, p->done[(size_t)g], 0));
+        }
+        char* dq = p->mx8_buf[(size_t)g] + (size_t)(slot - p->c0[(size_t)g]) * p->mx8_stride[(size_t)g];
+        char* de = dq + p->mx8_eoff[(size_t)g];
+        ++r.copy_gen;  // the next reducing call waits for the copy stream: the copies and the expansion
+        int rc2 = mx8_h2d(r, dq, reinterpret_cast<const char*>(q) + off, cnt, pinned);
+        if (!rc2) rc2 = mx8_h2d(r, de, reinterpret_cast<const char*>(e) + (off >> 5), mx8_scales(off, cnt), pinned);
+        if (rc2) return rc2;
+        for (int j = 0; j < p->npiece[(size_t)g]; ++j) {
+            const size_t lo = piece_lo(*p, g, j), pc = piece_cnt(*p, g, j);
+            const void* ref = absolute ? nullptr : static_cast<const char*>(p->dout[(size_t)g]) + lo * dsize(p->out);
+            FA_HIP(fa::launch_mx8_expand(reinterpret_cast<const int8_t*>(dq) + lo,
+                                         reinterpret_cast<const uint8_t*>(de) + (((off + lo) >> 5) - (off >> 5)),
+                                         (uint64_t)(off + lo), (int64_t)pc, ref, p->out, piece_ptr(*p, g, slot, j), p->in,
+                                         r.copy));
+        }
+        return FA_OK;
+    });
+    if (rc) return rc;
+    return mark_submitted(ctx, *p, slot, weight);
+}
+
 int tuning_from(const fa_tuning* t, CtxTuning* io) {
     if (!t) return fail(FA_ERR_ARG, "tuning is null");
     CtxTuning nt = *io;
@@ -2729,7 +2850,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     const bool clipped = ctx->clip > 0.0f && mode == FA_FEDAVG && !rs;  // takes the context's clip bound
     const bool noisy = ctx->noise > 0.0f && mode != FA_LITERAL && !rs;  // takes the context's noise stage
     const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged && !clipped &&
-                       !krummed && !geomedded && !noisy;
+                       !krummed && !geomedded && !noisy && !ctx->mx8;
     if (rs) {
         const size_t unit = G * kShardUnit;
         p.npad = (n_elems + unit - 1) / unit * unit;
@@ -2841,6 +2962,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
             return rc;
         }
     }
+    p.mx8 = ctx->mx8 && mode != FA_LITERAL && !rs;
     ctx->parts.emplace(part_id, std::move(p));
     return FA_OK;
 }
@@ -3422,6 +3544,97 @@ int fa_noise_host(uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0,
     if (n == 0) return FA_OK;
     if (!z) return fail(FA_ERR_ARG, "noise: z is null");
     fa::noise_host(seed, stream, round, idx0, n, z);
+    return FA_OK;
+}
+
+size_t fa_mx8_scale_bytes(size_t n) { return n / FA_MX8_BLOCK + (n % FA_MX8_BLOCK ? 1 : 0); }
+
+int fa_mx8_encode(const float* delta, size_t n, int8_t* q, uint8_t* e) {
+    g_err.clear();
+    if (n == 0) return FA_OK;
+    if (!delta || !q || !e) return fail(FA_ERR_ARG, "mx8: %s is null", !delta ? "delta" : !q ? "q" : "e");
+    fa::mx8_encode_host(delta, n, q, e);
+    return FA_OK;
+}
+
+int fa_mx8_decode(const int8_t* q, const uint8_t* e, size_t n, uint64_t idx0, float* d) {
+    g_err.clear();
+    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "mx8: idx0 + n beyond 2^64");
+    if (n == 0) return FA_OK;
+    if (!q || !e || !d) return fail(FA_ERR_ARG, "mx8: %s is null", !q ? "q" : !e ? "e" : "d");
+    fa::mx8_decode_host(q, e, n, idx0, d);
+    return FA_OK;
+}
+
+int fa_mx8_expand_device(fa_ctx* ctx, int gpu, const int8_t* d_q, const uint8_t* d_e, size_t n, uint64_t idx0,
+                         const void* d_ref, fa_dtype ref_dtype, void* d_dst, fa_dtype dst_dtype, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (!dvalid(dst_dtype) || !dvalid(ref_dtype)) return fail(FA_ERR_ARG, "bad dtype");
+    if (!fa::dtype_pair_ok(dst_dtype, ref_dtype))
+        return fail(FA_ERR_ARG, "mx8: no %s slot against a %s reference (a 16-bit slot takes its own type or f32)",
+                    fa::dtype_name(dst_dtype), fa::dtype_name(ref_dtype));
+    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "mx8: idx0 + n beyond 2^64");
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) return FA_OK;
+    if (!d_q || !d_e || !d_dst) return fail(FA_ERR_ARG, "mx8: %s pointer is null", !d_q ? "d_q" : !d_e ? "d_e" : "d_dst");
+    if (d_ref && !aligned(d_ref, dsize(ref_dtype)))
+        return fail(FA_ERR_ALIGN, "mx8: reference not %zu-byte aligned", dsize(ref_dtype));
+    if (!aligned(d_dst, dsize(dst_dtype))) return fail(FA_ERR_ALIGN, "mx8: slot not %zu-byte aligned", dsize(dst_dtype));
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    FA_HIP(fa::launch_mx8_expand(d_q, d_e, idx0, (int64_t)n, d_ref, ref_dtype, d_dst, dst_dtype, c.s));
+    return FA_OK;
+}
+
+int fa_set_mx8(fa_ctx* ctx, int part_id, int on) {
+    g_err.clear();
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (on && (ctx->flags & FA_SHARD_CLIENT_RS))
+        return fail(FA_ERR_ARG, "mx8: not on an FA_SHARD_CLIENT_RS context (a GPU holding a whole slot does not hold "
+                                "the matching output; use FA_SHARD_RANGE)");
+    if (part_id < 0) {
+        ctx->mx8 = on != 0;
+        return FA_OK;
+    }
+    Part* p;
+    if (int rc = check_part(ctx, part_id, &p)) return rc;
+    if (on && p->mode == FA_LITERAL) return fail(FA_ERR_ARG, "mx8: part %d is an FA_LITERAL part", part_id);
+    if (!on) {
+        if (p->mx8)  // the shadows may still be in use
+            if (int rc = opt_quiesce(ctx)) return rc;
+        free_mx8(ctx, *p);
+        return FA_OK;
+    }
+    if (p->mx8) return FA_OK;
+    // what this round kept host-side or chained so far goes back to the plain path
+    if (int rc = host_flush(ctx, *p)) return rc;
+    restart_round_plain(*p);
+    p->mx8 = true;
+    p->mx8_ref = false;
+    return FA_OK;
+}
+
+int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags) {
+    g_err.clear();
+    return submit_mx8_impl(ctx, part_id, client_slot, q, e, weight, flags);
+}
+
+int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
+    g_err.clear();
+    Part* p;
+    if (int rc = check_part(ctx, part_id, &p)) return rc;
+    if (!p->mx8) return fail(FA_ERR_STATE, "mx8: part %d does not take MX8 receipts (fa_set_mx8)", part_id);
+    if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
+    if (int rc = opt_quiesce(ctx)) return rc;  // the part's pending work, on whatever stream
+    const size_t so = dsize(p->out);
+    for (int g = 0; g < ctx->G; ++g) {
+        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
+        if (p->cnt[(size_t)g])
+            FA_HIP(hipMemcpy(p->dout[(size_t)g], static_cast<const char*>(host_src) + p->off[(size_t)g] * so,
+                             p->cnt[(size_t)g] * so, hipMemcpyHostToDevice));
+    }
+    set_range_runs(*p, ctx->G);  // as a round's output: the reference, and what fa_copy_output hands out
     return FA_OK;
 }
 

@@ -155,6 +155,16 @@ hipError_t launch_noise(const float* avg, void* out, fa_dtype odt, float stddev,
                         uint32_t round, uint64_t idx0, const Split& sp, const Tuning& tu, hipStream_t s);
 // The same normals on the host (fa_noise_host): z[0, n) := z_{idx0} .. z_{idx0 + n - 1}.  The kernel's own source.
 void noise_host(uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, size_t n, float* z);
+// MX8 receipts (fa.h "MX8 receipts"), fa_mx8.hip.  dst[i] (dtype ddt, one rounding) := fl(widen(ref[i]) + d_i), or d_i
+// without a reference (ref null), over n elements, d_i = fl((float)q[i] * 2^(E - 133)) with E = e[((idx0 + i) >> 5) -
+// (idx0 >> 5)]: e[0] is the scale of the block that bucket element idx0 lies in.  (ddt, rdt) as dtype_pair_ok(in, out).
+// Any pointers of element alignment: mx8_split (host-only) says which form a launch takes.
+Split mx8_split(const void* q, size_t n, const void* ref, fa_dtype rdt, const void* dst, fa_dtype ddt);
+hipError_t launch_mx8_expand(const int8_t* q, const uint8_t* e, uint64_t idx0, int64_t n, const void* ref, fa_dtype rdt,
+                             void* dst, fa_dtype ddt, hipStream_t s);
+// The codec on the host (fa_mx8_decode: the kernel's own multiply and scale; fa_mx8_encode: the owner's side).
+void mx8_decode_host(const int8_t* q, const uint8_t* e, size_t n, uint64_t idx0, float* d);
+void mx8_encode_host(const float* delta, size_t n, int8_t* q, uint8_t* e);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
                        const Tuning& tu, hipStream_t s);

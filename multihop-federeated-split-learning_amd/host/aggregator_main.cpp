@@ -96,6 +96,10 @@ struct Options {
     // streaming ingest: receipt frames of at least this many bytes go to their slot record by record while
     // they arrive (NetLayer::set_streaming; pinned frames only); 0 = off
     size_t stream_min = 1u << 20;
+    // --mx8: buckets take MX8 receipts (fa_set_mx8 on the context, before any bucket is defined): an archive of one
+    // int8 parameter (the codes) and one uint8 buffer (the scales) is an owner's update against the reply it last
+    // loaded, expanded on the GPU (fa_submit_mx8)
+    bool mx8 = false;
     bool gpu_crc = true;  // --crc gpu|host: the reply records' CRC-32s from the GPU (fa_output_crc32) or the host
     std::map<int, double> samples;  // client id -> n_k
     // --server-opt RULE --server-lr L [--server-beta1 B] [--server-beta2 B] [--server-tau T]: the server
@@ -269,6 +273,7 @@ void usage() {
                  "       [--krum-f F [--krum-m M]]\n"
                  "       [--geomed-iters T [--geomed-nu NU]]\n"
                  "       [--dp-noise-multiplier Z [--dp-seed S]]\n"
+                 "       [--mx8]\n"
                  "--mode trimmed: per element the T lowest and T highest of the owners' values are dropped and the\n"
                  "rest averaged (2T < DATA_OWNERS <= 128; without --trim, and with --mode median, the median), so up\n"
                  "to T owners that send NaN, inf or huge values change no reply; --samples is ignored; not with\n"
@@ -302,6 +307,11 @@ void usage() {
                  "aggregate before it is stepped or replied: DP-FedAvg.  The seed is drawn from the operating system at\n"
                  "every start, never stored, and no noise is ever replayed; --dp-seed S (u64) fixes it to reproduce a run,\n"
                  "which voids the guarantee.  Z finite and > 0; not with --mode literal or --layout rs.\n"
+                 "--mx8: a receipt may be an MX8 archive -- one int8 parameter of n codes and one uint8 buffer of\n"
+                 "ceil(n / 32) block scales -- holding the owner's update against the reply it last loaded, 33 bytes per 32\n"
+                 "elements; it is expanded on the GPU and counts as that owner's receipt.  A bucket is still defined by its\n"
+                 "first full receipt, which is also the reply's template, and needs one reduced round before it takes MX8\n"
+                 "receipts (exit 1 otherwise); a round may mix both kinds; not with --mode literal or --layout rs.\n"
                  "A bucket takes the dtype of its first receipt's parameters (all fp32, all bf16 or all fp16, by\n"
                  "their storage type) and is reduced and replied in it; a later receipt of another size or dtype\n"
                  "ends the process (exit 1).\n";
@@ -329,6 +339,7 @@ bool parse_args(int argc, char** argv, Options* o) {
         else if (a == "--no-pinned") o->pinned = false;
         else if (a == "--eager") o->eager = true;
         else if (a == "--test-shared-device") o->shared_device = true;
+        else if (a == "--mx8") o->mx8 = true;
         else if (a == "--rs-chunks") o->rs_chunks = std::atoi(val("--rs-chunks"));
         else if (a == "--stall-report") o->stall_report_s = std::atof(val("--stall-report"));
         else if (a == "--receipt-timeout") o->receipt_timeout_s = std::atof(val("--receipt-timeout"));
@@ -422,6 +433,11 @@ bool parse_args(int argc, char** argv, Options* o) {
             std::cerr << "unknown argument " << a << "\n";
             return false;
         }
+    }
+    if (o->mx8 && (o->mode == FA_LITERAL || o->rs)) {
+        std::cerr << "--mx8 expands an update against the bucket's last output on the GPU that holds it: not with "
+                  << (o->rs ? "--layout rs" : "--mode literal") << "\n";
+        return false;
     }
     if (o->trim_given && (o->mode != FA_TRIMMED || o->median || o->bulyan)) {
         std::cerr << "--trim goes with --mode trimmed\n";
@@ -657,6 +673,7 @@ public:
         if (o.clip_given) FA_CHECK(fa_set_clip(ctx_, -1, o.clip_norm));
         if (o.krum_given) FA_CHECK(fa_set_krum(ctx_, -1, o.krum_f, o.krum_m));
         if (o.geomed_given) FA_CHECK(fa_set_geomed(ctx_, -1, o.geomed_iters, o.geomed_nu));
+        if (o.mx8) FA_CHECK(fa_set_mx8(ctx_, -1, 1));  // before any bucket
         if (o.rs_chunks > 0) {
             fa_tuning t{};
             t.rs_chunks = o.rs_chunks;
@@ -782,6 +799,10 @@ public:
             std::exit(1);
         }
         Bucket& b = buckets_[r.model_part];
+        const int8_t* mq = nullptr;
+        const uint8_t* me = nullptr;
+        int64_t mn = 0;
+        if (o_.mx8 && ar.mx8_view(&mq, &me, &mn)) return absorb_mx8(r, st.slot >= 0, key, mq, me, mn, t0);
         // the bucket dtype, from the parameters' storage type (never from the element size: bf16 and fp16
         // are both 2 bytes): fp32 (the reference), bf16 (config C3) or fp16 (owners that train with .half())
         const ParamDtype pd = ar.param_dtype();
@@ -861,13 +882,54 @@ public:
         b.bytes_in += r.blob_len;
         ledger_.accept(r.client_id, r.model_part, key);
         const bool first = b.arrived.insert(r.client_id).second;
-        b.last = r;  // template of the reply: the last receipt (its buffers travel back, as in the reference)
+        b.last = r;  // template of the reply: the last full receipt (its buffers travel back, as in the reference)
         st_.absorb_s += secs_since(t0);
         if (!first) {
             std::cerr << "[aggregator] part " << r.model_part << ": owner " << r.client_id << " sent it again\n";
             ++replaced_;
         }
         return first;
+    }
+
+    // --mx8: an MX8 receipt (TorchArchive::mx8_view) of a defined bucket with a round behind it goes to its slot
+    // as codes and scales -- DMA'd from the frame when that is pinned -- and is expanded there against the bucket's
+    // last output.  Its frame was never streamed by the bucket's layout (claim() matches a frame's length against
+    // the last full receipt's; should the two ever agree, the expansion overwrites the whole slot).  It is not the
+    // reply's template: that stays the bucket's last full receipt.
+    bool absorb_mx8(const Receipt& r, bool streamed, const ReceiptKey& key, const int8_t* q, const uint8_t* e, int64_t n,
+                    std::chrono::steady_clock::time_point t0) {
+        auto& b = buckets_[r.model_part];
+        const char* why = !b.defined ? "is not defined yet (its first receipt must be a full one)"
+                          : !b.reduced ? "has no round reduced yet (the update has nothing to be applied to)"
+                          : (size_t)n != b.numel ? "holds another number of elements" : nullptr;
+        if (why) {
+            std::cerr << "[aggregator] MX8 receipt for part " << r.model_part << " from owner " << r.client_id
+                      << ": the bucket " << why << "\n";
+            net_->stop();  // as for --server-state: the readers finish before exit() destroys their allocator
+            std::exit(1);
+        }
+        const int slot = slot_of(r.client_id);
+        cancel_streams(r.client_id, r.model_part);
+        if (streamed) ++stream_fallbacks_;
+        FA_CHECK(fa_submit_mx8(ctx_, r.model_part, slot, q, e, weight_of(r.client_id), r.frame->pinned ? FA_HOST_PINNED : 0));
+        if (r.frame->pinned) b.held.push_back(r.frame);  // DMA'd from until the bucket is finalized
+        b.bytes_in += r.blob_len;
+        ++mx8_receipts_;
+        mx8_bytes_ += r.blob_len;
+        ledger_.accept(r.client_id, r.model_part, key);
+        const bool first = b.arrived.insert(r.client_id).second;
+        st_.absorb_s += secs_since(t0);
+        if (!first) {
+            std::cerr << "[aggregator] part " << r.model_part << ": owner " << r.client_id << " sent it again\n";
+            ++replaced_;
+        }
+        return first;
+    }
+    // This round's MX8 receipts and their archive bytes so far; reading them starts the next round's count.
+    std::pair<unsigned long long, unsigned long long> take_mx8() {
+        const auto v = std::make_pair(mx8_receipts_, mx8_bytes_);
+        mx8_receipts_ = mx8_bytes_ = 0;
+        return v;
     }
 
     // Reduces bucket mp and returns the framed reply, built once and shared by every destination:
@@ -960,6 +1022,7 @@ public:
         b.held.clear();
         b.arrived.clear();
         b.bytes_in = 0;
+        b.reduced = true;
         st_.finalize_s += t_fin;
         st_.frame_s += secs_since(t0) - t_fin;
         return f;
@@ -1294,7 +1357,8 @@ private:
         ParamDtype dtype = ParamDtype::F32;  // what the bucket was defined with; a receipt of another is refused
         Recs recs;            // the parameter records of the last pinned receipt (the streaming layout)
         size_t recs_len = 0;  // ... for archives of this length
-        Receipt last;
+        Receipt last;         // the last full receipt, across rounds: the reply's template
+        bool reduced = false; // a round of this bucket was reduced: its output can take an MX8 update
         std::vector<std::shared_ptr<const Bytes>> held;  // pinned frames DMA'd from, until finalize
         std::set<int> arrived;  // client ids received this round
     };
@@ -1359,6 +1423,7 @@ private:
     std::vector<Stream> streams_;
     std::set<int> phase_mps_;
     unsigned long long streamed_ = 0, stream_fallbacks_ = 0, streamed_bytes_ = 0;
+    unsigned long long mx8_receipts_ = 0, mx8_bytes_ = 0;  // --mx8: this round's
 };
 
 // The next receipt, with the failure detection the reference lacks (its receive loop blocks forever on a
@@ -1542,7 +1607,14 @@ int main(int argc, char** argv) {
                      server_rule_name(o.server.rule), (double)o.server.lr, agg.save_server_state());
             server_tail = buf;
         }
-        const std::string clip_tail =
+        std::string mx8_tail;
+        if (o.mx8) {
+            const auto mx = agg.take_mx8();
+            char buf[96];
+            snprintf(buf, sizeof buf, ",\"mx8_receipts\":%llu,\"mx8_bytes_in\":%llu", mx.first, mx.second);
+            mx8_tail = buf;
+        }
+        const std::string clip_tail = mx8_tail +
             (o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : o.geomed_given ? agg.geomed_tail() : o.bulyan ? agg.bulyan_tail() : std::string()) + (o.dp_given ? agg.dp_tail() : std::string());
         printf("{\"round\":%d,\"phase1\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f},"

@@ -754,6 +754,25 @@ int TorchArchive::param_elem_size() const {
     return 0;
 }
 
+bool TorchArchive::mx8_view(const int8_t** q, const uint8_t** e, int64_t* n) const {
+    if (params_.size() != 1 || buffers_.size() != 1) return false;
+    const TensorView &p = params_[0], &b = buffers_[0];
+    if (p.storage_type != "CharStorage" || b.storage_type != "ByteStorage" || !p.contiguous || !b.contiguous) return false;
+    if (p.numel < 0 || b.numel != p.numel / 32 + (p.numel % 32 ? 1 : 0)) return false;
+    for (const TensorView* t : {&p, &b}) {
+        if (t->record < 0 || (size_t)t->record >= entries_.size() || t->elem_size != 1) return false;
+        const ZipEntry& z = entries_[(size_t)t->record];
+        if (z.method != 0 || z.data_offset > size_ || z.size > size_ - z.data_offset) return false;
+        const uint8_t* lo = base_ + z.data_offset;
+        if (t->numel > 0 && (t->data < lo || t->data > lo + z.size || (uint64_t)t->numel > (uint64_t)(lo + z.size - t->data)))
+            return false;
+    }
+    *q = reinterpret_cast<const int8_t*>(p.data);
+    *e = b.data;
+    *n = p.numel;
+    return true;
+}
+
 bool TorchArchive::param_segments(std::vector<const void*>* ptrs, std::vector<size_t>* bytes) const {
     ptrs->clear();
     bytes->clear();

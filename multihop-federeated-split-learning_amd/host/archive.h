@@ -63,6 +63,13 @@ public:
     // param_dtype(), so a caller that reduces the values asks that, not the size.
     int param_elem_size() const;
 
+    // Whether the archive is an MX8 receipt (fa.h "MX8 receipts"): exactly one parameter, contiguous CharStorage of
+    // *n elements (the codes q), and exactly one buffer, contiguous ByteStorage of ceil(*n / 32) elements (the scales
+    // e) -- what torch.jit.script of a module with nn.Parameter(int8, requires_grad=False) and register_buffer(uint8)
+    // writes.  These are bytes from the wire: both views are checked again against the record they point into and the
+    // record against the archive, whatever parse() accepted.  False (nothing written) otherwise.
+    bool mx8_view(const int8_t** q, const uint8_t** e, int64_t* n) const;
+
     // Contiguous pieces of the parameter bucket, in order (one per contiguous param, fp32, bf16 or fp16
     // throughout): a gather list for fa_submit_gather.  False if some param is strided or the types mix.
     bool param_segments(std::vector<const void*>* ptrs, std::vector<size_t>* bytes) const;
