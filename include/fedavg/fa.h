@@ -303,6 +303,42 @@
  *                 valid input to the decoder.
  *              Added without a new FA_ABI_VERSION: fa_mx8_expand_device with n == 0 touches no device and answers
  *              FA_OK -- that is how a caller probes for it.
+ *   MX8 replies (fa_set_mx8_reply, fa_finalize_mx8, fa_copy_mx8, fa_mx8_encode_device): the other direction.  The new
+ *              model goes back to the owners as an MX8 update against the model they were last sent, encoded on
+ *              the GPU; the format and the decoder are those of MX8 receipts.  The reply is lossy, so the library
+ *              continues from what the owners then hold, not from its own aggregate.
+ *              Part state: `sent`, the model the owners last received -- per GPU the elements of its range, in the
+ *              part's out dtype -- and whether it exists.
+ *              Per reducing call of a part with the stage on:
+ *              1. y is the part's output exactly as the call would leave it without the stage: after the noise
+ *                 stage and the server optimizer, rounded to the out dtype.
+ *              2. Bootstrap.  If `sent` does not exist: the output stays y, sent := y, the round has no codes.
+ *              3. Otherwise, per element, delta_i = fl32(widen(y_i) - widen(sent_i)), one IEEE subtract, no
+ *                 contraction.  The deltas are encoded by encode rules 1-3 of MX8 receipts, unchanged, into q and
+ *                 e; the block of an element is its bucket index >> 5, whatever the shard.  The GPU's bytes are
+ *                 those fa_mx8_encode gives for these deltas.  (The kernel takes E from the bit pattern of the
+ *                 block's maximum: its exponent field, one more if the mantissa is above 0x7E0000, 0 up to the
+ *                 subnormal 0x7F0000, held at 254 -- the same number as rule 3's frexp.)
+ *              4. g'_i is decode rule 3 of (q, e) against sent, into the out dtype: fl32(widen(sent_i) +
+ *                 fl32((float)q_i * s)), rounded once more for a 16-bit out dtype.  A block with E = 255 becomes
+ *                 NaN throughout, as the decoder says, and stays NaN until fa_mx8_set_reference is called or the
+ *                 stage is switched off and on (which drops `sent`: the next round is a bootstrap).  The round
+ *                 reports its count of E = 255 blocks (fa_mx8_reply_stats).
+ *              5. The part's device output becomes g', and sent := g'.  Everything that reads the part's output
+ *                 after the call sees g': fa_copy_output, fa_finalize*, fa_output_crc32, fa_bucket_output, the
+ *                 clip stage's reference update (clip rule 6) and the reference of MX8 receipts.  The server
+ *                 optimizer's master and moments and the noise counter are not touched: the master keeps the
+ *                 exact model, and the next round's delta, taken from the master's output against g', carries
+ *                 this round's quantisation error into the next reply.
+ *              6. Layout independence.  q, e and g' are the same bytes for any GPU count and any range
+ *                 boundaries.  A block that lies in the ranges of several GPUs gets the byte maximum of their
+ *                 partial scales -- exact, because E is non-decreasing in the block maximum and 255 dominates --
+ *                 and the codes of its elements are taken under that scale (fa_mx8_encode_device's scales-only
+ *                 and scales-given modes around the maximum).  A context never has such a block: its range shards
+ *                 and pieces are cut at multiples of 64 elements, so no round has that extra wait, and the stage
+ *                 refuses a range that starts inside a block (FA_ERR_STATE).
+ *              Added without a new FA_ABI_VERSION: fa_mx8_encode_device with n == 0 touches no device and answers
+ *              FA_OK -- that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -807,8 +843,47 @@ int fa_set_mx8(fa_ctx* ctx, int part_id, int on);
 int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags);
 /* Writes the part's device output on every GPU from host_src (n elements of the out dtype), as if a round had
  * produced it: the reference of the next relative submits (a restarted aggregator; tests).  Waits for the part's
- * pending work.  FA_ERR_STATE on a part without fa_set_mx8. */
+ * pending work.  On a part with the reply stage it also sets `sent`.  FA_ERR_STATE on a part with neither
+ * fa_set_mx8 nor fa_set_mx8_reply. */
 int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src);
+
+/* MX8 replies (the header comment, "MX8 replies"): the new model as block-scaled int8 deltas, encoded on the GPU. */
+#define FA_MX8_SCALES_ONLY 0x1  /* write d_e alone: the scales of the blocks from this launch's deltas */
+#define FA_MX8_SCALES_GIVEN 0x2 /* read d_e instead of writing it: codes and g' under the given scales */
+/* Rules 3-4 on raw device pointers, on device `gpu`: over the n elements of d_new and d_sent (both of dtype
+ * new_dtype == sent_dtype), bucket elements idx0 .. idx0 + n - 1, writes d_q (n bytes), d_e (the scale bytes of blocks
+ * idx0 >> 5 .. (idx0 + n - 1) >> 5, d_e[0] the first; a block that the launch holds only part of gets the scale of
+ * that part) and, unless d_out is NULL, g' into d_out (n elements of the same dtype).  flags: 0 = the fused pass;
+ * FA_MX8_SCALES_ONLY = d_e alone is written, d_q and d_out are not touched and may be NULL; FA_MX8_SCALES_GIVEN = d_e
+ * is read.  A block cut by launches: scales-only on each part, the byte maximum of the partial scales, scales-given
+ * on each part.  Aliasing: d_out may be d_sent or d_new exactly (the same address; both if d_new == d_sent) or
+ * overlap neither; d_q and d_e overlap nothing else; any other overlap of d_out is refused with FA_ERR_ARG.  ctx may
+ * be NULL (then `gpu` is the HIP device).  Every argument is checked before any device call: the dtypes (equal),
+ * the flags (not both), idx0 + n < 2^64, and for n > 0 null pointers and element alignment (FA_ERR_ALIGN); with n == 0
+ * and valid arguments it returns FA_OK without touching a device.  Any byte phase of d_q and d_e and any element phase
+ * of the others is correct; 16-byte accesses are used where every pointer is 16-byte aligned at the first block
+ * boundary.  Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
+int fa_mx8_encode_device(fa_ctx* ctx, int gpu, const void* d_new, fa_dtype new_dtype, const void* d_sent,
+                         fa_dtype sent_dtype, size_t n, uint64_t idx0, int8_t* d_q, uint8_t* d_e, void* d_out, int flags,
+                         void* hip_stream);
+/* Switches the reply stage of a part on or off (part_id >= 0), or sets the context default for parts defined later
+ * (part_id < 0; FA_LITERAL parts ignore it).  FA_ERR_ARG on an FA_LITERAL part or an FA_SHARD_CLIENT_RS context.  Like
+ * the other stage parts such a part is never kept host-side, FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager, it gets
+ * its own launches in fa_reduce_parts, a reducing call needs every client submitted, and fa_reduce_part marks the
+ * round reduced.  Switching it on drops `sent` (the next round is a bootstrap); on == 0 frees `sent` and the code
+ * buffers.  Memory, allocated at the first reducing call: per GPU its elements once more in the out dtype, one byte
+ * per element and the scale bytes. */
+int fa_set_mx8_reply(fa_ctx* ctx, int part_id, int on);
+/* fa_finalize with the round's codes as the D2H instead of the bucket: q (n bytes) and e (fa_mx8_scale_bytes(n) bytes).
+ * flags: FA_HOST_PINNED as in fa_finalize_gather (q and e are pinned, the DMA writes into them).  FA_ERR_STATE,
+ * checked before any work and leaving the round intact, when the part has no `sent` (this round is the bootstrap, or
+ * the part has no reply stage): the caller then finishes with fa_finalize*. */
+int fa_finalize_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags);
+/* The codes of the part's last reducing call, as fa_copy_output is for the bucket.  FA_ERR_STATE when that call was
+ * a bootstrap (or none was made). */
+int fa_copy_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags);
+/* *nan_blocks = the E = 255 blocks among the codes of the part's last reducing call (0 after a bootstrap). */
+int fa_mx8_reply_stats(fa_ctx* ctx, int part_id, uint64_t* nan_blocks);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

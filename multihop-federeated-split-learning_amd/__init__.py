@@ -125,6 +125,11 @@ def lib():
         "fa_set_mx8": (I, [P, I, I]),
         "fa_submit_mx8": (I, [P, I, I, P, P, F, I]),
         "fa_mx8_set_reference": (I, [P, I, P]),
+        "fa_mx8_encode_device": (I, [P, I, P, I, P, I, S, U64, P, P, P, I, P]),
+        "fa_set_mx8_reply": (I, [P, I, I]),
+        "fa_finalize_mx8": (I, [P, I, P, P, I]),
+        "fa_copy_mx8": (I, [P, I, P, P, I]),
+        "fa_mx8_reply_stats": (I, [P, I, P]),
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
         "fa_submit_gather": (I, [P, I, I, I, P, P, F]),
@@ -419,6 +424,7 @@ def noise_host(seed, stream_id, round, idx0, n):
 
 MX8_BLOCK = 32  # FA_MX8_BLOCK: elements per scale byte of an MX8 receipt (fa.h "MX8 receipts")
 MX8_ABSOLUTE = 0x2  # FA_MX8_ABSOLUTE
+MX8_SCALES_ONLY, MX8_SCALES_GIVEN = 0x1, 0x2  # FA_MX8_SCALES_ONLY, FA_MX8_SCALES_GIVEN (mx8_encode_device)
 
 
 def mx8_scale_bytes(n):
@@ -452,6 +458,18 @@ def mx8_expand_device(q, e, n, dst, dst_dtype=F32, ref=None, ref_dtype=F32, idx0
     not synchronized.  With n == 0 no device is touched: the feature probe."""
     check(lib().fa_mx8_expand_device(ctx.handle if ctx is not None else None, gpu, _addr(q), _addr(e), n, int(idx0),
                                      _addr(ref), ref_dtype, _addr(dst), dst_dtype, _stream(stream)))
+
+
+def mx8_encode_device(new, sent, n, q, e, out=None, dtype=F32, sent_dtype=None, idx0=0, scales_only=False,
+                      scales_given=False, stream=None, gpu=0, ctx=None):
+    """fa_mx8_encode_device (fa.h "MX8 replies", rules 3-4): over n device-resident elements of `dtype`, bucket elements
+    idx0 .., the codes q and the scales e of fl(new - sent), and (out not None) g' = sent + decode(q, e) into out, which
+    may be `sent` or `new` itself.  scales_only: e alone is written; scales_given: e is read.  Enqueued, not
+    synchronized.  With n == 0 no device is touched: the feature probe."""
+    flags = (MX8_SCALES_ONLY if scales_only else 0) | (MX8_SCALES_GIVEN if scales_given else 0)
+    check(lib().fa_mx8_encode_device(ctx.handle if ctx is not None else None, gpu, _addr(new), dtype, _addr(sent),
+                                     dtype if sent_dtype is None else sent_dtype, n, int(idx0), _addr(q), _addr(e),
+                                     _addr(out), flags, _stream(stream)))
 
 
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
@@ -848,6 +866,35 @@ class Aggregator:
             if g.nbytes != n * DTYPE_SIZE[out_dtype]:
                 raise ValueError("bucket %d's output holds %d bytes, got %d" % (part_id, n * DTYPE_SIZE[out_dtype], g.nbytes))
         check(lib().fa_mx8_set_reference(self.handle, part_id, g.ctypes.data))
+
+    def set_mx8_reply(self, on=True, part_id=-1):
+        """fa_set_mx8_reply: the part's new model goes back as MX8 codes against the model the owners were last sent,
+        and its output becomes what they hold after it (part_id < 0: the default of parts defined later); on=False
+        frees the sent model and the codes."""
+        check(lib().fa_set_mx8_reply(self.handle, part_id, 1 if on else 0))
+
+    def _mx8_codes(self, fn, part_id):
+        if part_id not in self.parts:  # let the library report it (FA_ERR_ARG)
+            check(fn(self.handle, part_id, None, None, 0))
+        n = self.parts[part_id][0]
+        q, e = np.empty(n, np.int8), np.empty(mx8_scale_bytes(n), np.uint8)
+        check(fn(self.handle, part_id, q.ctypes.data, e.ctypes.data, 0))
+        return q, e
+
+    def finalize_mx8(self, part_id):
+        """fa_finalize_mx8: ends the round as finalize does and returns its codes (q int8[n], e uint8[ceil(n / 32)])
+        instead of the bucket; FA_ERR_STATE, the round untouched, when the owners hold no model yet."""
+        return self._mx8_codes(lib().fa_finalize_mx8, part_id)
+
+    def copy_mx8(self, part_id):
+        """fa_copy_mx8: the codes (q, e) of the part's last reducing call."""
+        return self._mx8_codes(lib().fa_copy_mx8, part_id)
+
+    def mx8_reply_stats(self, part_id):
+        """fa_mx8_reply_stats: the E = 255 (NaN) blocks among the codes of the part's last reducing call."""
+        nan = ctypes.c_uint64()
+        check(lib().fa_mx8_reply_stats(self.handle, part_id, ctypes.byref(nan)))
+        return nan.value
 
     def submit_gather(self, part_id, slot, pieces, weight=1.0, pinned=False):
         """fa_submit_gather(_pinned): `pieces` (host arrays) concatenate to the bucket.  pinned: views of

@@ -386,13 +386,22 @@ struct Part {
     bool mx8 = false, mx8_ref = false;
     std::vector<char*> mx8_buf;
     std::vector<size_t> mx8_stride, mx8_eoff;
+    // MX8 replies (fa.h "MX8 replies"; fa_set_mx8_reply).  reply_sent: per GPU the model the owners last received,
+    // cnt elements of the out dtype (reply_has_sent: it holds one).  reply_codes: per GPU the codes of the last
+    // reducing call, q (cnt bytes) and from reply_eoff[g] on the scale bytes of the blocks its range touches
+    // (reply_has_codes: that call was no bootstrap).  Allocated at the first reducing call with the stage on.
+    bool reply = false, reply_has_sent = false, reply_has_codes = false;
+    std::vector<char*> reply_sent, reply_codes;
+    std::vector<size_t> reply_eoff;
+    bool reply_counted = true;  // reply_nan describes the codes above
+    uint64_t reply_nan = 0;
 };
 
-// A part whose reducing calls are rounds of their own (a server-optimizer, clip, Krum, geomed, Bulyan or noise stage):
-// never batched, eager or host-read, every client submitted before each.
+// A part whose reducing calls are rounds of their own (a server-optimizer, clip, Krum, geomed, Bulyan, noise or MX8
+// reply stage): never batched, eager or host-read, every client submitted before each.
 inline bool staged(const Part& p) {
     return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0 || p.geomed_iters != 0 || p.bulyan_f >= 0 ||
-           p.noise > 0.0f;
+           p.noise > 0.0f || p.reply;
 }
 // A part that gets its first stage: what this round chained or kept host-side so far goes back to the plain path.
 inline void restart_round_plain(Part& p) {
@@ -416,6 +425,7 @@ struct fa_ctx {
     float noise = 0.0f;         // default noise stage of FedAvg / trimmed parts defined later (0: none)
     uint64_t noise_seed = 0;
     bool mx8 = false;           // parts defined later (not FA_LITERAL) take MX8 receipts
+    bool mx8_reply = false;     // parts defined later (not FA_LITERAL) have the MX8 reply stage
     CtxTuning tuning;
     std::vector<GpuRes> gpu;
     std::map<int, Part> parts;
@@ -1110,9 +1120,25 @@ void free_mx8(fa_ctx* ctx, Part& p) {
     p.mx8_ref = false;
 }
 
+// `sent` and the code buffers go (hipFree waits for the device's pending work); the part has no reply stage.
+void free_reply(fa_ctx* ctx, Part& p) {
+    for (size_t g = 0; g < p.reply_sent.size(); ++g) {
+        DeviceGuard dg(ctx->gpu[g].dev);
+        if (p.reply_sent[g]) (void)hipFree(p.reply_sent[g]);
+        if (g < p.reply_codes.size() && p.reply_codes[g]) (void)hipFree(p.reply_codes[g]);
+    }
+    p.reply_sent.clear();
+    p.reply_codes.clear();
+    p.reply_eoff.clear();
+    p.reply = p.reply_has_sent = p.reply_has_codes = false;
+    p.reply_counted = true;
+    p.reply_nan = 0;
+}
+
 void free_part(fa_ctx* ctx, Part& p) {
     p.noise = 0.0f;
     free_mx8(ctx, p);
+    free_reply(ctx, p);
     free_opt(ctx, p);
     free_clip(ctx, p);
     for (size_t g = 0; g < p.pool.size(); ++g) {
@@ -1587,6 +1613,62 @@ int subset_chain(fa_ctx* ctx, Part& p, int g, int j, const SubsetPlan& plan, voi
 }
 
 // Rule 6 for the same piece: the reference := the output just written, widened to fp32.
+// The buffers of a reply part, allocated once: per GPU `sent` (cnt elements of the out dtype) and the codes (q: cnt
+// bytes, then from reply_eoff[g] on the scale bytes of the blocks the range touches).
+int ensure_reply_buf(fa_ctx* ctx, Part& p) {
+    const size_t G = (size_t)ctx->G;
+    if (p.reply_sent.size() == G) return FA_OK;
+    p.reply_sent.assign(G, nullptr);
+    p.reply_codes.assign(G, nullptr);
+    p.reply_eoff.assign(G, 0);
+    for (size_t g = 0; g < G; ++g) {
+        DeviceGuard dg(ctx->gpu[g].dev);
+        p.reply_eoff[g] = (p.cnt[g] + 15) / 16 * 16;
+        const size_t scales = p.cnt[g] ? ((p.off[g] + p.cnt[g] - 1) >> 5) - (p.off[g] >> 5) + 1 : 0;
+        const size_t sbytes = std::max<size_t>(256, p.cnt[g] * dsize(p.out)), cbytes = std::max<size_t>(256, p.reply_eoff[g] + scales);
+        if (hipMalloc((void**)&p.reply_sent[g], sbytes) != hipSuccess ||
+            hipMalloc((void**)&p.reply_codes[g], cbytes) != hipSuccess) {
+            (void)hipGetLastError();
+            const bool on = p.reply;
+            free_reply(ctx, p);  // what this attempt did allocate; the part keeps its stage
+            p.reply = on;
+            return fail(FA_ERR_NOMEM, "mx8 reply: alloc of %zu + %zu B failed on GPU %zu", sbytes, cbytes, g);
+        }
+    }
+    return FA_OK;
+}
+
+// The reply stage on GPU g (fa.h "MX8 replies", rules 2-5), after everything else of the reducing call: the output
+// holds y.  Without `sent` the round is the bootstrap, sent := y; else one fused pass writes the codes, g' into
+// the output and g' into `sent`.  Range shards are cut at multiples of 64 elements (kShardUnit), so no block of 32
+// lies in two GPUs' ranges and rule 6's exchange of partial scales never arises here; a layout that cut
+// elsewhere would have to run fa_mx8_encode_device's two scale modes around a host wait, and is refused.
+int reply_stage(fa_ctx* ctx, Part& p, int g, hipStream_t st) {
+    if (int rc = ensure_reply_buf(ctx, p)) return rc;
+    const size_t cnt = p.cnt[(size_t)g], off = p.off[(size_t)g];
+    if (cnt == 0) return FA_OK;
+    if (off % FA_MX8_BLOCK != 0)
+        return fail(FA_ERR_STATE, "mx8 reply: part %d: the range of GPU %d starts at element %zu, inside a block", p.id, g, off);
+    char* sent = p.reply_sent[(size_t)g];
+    if (!p.reply_has_sent) {
+        FA_HIP(hipMemcpyAsync(sent, p.dout[(size_t)g], cnt * dsize(p.out), hipMemcpyDeviceToDevice, st));
+        return FA_OK;
+    }
+    char* q = p.reply_codes[(size_t)g];
+    FA_HIP(fa::launch_mx8_encode(p.dout[(size_t)g], sent, p.out, (uint64_t)off, (int64_t)cnt, reinterpret_cast<int8_t*>(q),
+                                 reinterpret_cast<uint8_t*>(q + p.reply_eoff[(size_t)g]), p.dout[(size_t)g], sent,
+                                 fa::kMx8EncFused, st));
+    return FA_OK;
+}
+
+// After reply_stage ran on every GPU: a round with `sent` left codes, the bootstrap left `sent`.
+void reply_round_done(Part& p) {
+    p.reply_has_codes = p.reply_has_sent;
+    p.reply_has_sent = true;
+    p.reply_counted = !p.reply_has_codes;
+    p.reply_nan = 0;
+}
+
 int clip_take_reference(Part& p, int g, int j, hipStream_t st) {
     const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
     if (cnt == 0) return FA_OK;
@@ -1808,11 +1890,18 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
                     rc = opt_on(tu, p.opt_master ? p.opt.rule : fa::kOptBoot, p.opt, avg, p.ox[(size_t)g] + lo,
                                 p.om[(size_t)g] + lo, opt_adaptive(p.opt.rule) ? p.ov[(size_t)g] + lo : nullptr, cnt,
                                 dst, p.out, st);
-                if (!rc && clip) rc = clip_take_reference(p, g, j, st);
+                // with a reply stage the output is not final yet: the reference is taken after it, below
+                if (!rc && clip && !p.reply) rc = clip_take_reference(p, g, j, st);
+                if (rc) return rc;
+            }
+            if (p.reply) {  // y -> g' over the GPU's whole range, then the clip stage's reference from g'
+                rc = reply_stage(ctx, p, g, st);
+                for (int j = 0; !rc && clip && j < p.npiece[(size_t)g]; ++j) rc = clip_take_reference(p, g, j, st);
                 if (rc) return rc;
             }
             mark_done(p, g, st);
         }
+        if (p.reply) reply_round_done(p);
         set_range_runs(p, G);
         if (p.opt.rule != FA_OPT_NONE) {  // one reducing call = one step (the first one without a master: none)
             if (p.opt_master) ++p.opt_steps;
@@ -2850,7 +2939,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     const bool clipped = ctx->clip > 0.0f && mode == FA_FEDAVG && !rs;  // takes the context's clip bound
     const bool noisy = ctx->noise > 0.0f && mode != FA_LITERAL && !rs;  // takes the context's noise stage
     const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged && !clipped &&
-                       !krummed && !geomedded && !noisy && !ctx->mx8;
+                       !krummed && !geomedded && !noisy && !ctx->mx8 && !ctx->mx8_reply;
     if (rs) {
         const size_t unit = G * kShardUnit;
         p.npad = (n_elems + unit - 1) / unit * unit;
@@ -2963,6 +3052,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
         }
     }
     p.mx8 = ctx->mx8 && mode != FA_LITERAL && !rs;
+    p.reply = ctx->mx8_reply && mode != FA_LITERAL && !rs;
     ctx->parts.emplace(part_id, std::move(p));
     return FA_OK;
 }
@@ -3624,17 +3714,171 @@ int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
     g_err.clear();
     Part* p;
     if (int rc = check_part(ctx, part_id, &p)) return rc;
-    if (!p->mx8) return fail(FA_ERR_STATE, "mx8: part %d does not take MX8 receipts (fa_set_mx8)", part_id);
+    if (!p->mx8 && !p->reply)
+        return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
+                                  "(fa_set_mx8_reply)", part_id);
     if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
     if (int rc = opt_quiesce(ctx)) return rc;  // the part's pending work, on whatever stream
+    if (p->reply)
+        if (int rc = ensure_reply_buf(ctx, *p)) return rc;
     const size_t so = dsize(p->out);
     for (int g = 0; g < ctx->G; ++g) {
         DeviceGuard dg(ctx->gpu[(size_t)g].dev);
-        if (p->cnt[(size_t)g])
-            FA_HIP(hipMemcpy(p->dout[(size_t)g], static_cast<const char*>(host_src) + p->off[(size_t)g] * so,
-                             p->cnt[(size_t)g] * so, hipMemcpyHostToDevice));
+        if (!p->cnt[(size_t)g]) continue;
+        const char* src = static_cast<const char*>(host_src) + p->off[(size_t)g] * so;
+        FA_HIP(hipMemcpy(p->dout[(size_t)g], src, p->cnt[(size_t)g] * so, hipMemcpyHostToDevice));
+        if (p->reply)  // the owners hold it: the next reply is taken against it
+            FA_HIP(hipMemcpy(p->reply_sent[(size_t)g], src, p->cnt[(size_t)g] * so, hipMemcpyHostToDevice));
     }
+    if (p->reply) p->reply_has_sent = true;
     set_range_runs(*p, ctx->G);  // as a round's output: the reference, and what fa_copy_output hands out
+    return FA_OK;
+}
+
+int fa_mx8_encode_device(fa_ctx* ctx, int gpu, const void* d_new, fa_dtype new_dtype, const void* d_sent,
+                         fa_dtype sent_dtype, size_t n, uint64_t idx0, int8_t* d_q, uint8_t* d_e, void* d_out, int flags,
+                         void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (!dvalid(new_dtype) || !dvalid(sent_dtype)) return fail(FA_ERR_ARG, "bad dtype");
+    if (new_dtype != sent_dtype)
+        return fail(FA_ERR_ARG, "mx8 reply: the new model is %s, the sent one %s: one dtype", fa::dtype_name(new_dtype),
+                    fa::dtype_name(sent_dtype));
+    if (flags & ~(FA_MX8_SCALES_ONLY | FA_MX8_SCALES_GIVEN)) return fail(FA_ERR_ARG, "mx8 reply: unknown flags 0x%x", flags);
+    if ((flags & FA_MX8_SCALES_ONLY) && (flags & FA_MX8_SCALES_GIVEN))
+        return fail(FA_ERR_ARG, "mx8 reply: FA_MX8_SCALES_ONLY and FA_MX8_SCALES_GIVEN exclude each other");
+    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "mx8 reply: idx0 + n beyond 2^64");
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) return FA_OK;
+    const bool only = (flags & FA_MX8_SCALES_ONLY) != 0;
+    if (!d_new || !d_sent || !d_e || (!only && !d_q))
+        return fail(FA_ERR_ARG, "mx8 reply: %s pointer is null", !d_new ? "d_new" : !d_sent ? "d_sent" : !d_e ? "d_e" : "d_q");
+    const size_t es = dsize(new_dtype);
+    if (!aligned(d_new, es) || !aligned(d_sent, es) || (!only && d_out && !aligned(d_out, es)))
+        return fail(FA_ERR_ALIGN, "mx8 reply: %s not %zu-byte aligned", !aligned(d_new, es) ? "d_new" : !aligned(d_sent, es) ? "d_sent" : "d_out", es);
+    if (!only && d_out) {  // the same address as an input, or apart from it
+        const uintptr_t o = (uintptr_t)d_out, bytes = (uintptr_t)(n * es);
+        for (const void* in : {d_new, d_sent}) {
+            const uintptr_t a = (uintptr_t)in;
+            if (o != a && o < a + bytes && a < o + bytes)
+                return fail(FA_ERR_ARG, "mx8 reply: d_out overlaps %s without being it", in == d_new ? "d_new" : "d_sent");
+        }
+    }
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    const int mode = only ? fa::kMx8EncScalesOnly : (flags & FA_MX8_SCALES_GIVEN) ? fa::kMx8EncScalesGiven : fa::kMx8EncFused;
+    FA_HIP(fa::launch_mx8_encode(d_new, d_sent, new_dtype, idx0, (int64_t)n, d_q, d_e, only ? nullptr : d_out, nullptr, mode,
+                                 c.s));
+    return FA_OK;
+}
+
+int fa_set_mx8_reply(fa_ctx* ctx, int part_id, int on) {
+    g_err.clear();
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (on && (ctx->flags & FA_SHARD_CLIENT_RS))
+        return fail(FA_ERR_ARG, "mx8 reply: not on an FA_SHARD_CLIENT_RS context (use FA_SHARD_RANGE)");
+    if (part_id < 0) {
+        ctx->mx8_reply = on != 0;
+        return FA_OK;
+    }
+    Part* p;
+    if (int rc = check_part(ctx, part_id, &p)) return rc;
+    if (on && p->mode == FA_LITERAL) return fail(FA_ERR_ARG, "mx8 reply: part %d is an FA_LITERAL part", part_id);
+    if (!on) {
+        if (p->reply)  // the buffers may still be in use
+            if (int rc = opt_quiesce(ctx)) return rc;
+        free_reply(ctx, *p);
+        return FA_OK;
+    }
+    if (p->reply) return FA_OK;
+    // what this round kept host-side or chained so far goes back to the plain path
+    if (int rc = host_flush(ctx, *p)) return rc;
+    restart_round_plain(*p);
+    p->reply = true;
+    return FA_OK;
+}
+
+namespace {
+
+// D2H of the codes of the part's last reducing call, ordered after it as copy_output is; counts the E = 255 blocks
+// on the way.  A block's scale byte lies in one GPU's range (reply_stage), so the copies do not overlap.
+int copy_mx8_codes(fa_ctx* ctx, Part& p, int8_t* q, uint8_t* e) {
+    const int G = ctx->G;
+    for (int g = 0; g < G; ++g) {
+        GpuRes& r = ctx->gpu[(size_t)g];
+        const size_t cnt = p.cnt[(size_t)g], off = p.off[(size_t)g];
+        if (!cnt) continue;
+        DeviceGuard dg(r.dev);
+        hipStream_t ds = p.done_stream[(size_t)g];
+        if (ds && ds != r.compute) {
+            FA_HIP(hipEventRecord(p.done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(r.compute, p.done[(size_t)g], 0));
+        }
+        const char* src = p.reply_codes[(size_t)g];
+        if (q) FA_HIP(hipMemcpyAsync(q + off, src, cnt, hipMemcpyDeviceToHost, r.compute));
+        FA_HIP(hipMemcpyAsync(e + (off >> 5), src + p.reply_eoff[(size_t)g], ((off + cnt - 1) >> 5) - (off >> 5) + 1,
+                              hipMemcpyDeviceToHost, r.compute));
+    }
+    for (int g = 0; g < G; ++g) {
+        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
+        FA_HIP(hipStreamSynchronize(ctx->gpu[(size_t)g].compute));
+    }
+    uint64_t nan = 0;
+    for (size_t b = 0, B = fa_mx8_scale_bytes(p.n); b < B; ++b) nan += e[b] == 255;
+    p.reply_nan = nan;
+    p.reply_counted = true;
+    return FA_OK;
+}
+
+int check_mx8_dst(const Part& p, const void* q, const void* e, int flags) {
+    if (flags & ~FA_HOST_PINNED) return fail(FA_ERR_ARG, "unknown flags 0x%x", flags);
+    if (p.n && (!q || !e)) return fail(FA_ERR_ARG, "mx8 reply: %s is null", !q ? "q" : "e");
+    return FA_OK;
+}
+
+}  // namespace
+
+int fa_finalize_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags) {
+    g_err.clear();
+    Trace tr("fa_finalize_mx8 part %d", part_id);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc || (rc = check_mx8_dst(*p, q, e, flags))) return rc;
+    // the round as it stands decides, before any work: reduced already, it has codes or not; else it will have
+    // them if the owners hold a model
+    if (!p->reply || (p->ready ? !p->reply_has_codes : !p->reply_has_sent))
+        return fail(FA_ERR_STATE, "mx8 reply: part %d has %s: finish the round with fa_finalize", part_id,
+                    !p->reply ? "no reply stage (fa_set_mx8_reply)" : "no sent model yet (the bootstrap round)");
+    if (p->n_submitted != p->D)
+        return fail(FA_ERR_STATE, "part %d: %d of %d clients submitted", part_id, p->n_submitted, p->D);
+    if (!p->ready && (rc = reduce_part(ctx, *p, p->w.data(), nullptr))) return rc;
+    if (p->n && (rc = copy_mx8_codes(ctx, *p, q, e))) return rc;
+    reset_round(*p);
+    return FA_OK;
+}
+
+int fa_copy_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc || (rc = check_mx8_dst(*p, q, e, flags))) return rc;
+    if (!p->reply || !p->reply_has_codes)
+        return fail(FA_ERR_STATE, "mx8 reply: part %d has no codes (%s)", part_id,
+                    !p->reply ? "no reply stage" : "no reducing call yet, or the last one was the bootstrap");
+    return p->n ? copy_mx8_codes(ctx, *p, q, e) : FA_OK;
+}
+
+int fa_mx8_reply_stats(fa_ctx* ctx, int part_id, uint64_t* nan_blocks) {
+    g_err.clear();
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (!p->reply) return fail(FA_ERR_STATE, "mx8 reply: part %d has no reply stage (fa_set_mx8_reply)", part_id);
+    if (!p->reply_counted && p->n) {  // nobody fetched the codes yet: the scale bytes alone
+        std::vector<uint8_t> e(fa_mx8_scale_bytes(p->n));
+        if ((rc = copy_mx8_codes(ctx, *p, nullptr, e.data()))) return rc;
+    }
+    if (nan_blocks) *nan_blocks = p->reply_nan;
     return FA_OK;
 }
 

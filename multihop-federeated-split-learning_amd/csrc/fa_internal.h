@@ -165,6 +165,17 @@ hipError_t launch_mx8_expand(const int8_t* q, const uint8_t* e, uint64_t idx0, i
 // The codec on the host (fa_mx8_decode: the kernel's own multiply and scale; fa_mx8_encode: the owner's side).
 void mx8_decode_host(const int8_t* q, const uint8_t* e, size_t n, uint64_t idx0, float* d);
 void mx8_encode_host(const float* delta, size_t n, int8_t* q, uint8_t* e);
+// MX8 replies (fa.h "MX8 replies"), fa_mx8_enc.hip.  Over n elements of dtype dt: delta_i = fl(widen(y[i]) -
+// widen(sent[i])); mode 0 (fused): e := the scales of the blocks of bucket elements [idx0, idx0 + n) from the deltas
+// of this launch (e[0]: block idx0 >> 5), q := their codes, and out, out2 (each nullable) := g' = fl(widen(sent[i]) +
+// d_i), rounded once to dt; mode 1 (scales only): e alone is written; mode 2 (scales given): e is read, the rest as
+// mode 0.  out and out2 may each be y or sent exactly (a lane reads its elements before it writes any); q and e
+// overlap nothing.  Any pointers of element alignment: mx8_enc_split (host-only) says which form a fused launch takes.
+enum { kMx8EncFused = 0, kMx8EncScalesOnly = 1, kMx8EncScalesGiven = 2 };
+Split mx8_enc_split(const void* y, const void* sent, fa_dtype dt, uint64_t idx0, size_t n, const void* q,
+                    const void* out, const void* out2);
+hipError_t launch_mx8_encode(const void* y, const void* sent, fa_dtype dt, uint64_t idx0, int64_t n, int8_t* q,
+                             uint8_t* e, void* out, void* out2, int mode, hipStream_t s);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
                        const Tuning& tu, hipStream_t s);

@@ -8,7 +8,8 @@
 // Bit-exactness: `#pragma clang fp contract(off)` at file scope and in every function with fp32 arithmetic, as in
 // fa_clip.hip: fl(g + fl(q s)) is two roundings and an fma would make it one.  The scale is made from E by
 // integer arithmetic on the bit pattern (mx8_scale_bits: a subnormal pattern below E = 7, a quiet NaN for 255), so
-// no library function stands between the rule and the bits; the same function serves the host decoder.
+// no library function stands between the rule and the bits; the same function serves the host decoder.  It lies in
+// fa_mx8.h with the rest that the encoder (fa_mx8_enc.hip) shares.
 //
 // Two forms by fa::Split (fa_split.h), led by q with one byte per element: a vector is 16 elements.  The vector form
 // gives a lane the 16 q bytes at elements head + 16 i .. + 15 in one non-temporal load, the 64 (f32) or 32 (16-bit)
@@ -25,6 +26,7 @@
 
 #include "fa_device.h"
 #include "fa_internal.h"
+#include "fa_mx8.h"
 
 #pragma clang fp contract(off)
 
@@ -32,42 +34,7 @@ namespace fa {
 
 namespace {
 
-// The fp32 bit pattern of block scale E: 2^(E - 133) for E in 0 .. 254 (biased exponent E - 6 from E = 7 on, below it
-// the subnormal with bit E + 16 set), a quiet NaN for 255, which makes every product of the block one.
-__host__ __device__ __forceinline__ uint32_t mx8_scale_bits(uint32_t E) {
-    return E == 255u ? 0x7fc00000u : E >= 7u ? (E - 6u) << 23 : 1u << (E + 16u);
-}
-__host__ __device__ __forceinline__ float mx8_scale(uint32_t E) {
-    return __builtin_bit_cast(float, mx8_scale_bits(E));
-}
-// Rule 2: d = fl((float)q * s), one multiply; rule 3: x = fl(g + d), one add.
-__host__ __device__ __forceinline__ float mx8_delta(int q, float s) {
-#pragma clang fp contract(off)
-    return (float)q * s;
-}
-__device__ __forceinline__ float mx8_add(float g, float d) {
-#pragma clang fp contract(off)
-    return g + d;
-}
-
 struct NoRef {};  // absolute mode: x = d
-
-// 16 elements of the reference at element e (16-byte aligned there), widened.
-template <typename REF>
-__device__ __forceinline__ void load_ref16(const void* ref, int64_t e, float* g) {
-    const REF* p = reinterpret_cast<const REF*>(ref) + e;
-#pragma unroll
-    for (int j = 0; j < 16; j += In<REF>::kVec) In<REF>::widen(ld16<false>(p + j), g + j);
-}
-template <typename DST>
-__device__ __forceinline__ void store16(void* dst, int64_t e, const float* x) {
-    if constexpr (sizeof(DST) == 4) {
-        Out<DST>::template store<16, kStPlain>(dst, e, x);
-    } else {
-        Out<DST>::template store<8, kStPlain>(dst, e, x);
-        Out<DST>::template store<8, kStPlain>(dst, e + 8, x + 8);
-    }
-}
 
 // Vector form: lane i of the grid owns vector i, elements head + 16 i .. + 15 of q, ref and dst; g0 = idx0 + head is
 // the bucket index of the first of them, b0 = idx0 >> 5 the block e[0] scales.

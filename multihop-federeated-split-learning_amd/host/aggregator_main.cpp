@@ -100,6 +100,9 @@ struct Options {
     // int8 parameter (the codes) and one uint8 buffer (the scales) is an owner's update against the reply it last
     // loaded, expanded on the GPU (fa_submit_mx8)
     bool mx8 = false;
+    // --mx8-reply (implies --mx8): the buckets have the MX8 reply stage (fa_set_mx8_reply on the context); an owner
+    // whose receipt of the round was an MX8 archive gets the new model back as one, its own archive the template
+    bool mx8_reply = false;
     bool gpu_crc = true;  // --crc gpu|host: the reply records' CRC-32s from the GPU (fa_output_crc32) or the host
     std::map<int, double> samples;  // client id -> n_k
     // --server-opt RULE --server-lr L [--server-beta1 B] [--server-beta2 B] [--server-tau T]: the server
@@ -273,7 +276,7 @@ void usage() {
                  "       [--krum-f F [--krum-m M]]\n"
                  "       [--geomed-iters T [--geomed-nu NU]]\n"
                  "       [--dp-noise-multiplier Z [--dp-seed S]]\n"
-                 "       [--mx8]\n"
+                 "       [--mx8] [--mx8-reply]\n"
                  "--mode trimmed: per element the T lowest and T highest of the owners' values are dropped and the\n"
                  "rest averaged (2T < DATA_OWNERS <= 128; without --trim, and with --mode median, the median), so up\n"
                  "to T owners that send NaN, inf or huge values change no reply; --samples is ignored; not with\n"
@@ -312,6 +315,10 @@ void usage() {
                  "elements; it is expanded on the GPU and counts as that owner's receipt.  A bucket is still defined by its\n"
                  "first full receipt, which is also the reply's template, and needs one reduced round before it takes MX8\n"
                  "receipts (exit 1 otherwise); a round may mix both kinds; not with --mode literal or --layout rs.\n"
+                 "--mx8-reply (implies --mx8): an owner whose receipt of the round was an MX8 archive gets the new model\n"
+                 "back as one -- its own archive with the codes and scales of new model minus the model it was last sent,\n"
+                 "which it adds to that model (decode rule 3); every other owner gets the full reply, which then holds\n"
+                 "that same sum.  The round line reports mx8_replies, mx8_bytes_out and mx8_nan_blocks.\n"
                  "A bucket takes the dtype of its first receipt's parameters (all fp32, all bf16 or all fp16, by\n"
                  "their storage type) and is reduced and replied in it; a later receipt of another size or dtype\n"
                  "ends the process (exit 1).\n";
@@ -340,6 +347,7 @@ bool parse_args(int argc, char** argv, Options* o) {
         else if (a == "--eager") o->eager = true;
         else if (a == "--test-shared-device") o->shared_device = true;
         else if (a == "--mx8") o->mx8 = true;
+        else if (a == "--mx8-reply") o->mx8 = o->mx8_reply = true;
         else if (a == "--rs-chunks") o->rs_chunks = std::atoi(val("--rs-chunks"));
         else if (a == "--stall-report") o->stall_report_s = std::atof(val("--stall-report"));
         else if (a == "--receipt-timeout") o->receipt_timeout_s = std::atof(val("--receipt-timeout"));
@@ -435,7 +443,8 @@ bool parse_args(int argc, char** argv, Options* o) {
         }
     }
     if (o->mx8 && (o->mode == FA_LITERAL || o->rs)) {
-        std::cerr << "--mx8 expands an update against the bucket's last output on the GPU that holds it: not with "
+        std::cerr << (o->mx8_reply ? "--mx8-reply implies --mx8, which" : "--mx8")
+                  << " expands an update against the bucket's last output on the GPU that holds it: not with "
                   << (o->rs ? "--layout rs" : "--mode literal") << "\n";
         return false;
     }
@@ -674,6 +683,7 @@ public:
         if (o.krum_given) FA_CHECK(fa_set_krum(ctx_, -1, o.krum_f, o.krum_m));
         if (o.geomed_given) FA_CHECK(fa_set_geomed(ctx_, -1, o.geomed_iters, o.geomed_nu));
         if (o.mx8) FA_CHECK(fa_set_mx8(ctx_, -1, 1));  // before any bucket
+        if (o.mx8_reply) FA_CHECK(fa_set_mx8_reply(ctx_, -1, 1));
         if (o.rs_chunks > 0) {
             fa_tuning t{};
             t.rs_chunks = o.rs_chunks;
@@ -883,6 +893,7 @@ public:
         ledger_.accept(r.client_id, r.model_part, key);
         const bool first = b.arrived.insert(r.client_id).second;
         b.last = r;  // template of the reply: the last full receipt (its buffers travel back, as in the reference)
+        b.mx8_from.erase(r.client_id);  // a full receipt after an MX8 one of the same round: a full reply
         st_.absorb_s += secs_since(t0);
         if (!first) {
             std::cerr << "[aggregator] part " << r.model_part << ": owner " << r.client_id << " sent it again\n";
@@ -916,6 +927,7 @@ public:
         b.bytes_in += r.blob_len;
         ++mx8_receipts_;
         mx8_bytes_ += r.blob_len;
+        if (o_.mx8_reply) b.mx8_from[r.client_id] = r;  // the template of this owner's reply
         ledger_.accept(r.client_id, r.model_part, key);
         const bool first = b.arrived.insert(r.client_id).second;
         st_.absorb_s += secs_since(t0);
@@ -931,13 +943,79 @@ public:
         mx8_receipts_ = mx8_bytes_ = 0;
         return v;
     }
+    // This round's MX8 replies, their archive bytes and the E = 255 blocks of its codes; reading them starts the next
+    // round's count.
+    struct Mx8Out {
+        unsigned long long replies, bytes, nan_blocks;
+    };
+    Mx8Out take_mx8_out() {
+        const Mx8Out v{mx8_replies_, mx8_bytes_out_, mx8_nan_blocks_};
+        mx8_replies_ = mx8_bytes_out_ = mx8_nan_blocks_ = 0;
+        return v;
+    }
+
+    // The replies of one bucket: the full one (null when every owner gets its own) and, by owner id, the MX8 ones.
+    struct Replies {
+        std::shared_ptr<const Bytes> full;
+        std::map<int, std::shared_ptr<const Bytes>> mx8;
+    };
+    std::vector<int> destinations() const {  // node 0 and the data owners i + c + 1, i < D - 1
+        std::vector<int> ids = {0};
+        for (int i = 0; i < o_.data_owners - 1; ++i) ids.push_back(i + o_.compute_nodes + 1);
+        return ids;
+    }
+
+    // --mx8-reply: the MX8 replies of bucket mp for the owners whose receipt of this round was an MX8 archive, each
+    // the owner's own archive with the round's codes and scales in its two records (TorchArchive::with_mx8_into).
+    // The codes come from fa_finalize_mx8, which ends the round, when nobody needs the full reply, else from
+    // fa_copy_mx8 after the full reply ended it.
+    void mx8_replies(int mp, bool round_open, Replies* out) {
+        auto& b = buckets_[mp];
+        std::vector<int8_t> q(b.numel);
+        std::vector<uint8_t> e(fa_mx8_scale_bytes(b.numel));
+        FA_CHECK(round_open ? fa_finalize_mx8(ctx_, mp, q.data(), e.data(), 0) : fa_copy_mx8(ctx_, mp, q.data(), e.data(), 0));
+        for (auto& kv : b.mx8_from) {
+            const Receipt& r = kv.second;
+            TorchArchive ar;
+            std::string err;
+            Message m;
+            m.type = OPERATION;
+            m.client_id = o_.id;
+            m.prev_node = o_.id;
+            m.type_op = AGGREGATION;
+            m.model_part = mp;
+            m.t_start = now_ms();
+            char* values = nullptr;
+            std::shared_ptr<Bytes> f;
+            if (ar.parse(r.blob(), r.blob_len, &err)) f = operation_frame(m, ar.size(), &values);
+            if (!f || !ar.with_mx8_into(q.data(), e.data(), (int64_t)b.numel, (uint8_t*)values, &err)) {
+                std::cerr << "[aggregator] MX8 reply for part " << mp << " to owner " << kv.first << ": " << err << "\n";
+                std::exit(1);
+            }
+            out->mx8[kv.first] = f;
+            ++mx8_replies_;
+            mx8_bytes_out_ += ar.size();
+        }
+    }
 
     // Reduces bucket mp and returns the framed reply, built once and shared by every destination:
     // the last receipt's archive around the reduced parameters, which the D2H copy writes straight
     // into the frame's parameter records.
-    std::shared_ptr<const Bytes> reduce(int mp) {
+    Replies reduce(int mp) {
         Bucket& b = buckets_[mp];
         const auto t0 = std::chrono::steady_clock::now();
+        Replies out;
+        // owners without an MX8 receipt this round get the full reply; with none of them its D2H is skipped
+        bool need_full = b.mx8_from.empty();
+        for (int id : destinations()) need_full = need_full || !b.mx8_from.count(id);
+        if (!need_full) {
+            const auto t1 = std::chrono::steady_clock::now();
+            mx8_replies(mp, true, &out);
+            round_stats(mp);
+            end_round(mp);
+            st_.finalize_s += secs_since(t1);
+            return out;
+        }
         TorchArchive ar;
         std::string err;
         if (!ar.parse(b.last.blob(), b.last.blob_len, &err)) {
@@ -976,6 +1054,35 @@ public:
                 std::cerr << "[aggregator] reply for part " << mp << ": " << err << "\n";
                 std::exit(1);
             }
+        }
+        if (!b.mx8_from.empty()) mx8_replies(mp, false, &out);
+        round_stats(mp);
+        end_round(mp);
+        st_.finalize_s += t_fin;
+        st_.frame_s += secs_since(t0) - t_fin;
+        out.full = f;
+        return out;
+    }
+
+    void end_round(int mp) {
+        auto& b = buckets_[mp];
+        b.held.clear();
+        b.arrived.clear();
+        b.mx8_from.clear();
+        b.bytes_in = 0;
+        b.reduced = true;
+    }
+
+    // What the stages made of bucket mp's receipts in the reducing call just made, for the round line.
+    void round_stats(int mp) {
+        if (o_.mx8_reply) {
+            uint64_t nan = 0;
+            FA_CHECK(fa_mx8_reply_stats(ctx_, mp, &nan));
+            mx8_nan_blocks_ += nan;
+            if (nan)
+                std::cerr << "[aggregator] MX8 REPLY: part " << mp << ": " << nan << " blocks of the new model are NaN (a "
+                          << "NaN or an inf in the aggregate or in the model last sent); they stay NaN until the "
+                          << "aggregator is restarted\n";
         }
         if (o_.clip_given) {  // what the clip stage did to this bucket's receipts, for the round line
             std::vector<double>& q = clip_q_[mp];
@@ -1019,19 +1126,14 @@ public:
                 std::cerr << "[aggregator] BULYAN: part " << mp << ": NO OWNER PICKED (every score is infinite): the "
                           << "reply of this bucket is all zeros\n";
         }
-        b.held.clear();
-        b.arrived.clear();
-        b.bytes_in = 0;
-        b.reduced = true;
-        st_.finalize_s += t_fin;
-        st_.frame_s += secs_since(t0) - t_fin;
-        return f;
     }
 
     // Fan-out to node 0 and the data owners i + c + 1, i < D - 1 (aggregator.cpp:102-106, :158-164).
-    void fan_out(const std::shared_ptr<const Bytes>& f) {
-        net_->send(0, f);
-        for (int i = 0; i < o_.data_owners - 1; ++i) net_->send(i + o_.compute_nodes + 1, f);
+    void fan_out(const Replies& r) {
+        for (int id : destinations()) {
+            auto it = r.mx8.find(id);
+            net_->send(id, it != r.mx8.end() ? it->second : r.full);
+        }
     }
 
     // --server-state: every defined bucket's x, m, v and steps (parts read at startup and never defined in this
@@ -1361,6 +1463,7 @@ private:
         bool reduced = false; // a round of this bucket was reduced: its output can take an MX8 update
         std::vector<std::shared_ptr<const Bytes>> held;  // pinned frames DMA'd from, until finalize
         std::set<int> arrived;  // client ids received this round
+        std::map<int, Receipt> mx8_from;  // --mx8-reply: this round's MX8 receipts by owner, their replies' templates
     };
 
     int slot_of(int client) {
@@ -1424,6 +1527,7 @@ private:
     std::set<int> phase_mps_;
     unsigned long long streamed_ = 0, stream_fallbacks_ = 0, streamed_bytes_ = 0;
     unsigned long long mx8_receipts_ = 0, mx8_bytes_ = 0;  // --mx8: this round's
+    unsigned long long mx8_replies_ = 0, mx8_bytes_out_ = 0, mx8_nan_blocks_ = 0;  // --mx8-reply: this round's
 };
 
 // The next receipt, with the failure detection the reference lacks (its receive loop blocks forever on a
@@ -1590,7 +1694,7 @@ int main(int argc, char** argv) {
         for (int mp = 2; mp <= L + 1; ++mp) in2 += agg.bytes_in(mp);
         agg.end_phase();
         auto t3 = std::chrono::steady_clock::now();
-        std::vector<std::shared_ptr<const Bytes>> replies;
+        std::vector<Aggregator::Replies> replies;
         agg.reduce_all(mps);
         for (int mp : mps) replies.push_back(agg.reduce(mp));
         const double red2 = secs_since(t3);
@@ -1613,6 +1717,13 @@ int main(int argc, char** argv) {
             char buf[96];
             snprintf(buf, sizeof buf, ",\"mx8_receipts\":%llu,\"mx8_bytes_in\":%llu", mx.first, mx.second);
             mx8_tail = buf;
+            if (o.mx8_reply) {
+                const auto mo = agg.take_mx8_out();
+                char obuf[128];
+                snprintf(obuf, sizeof obuf, ",\"mx8_replies\":%llu,\"mx8_bytes_out\":%llu,\"mx8_nan_blocks\":%llu",
+                         mo.replies, mo.bytes, mo.nan_blocks);
+                mx8_tail += obuf;
+            }
         }
         const std::string clip_tail = mx8_tail +
             (o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : o.geomed_given ? agg.geomed_tail() : o.bulyan ? agg.bulyan_tail() : std::string()) + (o.dp_given ? agg.dp_tail() : std::string());

@@ -773,6 +773,44 @@ bool TorchArchive::mx8_view(const int8_t** q, const uint8_t** e, int64_t* n) con
     return true;
 }
 
+bool TorchArchive::with_mx8_into(const int8_t* q, const uint8_t* e, int64_t n, uint8_t* dst, std::string* err) const {
+    const int8_t* tq = nullptr;
+    const uint8_t* te = nullptr;
+    int64_t tn = 0;
+    if (!mx8_view(&tq, &te, &tn)) return fail(err, "the template is no MX8 archive");
+    if (tn != n) return fail(err, "the template holds " + std::to_string(tn) + " codes, the reply " + std::to_string(n));
+    if (n > 0 && (!q || !e || !dst)) return fail(err, "null codes, scales or destination");
+    const TensorView* views[2] = {&params_[0], &buffers_[0]};
+    if (views[0]->record == views[1]->record) return fail(err, "codes and scales share a record");
+    for (const TensorView* t : views) {  // where this record's CRC-32 is written
+        const ZipEntry& z = entries_[(size_t)t->record];
+        const uint64_t local = z.desc_offset ? z.desc_offset : z.local_offset + 14;
+        if (z.cd_offset > size_ || size_ - z.cd_offset < 20 || local > size_ || size_ - local < 4)
+            return fail(err, "a record's header lies outside the archive");
+        // neither CRC field may lie inside a record's data, which is written first
+        for (const TensorView* u : views) {
+            const ZipEntry& zu = entries_[(size_t)u->record];
+            for (uint64_t at : {z.cd_offset + 16, local})
+                if (at + 4 > zu.data_offset && at < zu.data_offset + zu.size)
+                    return fail(err, "a record's header lies inside a record");
+        }
+    }
+    std::memcpy(dst, base_, size_);
+    const uint8_t* src[2] = {reinterpret_cast<const uint8_t*>(q), e};
+    for (int k = 0; k < 2; ++k) {
+        const TensorView& t = *views[k];
+        if (t.numel > 0) std::memcpy(dst + (t.data - base_), src[k], (size_t)t.numel);
+    }
+    for (const TensorView* t : views) {
+        const ZipEntry& z = entries_[(size_t)t->record];
+        const uint32_t c = crc32(dst + z.data_offset, (size_t)z.size);
+        wr32(dst + z.cd_offset + 16, c);
+        if (z.desc_offset) wr32(dst + z.desc_offset, c);
+        else wr32(dst + z.local_offset + 14, c);
+    }
+    return true;
+}
+
 bool TorchArchive::param_segments(std::vector<const void*>* ptrs, std::vector<size_t>* bytes) const {
     ptrs->clear();
     bytes->clear();

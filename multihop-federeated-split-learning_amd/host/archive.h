@@ -69,6 +69,12 @@ public:
     // writes.  These are bytes from the wire: both views are checked again against the record they point into and the
     // record against the archive, whatever parse() accepted.  False (nothing written) otherwise.
     bool mx8_view(const int8_t** q, const uint8_t** e, int64_t* n) const;
+    // An MX8 reply (fa.h "MX8 replies") from an MX8 receipt as the template: a copy of the archive in dst[0, size())
+    // with the codes replaced by q (n bytes) and the scales by e (ceil(n / 32) bytes), and the CRC-32 of their two
+    // records recomputed where the archive stores it (central directory; data descriptor or local header).  The
+    // template came from the wire: mx8_view's checks are made again, n must be its n, the two tensors must lie in
+    // different records, and every header field written must lie inside the archive.  False, dst untouched, otherwise.
+    bool with_mx8_into(const int8_t* q, const uint8_t* e, int64_t n, uint8_t* dst, std::string* err) const;
 
     // Contiguous pieces of the parameter bucket, in order (one per contiguous param, fp32, bf16 or fp16
     // throughout): a gather list for fa_submit_gather.  False if some param is strided or the types mix.
