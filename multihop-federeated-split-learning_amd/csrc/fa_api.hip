@@ -1,7 +1,7 @@
 // fa_api.hip -- the C ABI (include/fedavg/fa.h): aggregation context, device
 // slots, pinned staging, multi-GPU layouts (range shards; client shards + an
 // RCCL reduce-scatter), batched and accumulate-on-arrival reductions, and the
-// raw device entry.
+// raw device entry.  The aggregation stages and their entries: fa_stages.hip.
 //
 // What it replaces in the reference (paths relative to the reference root):
 //   fa_create / fa_bucket_define  <- systemAPI(true,-1,..) + refactor() ->
@@ -16,50 +16,12 @@
 //       (aggregator.cpp:96-106, :153-166).
 // No CPU fallback exists: without a gfx950 device every entry that needs one
 // returns FA_ERR_NODEV.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-#include <rocprofiler-sdk-roctx/roctx.h>
+#include "fa_host.h"
 
-#include <algorithm>
-#include <cmath>
-#include <condition_variable>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-
-#include "fa_internal.h"
-
-namespace {
+namespace fah {
 
 thread_local std::string g_err;
 
-constexpr size_t kSkewAuto = SIZE_MAX;  // fa_tuning.slot_skew -2: chosen per bucket by slot_skew_for
-
-// Per-context tuning (fa_ctx_set_tuning); fa_set_tuning sets the process defaults that new contexts and
-// context-less fa_reduce_device calls start from.
-struct CtxTuning {
-    // block 128, one-shot grid, 16 clients per load group, nt loads, write-through (sc1) stores, phased
-    // walk with the larger register stage where a bucket holds a phase (tools/sweep.py over 3
-    // pools, profiles/r01_summary.json: sc1 stores 2.7% faster than nt, unroll 16 ~1% faster than 8,
-    // block 128 2-3% faster than 256; the phased walk 1.269 ms on the north star in every pool).
-    fa::Tuning tu{128, 0, 16, 1, 2, 4};
-    // Byte skew between consecutive client slots of one bucket (see slot_stride); kSkewAuto = by slot size.
-    size_t slot_skew = kSkewAuto;
-    // FA_SHARD_CLIENT_RS: pieces per round (the reduce-scatter of piece c overlaps the reduce of c+1).
-    int rs_chunks = 8;
-    // Range pieces (piece_len_for): bytes of slots per piece (0 = never cut) and the span of a GPU's slots
-    // above which they are cut.
-    size_t piece_span = size_t(16) << 30;
-    size_t piece_split = size_t(48) << 30;
-};
 std::mutex g_defaults_mu;
 CtxTuning g_defaults;
 
@@ -67,17 +29,6 @@ CtxTuning defaults() {
     std::lock_guard<std::mutex> g(g_defaults_mu);
     return g_defaults;
 }
-
-// A roctx range around a host-side entry (submit, finalize, batched reduce, ...), so that
-// `rocprofv3 --marker-trace` shows the aggregation round's host phases beside its kernels and copies.
-struct Trace {
-    explicit Trace(const char* fmt, int a = -1, int b = -1) {
-        char buf[96];
-        snprintf(buf, sizeof buf, fmt, a, b);
-        roctxRangePushA(buf);
-    }
-    ~Trace() { roctxRangePop(); }
-};
 
 int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -89,46 +40,8 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define FA_HIP(call)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail(FA_ERR_HIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                                          __FILE__, __LINE__);                                     \
-    } while (0)
-
-#define FA_NCCL(call)                                                                                   \
-    do {                                                                                                \
-        ncclResult_t r_ = (call);                                                                       \
-        if (r_ != ncclSuccess) return fail(FA_ERR_NCCL, "%s: %s (%s:%d)", #call, ncclGetErrorString(r_), \
-                                           __FILE__, __LINE__);                                         \
-    } while (0)
-
-inline size_t dsize(fa_dtype t) { return t == FA_F32 ? 4 : 2; }
-inline bool dvalid(int t) { return t == FA_F32 || t == FA_BF16 || t == FA_F16; }
-// The refusal of a dtype pair the kernels do not have (fa::dtype_pair_ok): bf16 <-> f16.
-#define FA_PAIR(in, out)                                                                                    \
-    do {                                                                                                    \
-        if (!fa::dtype_pair_ok((fa_dtype)(in), (fa_dtype)(out)))                                            \
-            return fail(FA_ERR_ARG, "no %s -> %s reduction (a 16-bit bucket keeps its type or goes through f32)", \
-                        fa::dtype_name((fa_dtype)(in)), fa::dtype_name((fa_dtype)(out)));                   \
-    } while (0)
-
-// Restores the caller's current device on scope exit.
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dev >= 0 && dev != prev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-constexpr size_t kStageBytes = 32u << 20;  // pinned staging chunk per buffer
 constexpr size_t kShardUnit = 64;          // range shards / rs pieces: multiples of 64 elements (16-B phase kept)
 constexpr int kMaxSegments = 256;          // buckets per batched launch
-constexpr int kSegRing = 4;                // device segment tables per GPU (GpuRes::seg)
 // Small receipts read in place (host_keep / host_reduce): a one-GPU range part whose D receipts total at most
 // kHostReadMax bytes, in pinned memory, is reduced by kernels that read the receipts' segments over PCIe,
 // in at most kHostReadPieces launches (the pieces on which every receipt and the destination are contiguous)
@@ -136,91 +49,11 @@ constexpr size_t kHostReadMax = FA_HOST_READ_MAX_BYTES;
 constexpr size_t kHostReadPieces = 16;
 constexpr int kNotHostReadable = 1;  // host_reduce: the path does not apply (nothing was launched)
 
-// Host memcpy into / out of the pinned staging chunks, split over worker threads:
-// one thread copies ~8-10 GB/s, a PCIe Gen5 x16 link takes ~50 GB/s.  One pool per GPU, so the GPUs of a
-// range-sharded context stage their pieces concurrently.
-class CopyPool {
-public:
-    explicit CopyPool(int n) : n_(std::max(1, n)) {
-        for (int i = 1; i < n_; ++i) th_.emplace_back([this, i] { loop(i); });
-    }
-    ~CopyPool() {
-        {
-            std::lock_guard<std::mutex> g(m_);
-            stop_ = true;
-            ++gen_;
-        }
-        cv_.notify_all();
-        for (auto& t : th_) t.join();
-    }
-    int size() const { return n_; }
-    // fn(i) for every i in [0, size()): i = 0 on the calling thread, the others on the workers; returns when
-    // all have.  One caller at a time.
-    void run(const std::function<void(int)>& fn) {
-        if (n_ == 1) {
-            fn(0);
-            return;
-        }
-        {
-            std::lock_guard<std::mutex> g(m_);
-            job_ = &fn;
-            pending_ = n_ - 1;
-            ++gen_;
-        }
-        cv_.notify_all();
-        fn(0);
-        std::unique_lock<std::mutex> l(m_);
-        done_.wait(l, [&] { return pending_ == 0; });
-    }
-    // dst[0, len) = src(0, len), split over the workers (the caller copies part 0).
-    void copy(char* dst, size_t len, const std::function<void(size_t, size_t, char*)>& src) {
-        if (n_ == 1 || len < (4u << 20)) {
-            src(0, len, dst);
-            return;
-        }
-        const size_t per = (len / n_ + 4095) / 4096 * 4096;
-        run([&](int p) {
-            const size_t lo = std::min(len, (size_t)p * per), hi = std::min(len, lo + per);
-            if (hi > lo) src(lo, hi - lo, dst + lo);
-        });
-    }
-
-private:
-    void loop(int id) {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::function<void(int)>* job;
-            {
-                std::unique_lock<std::mutex> l(m_);
-                cv_.wait(l, [&] { return gen_ != seen; });
-                seen = gen_;
-                if (stop_) return;
-                job = job_;
-            }
-            (*job)(id);
-            {
-                std::lock_guard<std::mutex> g(m_);
-                if (--pending_ == 0) done_.notify_one();
-            }
-        }
-    }
-    int n_;
-    std::vector<std::thread> th_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    uint64_t gen_ = 0;
-    int pending_ = 0;
-    bool stop_ = false;
-    const std::function<void(int)>* job_ = nullptr;
-};
-
 int default_copy_threads() {
     const unsigned hw = std::thread::hardware_concurrency();
     return (int)std::max(1u, std::min(8u, hw / 2));
 }
 
-// Runs fn(g) for g in [0, G): G > 1 on the context's persistent per-GPU workers (the host-side staging of
-// each GPU is independent; no thread is created per call), returning the first non-zero status.
 int for_each_gpu(CopyPool* workers, int G, const std::function<int(int)>& fn) {
     if (G == 1 || !workers) return fn(0);
     std::vector<int> rc((size_t)G, FA_OK);
@@ -237,211 +70,6 @@ int for_each_gpu(CopyPool* workers, int G, const std::function<int(int)>& fn) {
     return FA_OK;
 }
 
-// The scratch of a measure pass (the clip stage's norm pass, the Krum stage's distance pass) on one GPU, grown
-// on use (ensure_measure_scratch): `dev` holds room for `outs` fp64 results (a pass's sums or matrices, piece
-// after piece) followed by `parts` per-workgroup partials, `host` is the pinned array the results are read
-// back into.  One instance serves both stages and every part of a context, because every user waits on the
-// host for the stream it enqueued on before it returns, the error returns included (measure_pass,
-// measure_device): between two calls nothing on the device reads or writes it.
-struct MeasureScratch {
-    double* dev = nullptr;
-    double* host = nullptr;
-    size_t outs = 0, parts = 0;
-};
-
-struct GpuRes {
-    int dev = 0;
-    hipStream_t compute = nullptr, copy = nullptr, comm = nullptr;
-    char* stage[2] = {nullptr, nullptr};
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    int stage_i = 0;
-    hipEvent_t copy_ev = nullptr;  // orders a reduction after the H2D copies queued on `copy`
-    uint64_t copy_gen = 0;         // H2D batches queued on `copy` so far (a submit adds one)
-    uint64_t copy_ev_gen = 0;      // the batch copy_ev was last recorded after
-    std::map<hipStream_t, uint64_t> waited;  // per stream: the copy batch it last waited for
-    hipEvent_t step_ev = nullptr;  // orders the rs exchange of a piece after its reduction
-    void* scratch = nullptr;       // fp32 chain accumulator for a 16-bit output, D > kMaxClients
-    MeasureScratch measure;        // the clip and Krum stages' measure passes
-    // fa_output_crc32: the piece table (pinned staging + device copy) and the per-piece results, grown on use
-    char* crc_host = nullptr;
-    char* crc_dev = nullptr;
-    size_t crc_bytes = 0;
-    size_t scratch_bytes = 0;
-    // Device segment tables of batched launches (fa_reduce_parts beyond the kernel-argument table): a ring,
-    // so a changed table is uploaded into a slot whose last launch is long done; each slot remembers the
-    // stream and event of its last launch, which orders a reuse or an overwrite after it (allocated on
-    // first use).
-    struct SegTable {
-        fa::SegDesc* host = nullptr;  // pinned staging of the upload
-        fa::SegDesc* dev = nullptr;
-        hipEvent_t ev = nullptr;      // recorded after the slot's last launch (its upload precedes it)
-        hipStream_t stream = nullptr; // the stream of that launch
-        size_t bytes = 0;             // bytes of the table the slot holds
-    };
-    SegTable seg[kSegRing];
-    int seg_last = -1;                // the slot of the last batched launch
-    std::unique_ptr<CopyPool> pool;
-    ncclComm_t nccl = nullptr;
-};
-
-// One copy-out run: elements [src, src + cnt) of a GPU's output buffer are bucket elements [dst, dst + cnt).
-struct Run {
-    size_t src, dst, cnt;
-};
-
-struct Part {
-    int id = 0;  // its part_id (the noise stage's stream)
-    size_t n = 0;
-    fa_dtype in = FA_F32, out = FA_F32;
-    int D = 0;
-    fa_mode mode = FA_FEDAVG;
-    float divisor = FA_DEFAULT_DIVISOR;
-    int trim = FA_TRIM_MEDIAN;     // FA_TRIMMED: as given to fa_set_trim (resolved against D at each reduction)
-    bool rs = false;               // FA_SHARD_CLIENT_RS layout
-    size_t npad = 0;               // rs: slot length (n padded to a multiple of G * 64)
-    std::vector<size_t> off, cnt;  // per GPU: bucket elements held by its slots (range: its shard; rs: [0, n))
-    std::vector<int> c0, c1;       // per GPU: the client slots it holds, [c0, c1)
-    std::vector<char*> pool;       // per GPU: its client slots + the output (+ rs partial, eager acc)
-    std::vector<size_t> stride;    // per GPU: bytes between consecutive slots of one piece
-    // Pieces (range layout): a GPU whose slots would span more than 48 GiB (piece_len_for) holds its range as
-    // npiece[g] pieces of piece_len[g] elements (the last one shorter): piece j of every slot lies in the
-    // j-th region of the pool (slots of one piece stride[g] apart), so one launch reads clients that lie
-    // close together (the address span).  One piece = the plain layout.
-    std::vector<int> npiece;
-    std::vector<size_t> piece_len;
-    std::vector<void*> dout;       // per GPU: the output (range: cnt elements of `out`; rs: its fp32 shard)
-    std::vector<void*> dout16;     // rs with a 16-bit output: per GPU, its shard rounded to it (the copy-out's source)
-    std::vector<float*> partial;   // rs: per GPU, fp32 partial over its clients, npad elements
-    std::vector<float*> acc;       // FA_ACCUMULATE_ON_ARRIVAL: per GPU, fp32 chain of the reduced prefix
-    std::vector<hipEvent_t> done;  // per GPU: orders the copy-out after the reduction (see mark_done)
-    std::vector<hipStream_t> done_stream;  // per GPU: the stream the last reduction ran on
-    std::vector<float> w;
-    std::vector<char> submitted;
-    int n_submitted = 0;
-    int last_slot = -1;
-    int reduced = 0;    // accumulate on arrival: slots [0, reduced) are chained into acc (or dout)
-    bool ready = false; // this round's output is reduced already (eager prefix reached D, fa_reduce_parts)
-    std::vector<std::vector<Run>> runs;  // per GPU: where its output goes (set by the last reduction)
-    std::vector<void*> run_src;          // per GPU: the buffer the runs read
-    // Small receipts kept where they arrived (host_keep): per slot the receipt's pinned segments -- the host
-    // address (for a later DMA, host_flush) and the address a kernel reads it at -- empty = in the slot.
-    struct HostSeg {
-        const char* host;
-        const char* dev;
-        size_t bytes;
-    };
-    std::vector<std::vector<HostSeg>> host_src;
-    int n_host = 0;  // slots whose receipt is kept host-side this round
-    // Server-optimizer stage (fa.h "Server optimizer"; opt.rule == FA_OPT_NONE: none).  Per GPU the fp32 state
-    // over its cnt elements (ov only for the adaptive rules), each its own allocation, freed with the stage or
-    // the part.  oavg: for a 16-bit output, the fp32 buffer the round's aggregate is reduced into, there while
-    // the part has this stage or the noise stage (ensure_oavg, drop_oavg_if_unused).
-    fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};
-    std::vector<float*> ox, om, ov, oavg;
-    bool opt_master = false;  // x holds a model (set, or bootstrapped): the next reduction is a step
-    uint64_t opt_steps = 0;
-    // Clip stage (fa.h "Clip stage"; clip == 0: none).  Per GPU the fp32 reference over its cnt elements and,
-    // for a 16-bit input, the fp32 buffer the chain's first term fmaf(c0, g, +0) is written into; each its own
-    // allocation, freed with the stage or the part.
-    float clip = 0.0f;
-    std::vector<float*> cref, cinit;
-    bool clip_has_ref = false;  // g holds a model (set, or left by a round): the next reduction clips
-    bool clip_reported = false; // a reducing call ran with the stage: the arrays below describe it
-    std::vector<double> clip_q;
-    std::vector<float> clip_s;
-    std::vector<int> clip_in;
-    int clip_n = 0;
-    // Krum stage (fa.h "Krum stage"; krum_m == 0: none): f, the resolved m, and what the last reducing call
-    // found -- the D x D matrix, the scores, the selection flags.  Host state only.
-    int krum_f = 0, krum_m = 0;
-    bool krum_reported = false;
-    std::vector<double> krum_q, krum_s;
-    std::vector<int> krum_sel;
-    int krum_n = 0;
-    // Geomed stage (fa.h "Geomed stage"; geomed_iters == 0: none): T and nu, and the trace of the last reducing
-    // call -- its valid passes, Q^t and alpha^t row by row, the objective per pass, the final flags.  Host state only.
-    int geomed_iters = 0;
-    float geomed_nu = 0.0f;
-    bool geomed_reported = false;
-    int geomed_passes = 0;
-    std::vector<double> geomed_q, geomed_obj;
-    std::vector<float> geomed_w;
-    std::vector<int> geomed_in;
-    // Bulyan stage of an FA_TRIMMED part (fa.h "Bulyan stage"; bulyan_f < 0: none): f, and what the last reducing
-    // call found -- the D x D matrix, the picks in pick order with their scores, the flags.  Host state only.
-    int bulyan_f = -1;
-    bool bulyan_reported = false;
-    std::vector<double> bulyan_q, bulyan_s;
-    std::vector<int> bulyan_order, bulyan_sel;
-    int bulyan_n = 0;
-    // Noise stage (fa.h "Noise stage"; noise == 0: none): stddev, the seed and the round the next reducing call
-    // uses (2^32: that call is refused).  Host state only, besides oavg above.
-    float noise = 0.0f;
-    uint64_t noise_seed = 0;
-    uint64_t noise_round = 0;
-    // MX8 receipts (fa.h "MX8 receipts"; fa_set_mx8).  mx8_ref: the device output holds a reference -- a reducing
-    // call left it there while mx8 was on, or fa_mx8_set_reference wrote it.  mx8_buf: per GPU the compressed
-    // shadows of its held slots, mx8_stride[g] bytes apart (q: cnt bytes, then from mx8_eoff[g] on the scale bytes
-    // of the blocks its range touches), one allocation at the part's first fa_submit_mx8.
-    bool mx8 = false, mx8_ref = false;
-    std::vector<char*> mx8_buf;
-    std::vector<size_t> mx8_stride, mx8_eoff;
-    // MX8 replies (fa.h "MX8 replies"; fa_set_mx8_reply).  reply_sent: per GPU the model the owners last received,
-    // cnt elements of the out dtype (reply_has_sent: it holds one).  reply_codes: per GPU the codes of the last
-    // reducing call, q (cnt bytes) and from reply_eoff[g] on the scale bytes of the blocks its range touches
-    // (reply_has_codes: that call was no bootstrap).  Allocated at the first reducing call with the stage on.
-    bool reply = false, reply_has_sent = false, reply_has_codes = false;
-    std::vector<char*> reply_sent, reply_codes;
-    std::vector<size_t> reply_eoff;
-    bool reply_counted = true;  // reply_nan describes the codes above
-    uint64_t reply_nan = 0;
-};
-
-// A part whose reducing calls are rounds of their own (a server-optimizer, clip, Krum, geomed, Bulyan, noise or MX8
-// reply stage): never batched, eager or host-read, every client submitted before each.
-inline bool staged(const Part& p) {
-    return p.opt.rule != FA_OPT_NONE || p.clip > 0.0f || p.krum_m != 0 || p.geomed_iters != 0 || p.bulyan_f >= 0 ||
-           p.noise > 0.0f || p.reply;
-}
-// A part that gets its first stage: what this round chained or kept host-side so far goes back to the plain path.
-inline void restart_round_plain(Part& p) {
-    p.reduced = 0;
-    p.ready = false;
-}
-
-}  // namespace
-
-struct fa_ctx {
-    int G = 1;
-    int flags = 0;
-    float divisor = FA_DEFAULT_DIVISOR;
-    int trim = FA_TRIM_MEDIAN;  // default of FA_TRIMMED parts defined later
-    fa_server_opt opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};  // default stage of FedAvg / trimmed parts defined later
-    float clip = 0.0f;          // default clip bound of FedAvg parts defined later (0: none)
-    int krum_f = 0, krum_m = 0; // default Krum stage of FedAvg parts defined later (m == 0: none, -1: D - f)
-    int geomed_iters = 0;       // default geomed stage of FedAvg parts defined later (0: none)
-    float geomed_nu = 0.0f;
-    int bulyan_f = -1;          // default Bulyan stage of trimmed parts defined later (< 0: none)
-    float noise = 0.0f;         // default noise stage of FedAvg / trimmed parts defined later (0: none)
-    uint64_t noise_seed = 0;
-    bool mx8 = false;           // parts defined later (not FA_LITERAL) take MX8 receipts
-    bool mx8_reply = false;     // parts defined later (not FA_LITERAL) have the MX8 reply stage
-    CtxTuning tuning;
-    std::vector<GpuRes> gpu;
-    std::map<int, Part> parts;
-    std::unique_ptr<CopyPool> workers;  // G > 1: one persistent host thread per GPU (for_each_gpu)
-    unsigned long long host_reads = 0;  // reductions that read their receipts in place (fa_diag_host_reads)
-};
-
-namespace {
-
-// What a fa_*_device entry runs on (gpu checked against ctx->G before): the ctx's GPU `gpu`, hip_stream or that
-// GPU's compute stream, the ctx's tuning; without a ctx HIP device `gpu`, the defaults, g = 0.  No device call.
-struct DeviceCall {
-    int dev, g;
-    hipStream_t s;
-    fa::Tuning tu;
-};
 DeviceCall device_call(fa_ctx* ctx, int gpu, void* hip_stream) {
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (!ctx) return DeviceCall{gpu, 0, s, defaults().tu};
@@ -462,20 +90,13 @@ int ensure_scratch(fa_ctx* ctx, int g, size_t bytes) {
     return FA_OK;
 }
 
-// FA_TRIMMED: the trim a reduction over D clients uses (FA_TRIM_MEDIAN -> (D-1)/2), and its check.
-int resolved_trim(int trim, int D) { return trim == FA_TRIM_MEDIAN ? (D - 1) / 2 : trim; }
+// FA_TRIMMED: the check of a trim for D clients (resolved_trim).
 int check_trim(int trim, int D) {
     if (trim < -1 || (trim >= 0 && 2 * trim >= D))
         return fail(FA_ERR_ARG, "trim %d does not fit D = %d clients (FA_TRIM_MEDIAN, or 0 <= trim with 2 trim < D)", trim, D);
     return FA_OK;
 }
-float mode_arg(fa_mode mode, float divisor, int trim, int D) {
-    return mode == FA_TRIMMED ? (float)resolved_trim(trim, D) : divisor;
-}
 
-bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
-
-// A client pointer array (`what`: "client", "client slot"): there, every entry non-null and aligned to its element.
 int check_clients(const void* const* ptrs, int D, size_t elem, const char* what) {
     if (!ptrs) return fail(FA_ERR_ARG, "client array is null");
     for (int k = 0; k < D; ++k) {
@@ -484,7 +105,6 @@ int check_clients(const void* const* ptrs, int D, size_t elem, const char* what)
     }
     return FA_OK;
 }
-// Clients [k0, k0 + nc) of ptrs with their weights (w null: 0.0f, for the launches that read none).
 fa::ClientTable client_table(const void* const* ptrs, const float* w, int k0, int nc) {
     fa::ClientTable t;
     for (int k = 0; k < nc; ++k) {
@@ -494,59 +114,6 @@ fa::ClientTable client_table(const void* const* ptrs, const float* w, int k0, in
     return t;
 }
 
-// ------------------------------------------------------------------ server optimizer
-
-inline bool opt_adaptive(int rule) { return rule == FA_OPT_ADAGRAD || rule == FA_OPT_ADAM || rule == FA_OPT_YOGI; }
-inline bool finite_f(float f) { return f - f == 0.0f; }
-
-// The refusals of fa_set_server_opt / fa_server_opt_device, naming the field.
-int check_opt(const fa_server_opt& o) {
-    if (o.rule < FA_OPT_NONE || o.rule > FA_OPT_YOGI) return fail(FA_ERR_ARG, "server opt: rule %d outside 0..4", o.rule);
-    if (o.rule == FA_OPT_NONE) return FA_OK;
-    if (!finite_f(o.lr) || o.lr < 0.0f) return fail(FA_ERR_ARG, "server opt: lr %g must be finite and >= 0", (double)o.lr);
-    if (!(o.beta1 >= 0.0f && o.beta1 < 1.0f)) return fail(FA_ERR_ARG, "server opt: beta1 %g outside [0, 1)", (double)o.beta1);
-    if ((o.rule == FA_OPT_ADAM || o.rule == FA_OPT_YOGI) && !(o.beta2 >= 0.0f && o.beta2 < 1.0f))
-        return fail(FA_ERR_ARG, "server opt: beta2 %g outside [0, 1)", (double)o.beta2);
-    if (opt_adaptive(o.rule) && (!finite_f(o.tau) || !(o.tau > 0.0f)))
-        return fail(FA_ERR_ARG, "server opt: tau %g must be finite and > 0", (double)o.tau);
-    return FA_OK;
-}
-
-fa::OptHyper opt_hyper(const fa_server_opt& o) {
-    // c1, c2 in fp32 on the host (volatile: one rounded fp32 subtraction each, whatever the host's float mode)
-    volatile float c1 = 1.0f - o.beta1, c2 = 1.0f - o.beta2;
-    return fa::OptHyper{o.lr, o.beta1, o.beta2, o.tau, c1, c2};
-}
-
-// One launch of the stage on the current device: `rule` (or fa::kOptBoot) over n elements, split (fa_split.h)
-// with avg in the lead -- the vector form where the state and the output allow it too.
-int opt_on(const fa::Tuning& tu, int rule, const fa_server_opt& o, const float* avg, float* x, float* m, float* v,
-           size_t n, void* out, fa_dtype odt, hipStream_t s) {
-    if (n == 0) return FA_OK;
-    fa::Split sp = fa::split_at(avg, 4, n);
-    sp.require_input(x);
-    sp.require_input(m);
-    if (v) sp.require_input(v);
-    if (out) sp.require(out, dsize(odt));
-    FA_HIP(fa::launch_server_opt(rule, opt_hyper(o), avg, x, m, v, out, odt, sp, tu, s));
-    return FA_OK;
-}
-
-// One launch of the noise stage on the current device: out (dtype odt; avg itself for an in-place f32 pass) :=
-// avg + stddev z over n elements that are bucket elements idx0 .., split (fa_split.h) with avg in the lead.
-int noise_on(const fa::Tuning& tu, const float* avg, void* out, fa_dtype odt, float stddev, uint64_t seed, uint32_t stream,
-             uint32_t round, uint64_t idx0, size_t n, hipStream_t s) {
-    if (n == 0) return FA_OK;
-    fa::Split sp = fa::split_at(avg, 4, n);
-    sp.require(out, dsize(odt));
-    FA_HIP(fa::launch_noise(avg, out, odt, stddev, seed, stream, round, idx0, sp, tu, s));
-    return FA_OK;
-}
-constexpr uint64_t kNoiseRounds = (uint64_t)1 << 32;  // rounds 0 .. 2^32 - 1 exist
-
-// The device reduction for one GPU, shared by every entry: D clients (any D >= 1; more than kMaxClients
-// continue the chain from an fp32 accumulator in further passes) -> dst.  `divisor` is the mode's parameter:
-// FA_LITERAL's divisor, or FA_TRIMMED's resolved trim (mode_arg: a small integer, exact as a float).
 int reduce_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clients, const float* w, int D, size_t n,
               fa_dtype in, void* dst, fa_dtype out, fa_mode mode, float divisor, const float* init, hipStream_t s) {
     if (n == 0) return FA_OK;
@@ -626,335 +193,6 @@ int sync_on(fa_ctx* ctx, int g, const fa::Tuning& tu, void* const* slots, const 
     return FA_OK;
 }
 
-// ------------------------------------------------------------------ clip stage
-
-// Rule 2 of fa.h "Clip stage": volatile keeps each step one rounded fp64 / fp32 operation.
-float clip_scale(double sumsq, float max_norm, int* excluded) {
-    volatile double nrm = std::sqrt(sumsq);
-    const double N = nrm;
-    const bool out = N != N || N == HUGE_VAL;
-    if (excluded) *excluded = out ? 1 : 0;
-    if (out) return 0.0f;
-    if (N <= (double)max_norm) return 1.0f;
-    volatile double q = (double)max_norm / N;
-    return (float)q;
-}
-
-void free_measure_scratch(MeasureScratch& m) {
-    if (m.dev) (void)hipFree(m.dev);
-    if (m.host) (void)hipHostFree(m.host);
-    m = MeasureScratch{};
-}
-
-// Room on the current device for a measure pass of `outs` results and `parts` partials.  Never shrinks: a
-// reallocation keeps the larger of the old and the new count of each.  stage: "clip: norm-pass", "krum:
-// distance-pass".
-int ensure_measure_scratch(MeasureScratch& m, size_t outs, size_t parts, const char* stage) {
-    if (m.dev && m.outs >= outs && m.parts >= parts) return FA_OK;
-    const size_t ocap = std::max<size_t>(std::max(outs, m.outs), 256), pcap = std::max<size_t>(std::max(parts, m.parts), 1);
-    free_measure_scratch(m);
-    const size_t dev_bytes = (ocap + pcap) * sizeof(double);
-    if (hipMalloc((void**)&m.dev, dev_bytes) != hipSuccess ||
-        hipHostMalloc((void**)&m.host, ocap * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        if (m.dev) (void)hipFree(m.dev);
-        m = MeasureScratch{};
-        return fail(FA_ERR_NOMEM, "%s scratch of %zu B failed", stage, dev_bytes);
-    }
-    m.outs = ocap;
-    m.parts = pcap;
-    return FA_OK;
-}
-constexpr size_t kClipParts = (size_t)fa::kMaxClients * (size_t)fa::kClipMaxPartials;  // the norm pass's partials
-inline size_t krum_parts(int D) { return (size_t)fa::krum_pairs(D) * (size_t)fa::kKrumMaxPartials; }
-
-// Enqueues the norm pass on the current device: d_sums[k] = Q_k of clients[k] (n elements of `in`) against ref,
-// k < D, in passes of kMaxClients clients; d_part: kMaxClients * kClipMaxPartials doubles of scratch.  The
-// vector form where every client and ref allow it (fa_split.h).
-int clip_sumsq_on(const fa::Tuning& tu, const void* const* clients, int D, size_t n, fa_dtype in, const float* ref,
-                  double* d_part, double* d_sums, hipStream_t s) {
-    fa::Split sp = fa::split_at(clients[0], dsize(in), n);
-    for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
-    sp.require(ref, 4);
-    for (int k0 = 0; k0 < D; k0 += fa::kMaxClients) {
-        const int nc = std::min(fa::kMaxClients, D - k0);
-        const fa::ClientTable t = client_table(clients, nullptr, k0, nc);
-        FA_HIP(fa::launch_clip_sumsq(t, nc, in, ref, sp, d_part, d_sums + k0, tu, s));
-    }
-    return FA_OK;
-}
-
-// ------------------------------------------------------------------ Krum stage
-
-// The refusals of f and m for D clients (fa.h "Krum stage"), naming the cause; *m_out = m with -1 resolved.
-int check_krum(int D, int f, int m, int* m_out) {
-    if (D > FA_KRUM_MAX_CLIENTS) return fail(FA_ERR_ARG, "krum: D = %d clients (at most %d)", D, FA_KRUM_MAX_CLIENTS);
-    if (f < 0 || 2 * f + 2 >= D)
-        return fail(FA_ERR_ARG, "krum: f = %d does not fit D = %d clients (0 <= f and 2 f + 2 < D)", f, D);
-    const int mm = m == -1 ? D - f : m;
-    if (mm < 1 || mm > D - f)
-        return fail(FA_ERR_ARG, "krum: m = %d does not fit D = %d, f = %d (1 <= m <= D - f, or -1 for D - f)", m, D, f);
-    if (m_out) *m_out = mm;
-    return FA_OK;
-}
-
-// Rules 2-3 of fa.h "Krum stage" (D, f, m checked): volatile keeps each step one rounded fp64 add.
-void krum_select(const double* dist, int D, int f, int m, double* scores, int* selected, int* n_selected) {
-    const double inf = HUGE_VAL;
-    std::vector<double> row((size_t)D - 1), sc((size_t)D);
-    for (int k = 0; k < D; ++k) {
-        size_t c = 0;
-        for (int j = 0; j < D; ++j) {
-            if (j == k) continue;
-            const double q = dist[(size_t)k * D + j];
-            row[c++] = q != q ? inf : q;
-        }
-        std::sort(row.begin(), row.end());
-        volatile double acc = 0.0;
-        for (int i = 0; i < D - f - 2; ++i) acc = acc + row[(size_t)i];
-        sc[(size_t)k] = acc;
-    }
-    std::vector<int> order((size_t)D);
-    for (int k = 0; k < D; ++k) order[(size_t)k] = k;
-    // by (S_k, k) ascending; a NaN score (only from a matrix holding -inf) sorts as +inf
-    auto key = [&](int k) { return sc[(size_t)k] != sc[(size_t)k] ? inf : sc[(size_t)k]; };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key(a) < key(b); });
-    int ns = 0;
-    for (int k = 0; k < D; ++k) {
-        if (scores) scores[k] = sc[(size_t)k];
-        if (selected) selected[k] = 0;
-    }
-    for (int i = 0; i < m; ++i) {
-        const int k = order[(size_t)i];
-        if (!(sc[(size_t)k] < inf)) break;  // +inf is never selected, nor anything after it
-        if (selected) selected[k] = 1;
-        ++ns;
-    }
-    if (n_selected) *n_selected = ns;
-}
-
-// Rule 4: the weights of a round whose selection is `selected` (w_out[k] is set for every k; only the selected
-// ones enter the chain).
-void krum_weights(const float* w, const int* selected, int D, float* w_out) {
-    volatile double W = 0.0, Ws = 0.0;
-    int ns = 0;
-    for (int k = 0; k < D; ++k) {
-        W = W + (double)w[k];
-        if (selected[k]) {
-            Ws = Ws + (double)w[k];
-            ++ns;
-        }
-    }
-    volatile double ratio = 0.0;
-    bool plain = ns == D || !(Ws > 0.0);
-    if (!plain) {
-        ratio = W / Ws;
-        const double r = ratio;
-        plain = r != r || r == HUGE_VAL || r == -HUGE_VAL;
-    }
-    for (int k = 0; k < D; ++k) {
-        if (plain) {
-            w_out[k] = w[k];
-        } else {
-            volatile double prod = (double)w[k] * ratio;
-            w_out[k] = (float)prod;
-        }
-    }
-}
-
-// Enqueues the distance pass on the current device: d_dist (D * D doubles) = the matrix of clients[0..D) (n > 0
-// elements of `in`); d_part: the partials scratch.  The vector form where every client allows it (fa_split.h).
-int pairdist_on(const fa::Tuning& tu, const void* const* clients, int D, size_t n, fa_dtype in, double* d_part,
-                double* d_dist, hipStream_t s) {
-    fa::Split sp = fa::split_at(clients[0], dsize(in), n);
-    for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
-    const fa::ClientTable t = client_table(clients, nullptr, 0, D);
-    FA_HIP(fa::launch_pairdist(t, D, in, sp, d_part, d_dist, tu, s));
-    return FA_OK;
-}
-
-// ------------------------------------------------------------------ geomed stage
-
-// The refusals of T and nu, and of D clients when D > 0 (fa.h "Geomed stage"), naming the cause.
-int check_geomed(int D, int iters, float nu) {
-    if (iters < 0 || iters > FA_GEOMED_MAX_ITERS)
-        return fail(FA_ERR_ARG, "geomed: iters = %d outside 0..%d (0 removes the stage)", iters, FA_GEOMED_MAX_ITERS);
-    if (iters != 0 && (!finite_f(nu) || !(nu > 0.0f))) return fail(FA_ERR_ARG, "geomed: nu %g must be finite and > 0", (double)nu);
-    if (iters != 0 && D > FA_GEOMED_MAX_CLIENTS)
-        return fail(FA_ERR_ARG, "geomed: D = %d clients (at most %d)", D, FA_GEOMED_MAX_CLIENTS);
-    return FA_OK;
-}
-
-// Rules 3-4 of fa.h "Geomed stage": volatile keeps each step one rounded fp64 operation.  W is the mass of the owners
-// that entered the round: every k with w_k > 0, whatever `included` says by now.  *objective (nullable) = sum_k
-// (double)w_k N_k over the clients still included after rule 3.
-void geomed_weights(const float* w, const double* sumsq, int* included, int D, float nu, float* w_out, double* objective) {
-    volatile double W = 0.0, B = 0.0, obj = 0.0;
-    std::vector<double> beta((size_t)D, 0.0);
-    for (int k = 0; k < D; ++k) {
-        if (!(w[k] > 0.0f)) {
-            included[k] = 0;
-            continue;
-        }
-        W = W + (double)w[k];
-        if (!included[k]) continue;
-        volatile double nrm = std::sqrt(sumsq[k]);
-        const double N = nrm;
-        if (N != N || N == HUGE_VAL) {
-            included[k] = 0;
-            continue;
-        }
-        volatile double term = (double)w[k] * N;
-        obj = obj + term;
-        const double floor_ = (double)nu;
-        volatile double b = (double)w[k] / (floor_ > N ? floor_ : N);
-        beta[(size_t)k] = b;
-        B = B + b;
-    }
-    volatile double ratio = 0.0;
-    bool plain = !(B > 0.0);
-    if (!plain) {
-        ratio = W / B;
-        const double r = ratio;
-        plain = r != r || r == HUGE_VAL || r == -HUGE_VAL;
-    }
-    for (int k = 0; k < D; ++k) {
-        if (!included[k]) {
-            w_out[k] = 0.0f;
-        } else if (plain) {
-            w_out[k] = w[k];
-        } else {
-            volatile double prod = beta[(size_t)k] * ratio;
-            w_out[k] = (float)prod;
-        }
-    }
-    if (objective) *objective = obj;
-}
-
-constexpr size_t kGeomedParts = 2 * kClipParts;  // the fused pass's partials: Q and B of every client
-
-// Enqueues the fused pass on the current device: d_out[k] = Q_k and d_out[nc + k] = B_k of clients[0..nc) (n > 0
-// elements of `in`) under the weights w, d_v (nullable, n fp32) = the chain; d_part: kGeomedParts doubles of scratch.
-// The vector form where every client (and d_v) allows it (fa_split.h).
-int geomed_pass_on(const fa::Tuning& tu, const void* const* clients, const float* w, int nc, size_t n, fa_dtype in,
-                   float* d_v, double* d_part, double* d_out, hipStream_t s) {
-    fa::Split sp = fa::split_at(clients[0], dsize(in), n);
-    for (int k = 0; k < nc; ++k) sp.require_input(clients[k]);
-    if (d_v) sp.require(d_v, 4);
-    const fa::ClientTable t = client_table(clients, w, 0, nc);
-    FA_HIP(fa::launch_geomed_pass(t, nc, in, d_v, sp, d_part, d_out, tu, s));
-    return FA_OK;
-}
-
-// ------------------------------------------------------------------ Bulyan stage
-
-// The refusals of f for D clients (fa.h "Bulyan stage"), naming the cause.
-int check_bulyan(int D, int f) {
-    if (D > FA_TRIMMED_MAX_CLIENTS)
-        return fail(FA_ERR_ARG, "bulyan: D = %d clients (at most %d)", D, FA_TRIMMED_MAX_CLIENTS);
-    if (f < 0 || 4 * f + 3 > D)
-        return fail(FA_ERR_ARG, "bulyan: f = %d does not fit D = %d clients (0 <= f and 4 f + 3 <= D)", f, D);
-    return FA_OK;
-}
-
-// Rule 2 of fa.h "Bulyan stage" (D, f checked): order, pick_scores and selected hold D entries each, any may be
-// null.  Every row is sorted once with its column indices; a round's score is the row's first entries that are
-// still in R, which is the sorted row of rule 2 (equal values add to the same sum in either order).  volatile
-// keeps each step one rounded fp64 add.
-void bulyan_select(const double* dist, int D, int f, int* order, double* pick_scores, int* selected, int* n_selected) {
-    const double inf = HUGE_VAL;
-    const size_t n = (size_t)D;
-    std::vector<std::vector<std::pair<double, int>>> rows(n);
-    for (int k = 0; k < D; ++k) {
-        auto& row = rows[(size_t)k];
-        row.reserve(n - 1);
-        for (int j = 0; j < D; ++j) {
-            if (j == k) continue;
-            const double q = dist[(size_t)k * n + (size_t)j];
-            row.emplace_back(q != q ? inf : q, j);
-        }
-        std::stable_sort(row.begin(), row.end(),
-                         [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
-    }
-    std::vector<char> in_r(n, 1);
-    for (int k = 0; k < D; ++k) {
-        if (order) order[k] = -1;
-        if (pick_scores) pick_scores[k] = inf;
-        if (selected) selected[k] = 0;
-    }
-    const int theta = D - 2 * f;
-    int picked = 0;
-    for (int left = D; picked < theta; --left) {
-        const int take = std::min(std::max(1, left - f - 2), left - 1);
-        int best = -1;
-        double best_s = inf;
-        for (int k = 0; k < D; ++k) {
-            if (!in_r[(size_t)k]) continue;
-            volatile double acc = 0.0;
-            int got = 0;
-            for (const auto& e : rows[(size_t)k]) {
-                if (got == take) break;
-                if (!in_r[(size_t)e.second]) continue;
-                acc = acc + e.first;
-                ++got;
-            }
-            const double s = acc;
-            const double key = s != s ? inf : s;  // a NaN score (only from a matrix holding -inf) counts as +inf
-            if (best < 0 || key < best_s) {
-                best = k;
-                best_s = key;
-            }
-        }
-        if (!(best_s < inf)) break;  // +inf is never picked, nor anything after it
-        if (order) order[picked] = best;
-        if (pick_scores) pick_scores[picked] = best_s;
-        if (selected) selected[best] = 1;
-        in_r[(size_t)best] = 0;
-        ++picked;
-    }
-    if (n_selected) *n_selected = picked;
-}
-
-// Enqueues the centred mean (rule 4) on the current device: nc clients (n > 0 elements of `in`) -> dst.
-int centered_on(const fa::Tuning& tu, const void* const* clients, int nc, size_t n, fa_dtype in, void* dst, fa_dtype out,
-                int keep, hipStream_t s) {
-    const size_t si = dsize(in), so = dsize(out);
-    if (int rc = check_clients(clients, nc, si, "client")) return rc;
-    if (!dst) return fail(FA_ERR_ARG, "output pointer is null");
-    if (!aligned(dst, so)) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", so);
-    fa::Split sp = fa::split_at(clients[0], si, n);
-    for (int k = 0; k < nc; ++k) sp.require_input(clients[k]);
-    sp.require(dst, so);
-    const fa::ClientTable t = client_table(clients, nullptr, 0, nc);
-    FA_HIP(fa::launch_centered(t, nc, in, out, keep, dst, sp, tu, s));
-    return FA_OK;
-}
-
-// The body of the two raw device entries (arguments checked): one measure pass, enqueue(call, d_part, d_out) ->
-// FA_*, on the context's scratch, or without a context on scratch of its own, freed before the return; its
-// `outs` results into h_out after the wait for the stream, which follows whatever was enqueued (MeasureScratch).
-template <typename Enqueue>
-int measure_device(fa_ctx* ctx, int gpu, void* hip_stream, size_t outs, size_t parts, const char* stage, double* h_out,
-                   Enqueue enqueue) {
-    const DeviceCall c = device_call(ctx, gpu, hip_stream);
-    DeviceGuard dg(c.dev);
-    MeasureScratch own;
-    MeasureScratch& m = ctx ? ctx->gpu[(size_t)gpu].measure : own;
-    int rc = ensure_measure_scratch(m, outs, parts, stage);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        rc = enqueue(c, m.dev + m.outs, m.dev);
-        if (!rc) e = hipMemcpyAsync(m.host, m.dev, outs * sizeof(double), hipMemcpyDeviceToHost, c.s);
-        const hipError_t es = hipStreamSynchronize(c.s);
-        if (e == hipSuccess) e = es;
-        if (!rc && e == hipSuccess) std::copy(m.host, m.host + outs, h_out);
-    }
-    if (!ctx) free_measure_scratch(own);
-    if (rc) return rc;
-    FA_HIP(e);
-    return FA_OK;
-}
-
 // ------------------------------------------------------------------ layouts
 
 // [c0, c1) of the D client slots held by GPU g of G under the rs layout (contiguous, balanced; chain
@@ -1021,26 +259,6 @@ size_t piece_len_for(size_t held, size_t cnt, size_t si, const CtxTuning& t) {
     return piece_len_for(held, cnt, si, t.piece_span, t.piece_split);
 }
 
-inline bool holds(const Part& p, int g, int k) { return k >= p.c0[(size_t)g] && k < p.c1[(size_t)g]; }
-// Piece j of GPU g: GPU-local elements [piece_lo, piece_lo + piece_cnt), the slot of client k at piece_ptr.
-inline size_t piece_lo(const Part& p, int g, int j) { return (size_t)j * p.piece_len[(size_t)g]; }
-inline size_t piece_cnt(const Part& p, int g, int j) {
-    const size_t lo = piece_lo(p, g, j), n = p.cnt[(size_t)g];
-    return lo >= n ? 0 : std::min(p.piece_len[(size_t)g], n - lo);
-}
-inline char* piece_ptr(const Part& p, int g, int k, int j) {
-    const size_t held = (size_t)(p.c1[(size_t)g] - p.c0[(size_t)g]);
-    return p.pool[(size_t)g] + ((size_t)j * held + (size_t)(k - p.c0[(size_t)g])) * p.stride[(size_t)g];
-}
-inline char* slot_ptr(const Part& p, int g, int k) { return piece_ptr(p, g, k, 0); }  // one-piece parts
-// The pointer list of piece j of GPU g over clients [k0, k1), in a vector the caller keeps across pieces.
-template <typename P>
-P* const* piece_ptrs(const Part& p, int g, int j, int k0, int k1, std::vector<P*>& out) {
-    out.resize((size_t)(k1 - k0));
-    for (int k = k0; k < k1; ++k) out[(size_t)(k - k0)] = piece_ptr(p, g, k, j);
-    return out.data();
-}
-
 int check_part(fa_ctx* ctx, int part_id, Part** out) {
     if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
     auto it = ctx->parts.find(part_id);
@@ -1049,98 +267,8 @@ int check_part(fa_ctx* ctx, int part_id, Part** out) {
     return FA_OK;
 }
 
-// The fp32 aggregate buffer of a 16-bit part: wanted while it has a server-optimizer or a noise stage.
-inline bool wants_oavg(const Part& p) { return p.out != FA_F32 && (p.opt.rule != FA_OPT_NONE || p.noise > 0.0f); }
-void drop_oavg_if_unused(fa_ctx* ctx, Part& p) {
-    if (wants_oavg(p)) return;
-    for (size_t g = 0; g < p.oavg.size(); ++g) {
-        DeviceGuard dg(ctx->gpu[g].dev);
-        if (p.oavg[g]) (void)hipFree(p.oavg[g]);  // waits for the device's pending work
-    }
-    p.oavg.clear();
-}
-// Allocates what is missing of it (`stage` names the caller in the message); on failure what was there stays.
-int ensure_oavg(fa_ctx* ctx, Part& p, const char* stage) {
-    if (!wants_oavg(p)) return FA_OK;
-    const size_t G = (size_t)ctx->G;
-    if (p.oavg.size() != G) p.oavg.assign(G, nullptr);
-    for (size_t g = 0; g < G; ++g) {
-        if (p.oavg[g]) continue;
-        DeviceGuard dg(ctx->gpu[g].dev);
-        const size_t bytes = std::max<size_t>(16, p.cnt[g] * 4);
-        if (hipMalloc((void**)&p.oavg[g], bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            p.oavg[g] = nullptr;
-            return fail(FA_ERR_NOMEM, "%s: aggregate buffer alloc of %zu B failed on GPU %zu", stage, bytes, g);
-        }
-    }
-    return FA_OK;
-}
-
-// Frees the stage's arrays on every GPU (hipFree waits for the device's pending work) and forgets the master.
-void free_opt(fa_ctx* ctx, Part& p) {
-    for (size_t g = 0; g < p.ox.size(); ++g) {
-        DeviceGuard dg(ctx->gpu[g].dev);
-        for (auto* arr : {&p.ox, &p.om, &p.ov})
-            if (g < arr->size() && (*arr)[g]) (void)hipFree((*arr)[g]);
-    }
-    p.ox.clear();
-    p.om.clear();
-    p.ov.clear();
-    p.opt = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};
-    p.opt_master = false;
-    p.opt_steps = 0;
-    drop_oavg_if_unused(ctx, p);
-}
-
-// The same for the clip stage: its arrays go, the reference is forgotten.
-void free_clip(fa_ctx* ctx, Part& p) {
-    for (size_t g = 0; g < p.cref.size(); ++g) {
-        DeviceGuard dg(ctx->gpu[g].dev);
-        for (auto* arr : {&p.cref, &p.cinit})
-            if (g < arr->size() && (*arr)[g]) (void)hipFree((*arr)[g]);
-    }
-    p.cref.clear();
-    p.cinit.clear();
-    p.clip = 0.0f;
-    p.clip_has_ref = false;
-    p.clip_reported = false;
-}
-
-// The compressed shadows go (hipFree waits for the device's pending work); the part takes full receipts only.
-void free_mx8(fa_ctx* ctx, Part& p) {
-    for (size_t g = 0; g < p.mx8_buf.size(); ++g) {
-        DeviceGuard dg(ctx->gpu[g].dev);
-        if (p.mx8_buf[g]) (void)hipFree(p.mx8_buf[g]);
-    }
-    p.mx8_buf.clear();
-    p.mx8_stride.clear();
-    p.mx8_eoff.clear();
-    p.mx8 = false;
-    p.mx8_ref = false;
-}
-
-// `sent` and the code buffers go (hipFree waits for the device's pending work); the part has no reply stage.
-void free_reply(fa_ctx* ctx, Part& p) {
-    for (size_t g = 0; g < p.reply_sent.size(); ++g) {
-        DeviceGuard dg(ctx->gpu[g].dev);
-        if (p.reply_sent[g]) (void)hipFree(p.reply_sent[g]);
-        if (g < p.reply_codes.size() && p.reply_codes[g]) (void)hipFree(p.reply_codes[g]);
-    }
-    p.reply_sent.clear();
-    p.reply_codes.clear();
-    p.reply_eoff.clear();
-    p.reply = p.reply_has_sent = p.reply_has_codes = false;
-    p.reply_counted = true;
-    p.reply_nan = 0;
-}
-
 void free_part(fa_ctx* ctx, Part& p) {
-    p.noise = 0.0f;
-    free_mx8(ctx, p);
-    free_reply(ctx, p);
-    free_opt(ctx, p);
-    free_clip(ctx, p);
+    free_stages(ctx, p);
     for (size_t g = 0; g < p.pool.size(); ++g) {
         DeviceGuard dg(ctx->gpu[g].dev);
         if (p.pool[g]) (void)hipFree(p.pool[g]);
@@ -1172,7 +300,7 @@ int wait_copies(fa_ctx* ctx, int g, hipStream_t s) {
 // Copy-out runs of a range part: GPU g's output holds its shard -- every reduction of a range part into its device
 // output ends here, so this is also where an MX8 part's output becomes the next round's reference.
 void set_range_runs(Part& p, int G) {
-    p.mx8_ref = p.mx8;
+    p.mx8.ref = p.mx8.on();
     for (int g = 0; g < G; ++g) {
         p.runs[(size_t)g] = {Run{0, p.off[(size_t)g], p.cnt[(size_t)g]}};
         p.run_src[(size_t)g] = p.dout[(size_t)g];
@@ -1334,9 +462,9 @@ const char* device_visible(const void* ptr) {
 
 bool host_read_part(const fa_ctx* ctx, const Part& p) {
     // trimmed parts are never kept host-side (fa.h): D PCIe reads per element feed a sort, not a chain
-    // nor parts with a server-optimizer or clip stage: their round reads or ends in device state
+    // nor parts with a stage (staged): their round reads or ends in device state
     // nor MX8 parts: their output must land on the device, where it is the next round's reference
-    return host_read_enabled() && p.mode != FA_TRIMMED && !staged(p) && !p.mx8 && ctx->G == 1 && !p.rs &&
+    return host_read_enabled() && p.mode != FA_TRIMMED && !stages_on(p) && ctx->G == 1 && !p.rs &&
            !(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) &&
            p.npiece[0] == 1 && p.n > 0 && (size_t)p.D * p.n * dsize(p.in) <= kHostReadMax;
 }
@@ -1486,335 +614,6 @@ int host_reduce(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, const Gathe
     return FA_OK;
 }
 
-// What a measure-then-select stage makes of a round (fa.h "Clip stage", rules 1-3; "Krum stage", rules 1-4): the
-// clients that enter the chain in ascending order, their weights w'_k, and the weight c0 of the clip reference
-// as the chain's first term (0: none, as always for Krum).
-struct SubsetPlan {
-    std::vector<int> inc;
-    std::vector<float> w;
-    float c0 = 0.0f;
-};
-
-// A stage's measure pass over part p (range layout).  On every GPU with elements, after its H2D copies:
-// launch(g, j, clients, cnt, d_part, d_out, stream) -> FA_* enqueues the pass of piece j, in order, its `outs`
-// fp64 results into d_out (d_part: `parts` partials of scratch), then one D2H brings all the pieces' results.
-// Then, per GPU in order, one wait and each piece's results into acc[0, outs), zeroed by the caller: one rounded
-// fp64 add per element, in GPU order, then piece order (fa.h).  An error ends the enqueuing, not the waits:
-// every GPU enqueued on is waited for (MeasureScratch).
-template <typename Launch>
-int measure_pass(fa_ctx* ctx, Part& p, hipStream_t s, size_t outs, size_t parts, const char* stage, double* acc,
-                 Launch launch) {
-    std::vector<const void*> ptrs;
-    const auto enqueue = [&](int g) -> int {
-        MeasureScratch& m = ctx->gpu[(size_t)g].measure;
-        hipStream_t st = s ? s : ctx->gpu[(size_t)g].compute;
-        const size_t np = (size_t)p.npiece[(size_t)g];
-        int rc = wait_copies(ctx, g, st);
-        if (rc || (rc = ensure_measure_scratch(m, np * outs, parts, stage))) return rc;
-        for (size_t j = 0; j < np; ++j)
-            if ((rc = launch(g, (int)j, piece_ptrs(p, g, (int)j, 0, p.D, ptrs), piece_cnt(p, g, (int)j), m.dev + m.outs,
-                             m.dev + j * outs, st)))
-                return rc;
-        FA_HIP(hipMemcpyAsync(m.host, m.dev, np * outs * sizeof(double), hipMemcpyDeviceToHost, st));
-        return FA_OK;
-    };
-    int rc = FA_OK, tried = 0;  // GPUs [0, tried) may have work of this pass in flight
-    for (; !rc && tried < ctx->G; ++tried) {
-        if (p.cnt[(size_t)tried] == 0) continue;
-        DeviceGuard dg(ctx->gpu[(size_t)tried].dev);
-        rc = enqueue(tried);
-    }
-    for (int g = 0; g < tried; ++g) {
-        if (p.cnt[(size_t)g] == 0) continue;
-        GpuRes& r = ctx->gpu[(size_t)g];
-        DeviceGuard dg(r.dev);
-        const hipError_t e = hipStreamSynchronize(s ? s : r.compute);
-        if (rc) continue;
-        if (e != hipSuccess) {
-            rc = fail(FA_ERR_HIP, "hipStreamSynchronize(s ? s : r.compute): %s (%s:%d)", hipGetErrorString(e), __FILE__,
-                      __LINE__);
-            continue;
-        }
-        for (size_t j = 0; j < (size_t)p.npiece[(size_t)g]; ++j)
-            for (size_t i = 0; i < outs; ++i) {
-                volatile double q = acc[i] + r.measure.host[j * outs + i];
-                acc[i] = q;
-            }
-    }
-    return rc;
-}
-
-// Rules 1-3 for part p (range layout, a reference present): the norm pass (measure_pass), then the host
-// arithmetic.  Leaves the round's report in the part.
-int clip_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* plan) {
-    const size_t D = (size_t)p.D;
-    std::fill(p.clip_q.begin(), p.clip_q.end(), 0.0);
-    if (int rc = measure_pass(ctx, p, s, D, kClipParts, "clip: norm-pass", p.clip_q.data(),
-                              [&](int g, int j, const void* const* clients, size_t cnt, double* d_part, double* d_out,
-                                  hipStream_t st) {
-                                  return clip_sumsq_on(ctx->tuning.tu, clients, p.D, cnt, p.in,
-                                                       p.cref[(size_t)g] + piece_lo(p, g, j), d_part, d_out, st);
-                              }))
-        return rc;
-    double W = 0.0, Wp = 0.0;
-    p.clip_n = 0;
-    for (size_t k = 0; k < D; ++k) {
-        int ex = 0;
-        const float sc = clip_scale(p.clip_q[k], p.clip, &ex);
-        p.clip_s[k] = sc;
-        p.clip_in[k] = ex ? 0 : 1;
-        W += (double)w[k];
-        if (ex) continue;
-        if (sc < 1.0f) ++p.clip_n;
-        volatile float prod = w[k] * sc;  // one rounded fp32 product
-        const float wk = prod;
-        Wp += (double)wk;
-        plan->inc.push_back((int)k);
-        plan->w.push_back(wk);
-    }
-    volatile double rest = W - Wp;
-    plan->c0 = (float)rest;
-    return FA_OK;
-}
-
-// The chain of a stage's plan for piece j of GPU g (the current device), into dst (dtype odt): over the plan's
-// clients (clip rule 4, Krum rule 5), with c0 != 0 the clip reference as its first term.  An f32 part passes g
-// as the chain's first client with weight c0; a 16-bit part first writes fmaf(c0, g, +0) into its fp32 buffer
-// (a one-client f32 chain) and continues from it.  Only then are p.cref and p.cinit touched: a Krum part has
-// neither.
-int subset_chain(fa_ctx* ctx, Part& p, int g, int j, const SubsetPlan& plan, void* dst, fa_dtype odt, hipStream_t st) {
-    const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
-    if (cnt == 0) return FA_OK;
-    const fa::Tuning& tu = ctx->tuning.tu;
-    const bool lead = plan.c0 != 0.0f;
-    const void* ref = lead ? p.cref[(size_t)g] + lo : nullptr;
-    if (plan.inc.empty()) {  // the first term alone, +0 without one
-        if (lead) return reduce_on(ctx, g, tu, &ref, &plan.c0, 1, cnt, FA_F32, dst, odt, FA_FEDAVG, 0.0f, nullptr, st);
-        FA_HIP(hipMemsetAsync(dst, 0, cnt * dsize(odt), st));
-        return FA_OK;
-    }
-    std::vector<const void*> ptrs;
-    std::vector<float> ws;
-    const float* init = nullptr;
-    if (lead && p.in == FA_F32) {
-        ptrs.push_back(ref);
-        ws.push_back(plan.c0);
-    } else if (lead) {
-        float* first = p.cinit[(size_t)g] + lo;
-        if (int rc = reduce_on(ctx, g, tu, &ref, &plan.c0, 1, cnt, FA_F32, first, FA_F32, FA_FEDAVG, 0.0f, nullptr, st))
-            return rc;
-        init = first;
-    }
-    for (size_t i = 0; i < plan.inc.size(); ++i) {
-        ptrs.push_back(piece_ptr(p, g, plan.inc[i], j));
-        ws.push_back(plan.w[i]);
-    }
-    return reduce_on(ctx, g, tu, ptrs.data(), ws.data(), (int)ptrs.size(), cnt, p.in, dst, odt, FA_FEDAVG, 0.0f, init, st);
-}
-
-// Rule 6 for the same piece: the reference := the output just written, widened to fp32.
-// The buffers of a reply part, allocated once: per GPU `sent` (cnt elements of the out dtype) and the codes (q: cnt
-// bytes, then from reply_eoff[g] on the scale bytes of the blocks the range touches).
-int ensure_reply_buf(fa_ctx* ctx, Part& p) {
-    const size_t G = (size_t)ctx->G;
-    if (p.reply_sent.size() == G) return FA_OK;
-    p.reply_sent.assign(G, nullptr);
-    p.reply_codes.assign(G, nullptr);
-    p.reply_eoff.assign(G, 0);
-    for (size_t g = 0; g < G; ++g) {
-        DeviceGuard dg(ctx->gpu[g].dev);
-        p.reply_eoff[g] = (p.cnt[g] + 15) / 16 * 16;
-        const size_t scales = p.cnt[g] ? ((p.off[g] + p.cnt[g] - 1) >> 5) - (p.off[g] >> 5) + 1 : 0;
-        const size_t sbytes = std::max<size_t>(256, p.cnt[g] * dsize(p.out)), cbytes = std::max<size_t>(256, p.reply_eoff[g] + scales);
-        if (hipMalloc((void**)&p.reply_sent[g], sbytes) != hipSuccess ||
-            hipMalloc((void**)&p.reply_codes[g], cbytes) != hipSuccess) {
-            (void)hipGetLastError();
-            const bool on = p.reply;
-            free_reply(ctx, p);  // what this attempt did allocate; the part keeps its stage
-            p.reply = on;
-            return fail(FA_ERR_NOMEM, "mx8 reply: alloc of %zu + %zu B failed on GPU %zu", sbytes, cbytes, g);
-        }
-    }
-    return FA_OK;
-}
-
-// The reply stage on GPU g (fa.h "MX8 replies", rules 2-5), after everything else of the reducing call: the output
-// holds y.  Without `sent` the round is the bootstrap, sent := y; else one fused pass writes the codes, g' into
-// the output and g' into `sent`.  Range shards are cut at multiples of 64 elements (kShardUnit), so no block of 32
-// lies in two GPUs' ranges and rule 6's exchange of partial scales never arises here; a layout that cut
-// elsewhere would have to run fa_mx8_encode_device's two scale modes around a host wait, and is refused.
-int reply_stage(fa_ctx* ctx, Part& p, int g, hipStream_t st) {
-    if (int rc = ensure_reply_buf(ctx, p)) return rc;
-    const size_t cnt = p.cnt[(size_t)g], off = p.off[(size_t)g];
-    if (cnt == 0) return FA_OK;
-    if (off % FA_MX8_BLOCK != 0)
-        return fail(FA_ERR_STATE, "mx8 reply: part %d: the range of GPU %d starts at element %zu, inside a block", p.id, g, off);
-    char* sent = p.reply_sent[(size_t)g];
-    if (!p.reply_has_sent) {
-        FA_HIP(hipMemcpyAsync(sent, p.dout[(size_t)g], cnt * dsize(p.out), hipMemcpyDeviceToDevice, st));
-        return FA_OK;
-    }
-    char* q = p.reply_codes[(size_t)g];
-    FA_HIP(fa::launch_mx8_encode(p.dout[(size_t)g], sent, p.out, (uint64_t)off, (int64_t)cnt, reinterpret_cast<int8_t*>(q),
-                                 reinterpret_cast<uint8_t*>(q + p.reply_eoff[(size_t)g]), p.dout[(size_t)g], sent,
-                                 fa::kMx8EncFused, st));
-    return FA_OK;
-}
-
-// After reply_stage ran on every GPU: a round with `sent` left codes, the bootstrap left `sent`.
-void reply_round_done(Part& p) {
-    p.reply_has_codes = p.reply_has_sent;
-    p.reply_has_sent = true;
-    p.reply_counted = !p.reply_has_codes;
-    p.reply_nan = 0;
-}
-
-int clip_take_reference(Part& p, int g, int j, hipStream_t st) {
-    const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
-    if (cnt == 0) return FA_OK;
-    const char* out = static_cast<const char*>(p.dout[(size_t)g]) + lo * dsize(p.out);
-    float* ref = p.cref[(size_t)g] + lo;
-    if (p.out == FA_F32) FA_HIP(hipMemcpyAsync(ref, out, cnt * 4, hipMemcpyDeviceToDevice, st));
-    else FA_HIP(fa::launch_clip_widen(out, p.out, ref, (int64_t)cnt, st));
-    return FA_OK;
-}
-
-// Rules 1-4 for part p (range layout): the distance pass (measure_pass), then the host arithmetic.  Leaves the
-// round's report in the part.
-int krum_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* plan) {
-    const size_t D = (size_t)p.D;
-    p.krum_q.assign(D * D, 0.0);
-    if (int rc = measure_pass(ctx, p, s, D * D, krum_parts(p.D), "krum: distance-pass", p.krum_q.data(),
-                              [&](int, int, const void* const* clients, size_t cnt, double* d_part, double* d_out,
-                                  hipStream_t st) {
-                                  return pairdist_on(ctx->tuning.tu, clients, p.D, cnt, p.in, d_part, d_out, st);
-                              }))
-        return rc;
-    p.krum_s.assign(D, 0.0);
-    p.krum_sel.assign(D, 0);
-    krum_select(p.krum_q.data(), p.D, p.krum_f, p.krum_m, p.krum_s.data(), p.krum_sel.data(), &p.krum_n);
-    std::vector<float> wp(D);
-    krum_weights(w, p.krum_sel.data(), p.D, wp.data());
-    for (size_t k = 0; k < D; ++k)
-        if (p.krum_sel[k]) {
-            plan->inc.push_back((int)k);
-            plan->w.push_back(wp[k]);
-        }
-    p.krum_reported = true;
-    return FA_OK;
-}
-
-// Rules 0-4 for part p (range layout): T fused passes (measure_pass over the included clients alone, 2 m results: Q
-// then B), each followed by the host arithmetic; a pass that finds a non-finite bucket is void and repeated without
-// its owner.  The plan is the final chain's: the included clients and alpha^T.  Leaves the round's trace in the part.
-int geomed_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* plan) {
-    const size_t D = (size_t)p.D;
-    const int T = p.geomed_iters;
-    p.geomed_q.assign((size_t)T * D, 0.0);
-    p.geomed_w.assign((size_t)(T + 1) * D, 0.0f);
-    p.geomed_obj.assign((size_t)T, 0.0);
-    p.geomed_in.assign(D, 0);
-    p.geomed_passes = 0;
-    std::vector<int>& inc = p.geomed_in;
-    std::vector<float> alpha(D, 0.0f);
-    for (size_t k = 0; k < D; ++k) {
-        inc[k] = w[k] > 0.0f ? 1 : 0;
-        if (inc[k]) alpha[k] = w[k];
-    }
-    std::vector<int> idx;
-    std::vector<float> wsub;
-    std::vector<const void*> sub;
-    std::vector<double> res;
-    const double* last_q = nullptr;  // the last valid pass's row
-    int t = 0;
-    while (t < T) {
-        idx.clear();
-        wsub.clear();
-        for (size_t k = 0; k < D; ++k)
-            if (inc[k]) {
-                idx.push_back((int)k);
-                wsub.push_back(alpha[k]);
-            }
-        const size_t m = idx.size();
-        if (m == 0) break;  // nobody left: the aggregate is +0
-        res.assign(2 * m, 0.0);
-        if (int rc = measure_pass(ctx, p, s, 2 * m, kGeomedParts, "geomed: fused pass", res.data(),
-                                  [&](int, int, const void* const* clients, size_t cnt, double* d_part, double* d_out,
-                                      hipStream_t st) {
-                                      sub.resize(m);
-                                      for (size_t i = 0; i < m; ++i) sub[i] = clients[idx[i]];
-                                      return geomed_pass_on(ctx->tuning.tu, sub.data(), wsub.data(), (int)m, cnt, p.in, nullptr,
-                                                            d_part, d_out, st);
-                                  }))
-            return rc;
-        bool removed = false;
-        for (size_t i = 0; i < m; ++i)
-            if (res[m + i] > 0.0) {  // rule 2: a non-finite bucket poisons v; the pass is void
-                inc[(size_t)idx[i]] = 0;
-                removed = true;
-            }
-        if (removed) {
-            for (size_t k = 0; k < D; ++k) alpha[k] = inc[k] ? w[k] : 0.0f;
-            if (last_q) geomed_weights(w, last_q, inc.data(), p.D, p.geomed_nu, alpha.data(), nullptr);
-            continue;
-        }
-        double* qrow = &p.geomed_q[(size_t)t * D];
-        for (size_t i = 0; i < m; ++i) qrow[(size_t)idx[i]] = res[i];
-        std::copy(alpha.begin(), alpha.end(), p.geomed_w.begin() + (ptrdiff_t)((size_t)t * D));
-        geomed_weights(w, qrow, inc.data(), p.D, p.geomed_nu, alpha.data(), &p.geomed_obj[(size_t)t]);
-        last_q = qrow;
-        p.geomed_passes = ++t;
-    }
-    for (size_t k = 0; k < D; ++k)
-        if (!inc[k]) alpha[k] = 0.0f;
-    std::copy(alpha.begin(), alpha.end(), p.geomed_w.begin() + (ptrdiff_t)((size_t)p.geomed_passes * D));
-    for (size_t k = 0; k < D; ++k)
-        if (inc[k]) {
-            plan->inc.push_back((int)k);
-            plan->w.push_back(alpha[k]);
-        }
-    p.geomed_reported = true;
-    return FA_OK;
-}
-
-// Rules 1-2 of the Bulyan stage for part p (range layout): the distance pass (measure_pass), then the iterated
-// selection.  The plan's clients are the picks in ascending client order; its weights stay empty (the rule has
-// none).  Leaves the round's report in the part.
-int bulyan_plan(fa_ctx* ctx, Part& p, hipStream_t s, SubsetPlan* plan) {
-    const size_t D = (size_t)p.D;
-    p.bulyan_q.assign(D * D, 0.0);
-    if (int rc = measure_pass(ctx, p, s, D * D, krum_parts(p.D), "bulyan: distance-pass", p.bulyan_q.data(),
-                              [&](int, int, const void* const* clients, size_t cnt, double* d_part, double* d_out,
-                                  hipStream_t st) {
-                                  return pairdist_on(ctx->tuning.tu, clients, p.D, cnt, p.in, d_part, d_out, st);
-                              }))
-        return rc;
-    p.bulyan_s.assign(D, 0.0);
-    p.bulyan_order.assign(D, -1);
-    p.bulyan_sel.assign(D, 0);
-    bulyan_select(p.bulyan_q.data(), p.D, p.bulyan_f, p.bulyan_order.data(), p.bulyan_s.data(), p.bulyan_sel.data(),
-                  &p.bulyan_n);
-    for (size_t k = 0; k < D; ++k)
-        if (p.bulyan_sel[k]) plan->inc.push_back((int)k);
-    p.bulyan_reported = true;
-    return FA_OK;
-}
-
-// Rule 3 for piece j of GPU g (the current device), into dst (dtype odt): the centred mean over the plan's
-// clients keeping max(1, theta' - 2f) of them, +0 when nobody was picked.
-int bulyan_piece(fa_ctx* ctx, Part& p, int g, int j, const SubsetPlan& plan, void* dst, fa_dtype odt, hipStream_t st) {
-    const size_t cnt = piece_cnt(p, g, j);
-    if (cnt == 0) return FA_OK;
-    if (plan.inc.empty()) {
-        FA_HIP(hipMemsetAsync(dst, 0, cnt * dsize(odt), st));
-        return FA_OK;
-    }
-    std::vector<const void*> ptrs;
-    for (int k : plan.inc) ptrs.push_back(piece_ptr(p, g, k, j));
-    const int nc = (int)ptrs.size();
-    return centered_on(ctx->tuning.tu, ptrs.data(), nc, cnt, p.in, dst, odt, std::max(1, nc - 2 * p.bulyan_f), st);
-}
-
 // Enqueue the full reduction of part p on every GPU (the ctx's streams, or `s` for a one-GPU ctx):
 // range -> each GPU's shard; rs -> the clients' fp32 partials, piece by piece, each piece's RCCL
 // reduce-scatter (ring over xGMI) overlapping the reduction of the next.
@@ -1824,36 +623,11 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
     // small receipts kept where they arrived are read there only by the finalize that ends their round (the
     // caller keeps them until then); a reduction before it takes them into the slots first
     if (int rc = host_flush(ctx, p)) return rc;
-    const bool noisy = p.noise > 0.0f;  // never on an rs part
-    if (noisy && p.noise_round >= kNoiseRounds)
-        return fail(FA_ERR_STATE, "noise: part %d has used all 2^32 rounds of its seed (fa_set_noise a new seed and "
-                                  "fa_noise_set_round)", p.id);
     if (!p.rs) {
-        // a clip stage with a reference: the norm pass and the host's wait for its sums come first (without a
-        // reference the round is the bootstrap: the plain aggregate, reported as unclipped)
-        const bool clip = p.clip > 0.0f, clipping = clip && p.clip_has_ref;
-        SubsetPlan plan;
-        if (clip) {
-            p.clip_q.assign((size_t)p.D, 0.0);
-            p.clip_s.assign((size_t)p.D, 1.0f);
-            p.clip_in.assign((size_t)p.D, 1);
-            p.clip_n = 0;
-            p.clip_reported = true;
-            if (clipping)
-                if (int rc = clip_plan(ctx, p, w, s, &plan)) return rc;
-        }
-        // a Krum stage: the distance pass, the host's wait for its matrices and the selection come first
-        const bool krum = p.krum_m != 0;  // never with a clip stage
-        if (krum)
-            if (int rc = krum_plan(ctx, p, w, s, &plan)) return rc;
-        // a geomed stage (never with the two above): T fused passes, a host wait and the new weights after each
-        const bool geomed = p.geomed_iters != 0;
-        if (geomed)
-            if (int rc = geomed_plan(ctx, p, w, s, &plan)) return rc;
-        // a Bulyan stage (an FA_TRIMMED part: never with the three above): the same pass and wait, then the picks
-        const bool bulyan = p.bulyan_f >= 0;
-        if (bulyan)
-            if (int rc = bulyan_plan(ctx, p, s, &plan)) return rc;
+        // the stages (fa_stages.hip): what must precede the round's launches -- a refusal, the measure passes and the
+        // host's waits for their results -- comes first
+        StageRound round;
+        if (int rc = stage_round_begin(ctx, p, w, s, &round)) return rc;
         std::vector<const void*> ptrs;
         for (int g = 0; g < G; ++g) {
             GpuRes& r = ctx->gpu[(size_t)g];
@@ -1861,54 +635,22 @@ int reduce_part(fa_ctx* ctx, Part& p, const float* w, hipStream_t s) {
             hipStream_t st = s ? s : r.compute;
             int rc = wait_copies(ctx, g, st);
             if (rc) return rc;
-            const fa::Tuning& tu = ctx->tuning.tu;
             for (int j = 0; j < p.npiece[(size_t)g]; ++j) {  // one launch per piece, in order
-                const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
-                void* dst = static_cast<char*>(p.dout[(size_t)g]) + lo * dsize(p.out);
-                // the aggregate into adst (dst without a stage; FA_LITERAL never has one) -- clipped, if the part has a
-                // reference; with a server optimizer or a noise stage in fp32 (an f32 part: in its output, where the
-                // stages then run in place) -- then the noise (in place before a server optimizer, else into dst with
-                // the one rounding), then one step or the bootstrap of a part without a master, then the new reference
-                const bool opt = p.opt.rule != FA_OPT_NONE, wide = opt || noisy;
-                float* avg = !wide ? nullptr : p.out == FA_F32 ? static_cast<float*>(dst) : p.oavg[(size_t)g] + lo;
-                void* adst = wide ? (void*)avg : dst;
-                const fa_dtype adt = wide ? FA_F32 : p.out;
-                if (p.mode == FA_LITERAL) {
+                if (p.mode == FA_LITERAL) {                  // never has a stage
+                    void* dst = static_cast<char*>(p.dout[(size_t)g]) + piece_lo(p, g, j) * dsize(p.out);
                     const void* last = piece_ptr(p, g, p.last_slot >= 0 ? p.last_slot : p.D - 1, j);
-                    rc = reduce_on(ctx, g, tu, &last, w, 1, cnt, p.in, dst, p.out, FA_LITERAL, p.divisor, nullptr, st);
-                } else if (clipping || krum || geomed)
-                    rc = subset_chain(ctx, p, g, j, plan, adst, adt, st);
-                else if (bulyan)
-                    rc = bulyan_piece(ctx, p, g, j, plan, adst, adt, st);
-                else
-                    rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
-                                   mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
-                if (!rc && noisy)
-                    rc = noise_on(tu, avg, opt ? (void*)avg : dst, opt ? FA_F32 : p.out, p.noise, p.noise_seed,
-                                  (uint32_t)p.id, (uint32_t)p.noise_round, (uint64_t)(p.off[(size_t)g] + lo), cnt, st);
-                if (!rc && opt)
-                    rc = opt_on(tu, p.opt_master ? p.opt.rule : fa::kOptBoot, p.opt, avg, p.ox[(size_t)g] + lo,
-                                p.om[(size_t)g] + lo, opt_adaptive(p.opt.rule) ? p.ov[(size_t)g] + lo : nullptr, cnt,
-                                dst, p.out, st);
-                // with a reply stage the output is not final yet: the reference is taken after it, below
-                if (!rc && clip && !p.reply) rc = clip_take_reference(p, g, j, st);
+                    rc = reduce_on(ctx, g, ctx->tuning.tu, &last, w, 1, piece_cnt(p, g, j), p.in, dst, p.out, FA_LITERAL,
+                                   p.divisor, nullptr, st);
+                } else {
+                    rc = stage_piece(ctx, p, g, j, w, round, ptrs, st);
+                }
                 if (rc) return rc;
             }
-            if (p.reply) {  // y -> g' over the GPU's whole range, then the clip stage's reference from g'
-                rc = reply_stage(ctx, p, g, st);
-                for (int j = 0; !rc && clip && j < p.npiece[(size_t)g]; ++j) rc = clip_take_reference(p, g, j, st);
-                if (rc) return rc;
-            }
+            if ((rc = stage_gpu_end(ctx, p, g, st))) return rc;
             mark_done(p, g, st);
         }
-        if (p.reply) reply_round_done(p);
+        stage_round_end(p);
         set_range_runs(p, G);
-        if (p.opt.rule != FA_OPT_NONE) {  // one reducing call = one step (the first one without a master: none)
-            if (p.opt_master) ++p.opt_steps;
-            p.opt_master = true;
-        }
-        if (clip) p.clip_has_ref = true;  // what this round sent out
-        if (noisy) ++p.noise_round;       // one reducing call = one round of the generator
         return FA_OK;
     }
     if (p.mode == FA_LITERAL) {  // the last client's GPU computes the whole bucket; nothing to exchange
@@ -2005,7 +747,7 @@ int advance_prefix(fa_ctx* ctx, Part& p) {
     // that took the context's stage at its definition has none and stays non-eager when the stage goes; a part
     // with a stage is non-eager while it has one.
     if (!(ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) || p.rs || p.mode != FA_FEDAVG || p.ready || !p.acc[0] ||
-        staged(p) || p.mx8)
+        stages_on(p))
         return FA_OK;
     int j = p.reduced;
     while (j < p.D && p.submitted[(size_t)j]) ++j;
@@ -2222,144 +964,6 @@ void reset_round(Part& p) {
     p.ready = false;
 }
 
-// Waits for everything that may touch the part's stage state.  A reduction may have run on a caller's stream
-// that is gone by now, so this waits for the devices, not for a stream handle (state reads, writes and rule
-// changes are rare).
-int opt_quiesce(fa_ctx* ctx) {
-    for (int g = 0; g < ctx->G; ++g) {
-        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
-        FA_HIP(hipDeviceSynchronize());
-    }
-    return FA_OK;
-}
-
-// fa_set_server_opt on a part (o checked; not FA_LITERAL, not rs).  None: the stage and its state go.  The
-// same rule: only the hyperparameters change.  Another rule (or the first one): the arrays the rule needs are
-// allocated, x is kept when the part had a stage, m and v are zeroed.
-int set_part_opt(fa_ctx* ctx, Part& p, const fa_server_opt& o) {
-    if (o.rule == FA_OPT_NONE) {
-        free_opt(ctx, p);
-        return FA_OK;
-    }
-    if (o.rule == p.opt.rule) {
-        p.opt = o;
-        return FA_OK;
-    }
-    const size_t G = (size_t)ctx->G;
-    const bool fresh = p.opt.rule == FA_OPT_NONE;
-    if (!fresh)  // the arrays about to be zeroed or freed may still be in use
-        if (int rc = opt_quiesce(ctx)) return rc;
-    if (fresh) {
-        p.ox.assign(G, nullptr);
-        p.om.assign(G, nullptr);
-        p.ov.assign(G, nullptr);
-        p.opt_master = false;
-        p.opt_steps = 0;
-    }
-    for (size_t g = 0; g < G; ++g) {
-        DeviceGuard dg(ctx->gpu[g].dev);
-        const size_t bytes = std::max<size_t>(16, p.cnt[g] * 4);
-        auto need = [&](std::vector<float*>& arr, bool wanted, bool zero) -> int {
-            if (wanted && !arr[g] && hipMalloc((void**)&arr[g], bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                arr[g] = nullptr;
-                return fail(FA_ERR_NOMEM, "server opt: state alloc of %zu B failed on GPU %zu", bytes, g);
-            }
-            if (!wanted && arr[g]) {
-                (void)hipFree(arr[g]);
-                arr[g] = nullptr;
-            }
-            if (wanted && zero) FA_HIP(hipMemset(arr[g], 0, bytes));
-            return FA_OK;
-        };
-        int rc = need(p.ox, true, fresh);
-        if (!rc) rc = need(p.om, true, true);
-        if (!rc) rc = need(p.ov, opt_adaptive(o.rule), true);
-        if (rc) {
-            const std::string why = g_err;
-            free_opt(ctx, p);
-            g_err = why;
-            return rc;
-        }
-    }
-    // the zeroing ran on the null stream, which the context's non-blocking streams do not wait for
-    if (int rc = opt_quiesce(ctx)) return rc;
-    p.opt = o;
-    if (int rc = ensure_oavg(ctx, p, "server opt")) {
-        const std::string why = g_err;
-        free_opt(ctx, p);
-        g_err = why;
-        return rc;
-    }
-    // A rule change leaves a round already stepped as it is: the finalize after it copies out, one step per round.
-    if (fresh) restart_round_plain(p);
-    return FA_OK;
-}
-
-// fa_set_clip on a part (max_norm checked; an FA_FEDAVG part, not rs).  0: the stage and its arrays go.  A part
-// that has the stage: only the bound changes.  Else the reference (and a 16-bit part's first-term buffer) is
-// allocated; the part has no reference until a round or fa_clip_set_reference gives it one.
-int set_part_clip(fa_ctx* ctx, Part& p, float max_norm) {
-    if (max_norm == 0.0f) {
-        if (p.clip > 0.0f)  // the arrays may still be in use
-            if (int rc = opt_quiesce(ctx)) return rc;
-        free_clip(ctx, p);
-        return FA_OK;
-    }
-    if (p.clip > 0.0f) {
-        p.clip = max_norm;
-        return FA_OK;
-    }
-    const size_t G = (size_t)ctx->G;
-    p.cref.assign(G, nullptr);
-    p.cinit.assign(G, nullptr);
-    for (size_t g = 0; g < G; ++g) {
-        DeviceGuard dg(ctx->gpu[g].dev);
-        const size_t bytes = std::max<size_t>(16, p.cnt[g] * 4);
-        if (hipMalloc((void**)&p.cref[g], bytes) != hipSuccess ||
-            (p.in != FA_F32 && hipMalloc((void**)&p.cinit[g], bytes) != hipSuccess)) {
-            (void)hipGetLastError();
-            free_clip(ctx, p);
-            return fail(FA_ERR_NOMEM, "clip: reference alloc of %zu B failed on GPU %zu", bytes, g);
-        }
-    }
-    p.clip = max_norm;
-    p.clip_has_ref = false;
-    p.clip_reported = false;
-    restart_round_plain(p);
-    return FA_OK;
-}
-
-// fa_set_noise on a part (stddev checked; not FA_LITERAL, not rs).  0: the stage goes, and the aggregate buffer
-// unless a server optimizer keeps it.  A part that has the stage: stddev and seed change, the round stays.
-// Else the stage starts at round 0, a 16-bit part gets its fp32 aggregate buffer.
-int set_part_noise(fa_ctx* ctx, Part& p, float stddev, uint64_t seed) {
-    if (stddev == 0.0f) {
-        p.noise = 0.0f;
-        p.noise_seed = 0;
-        p.noise_round = 0;
-        drop_oavg_if_unused(ctx, p);
-        return FA_OK;
-    }
-    const bool fresh = !(p.noise > 0.0f);
-    p.noise = stddev;
-    if (int rc = ensure_oavg(ctx, p, "noise")) {
-        if (fresh) {
-            const std::string why = g_err;
-            p.noise = 0.0f;
-            drop_oavg_if_unused(ctx, p);  // what the failed attempt did allocate
-            g_err = why;
-        }
-        return rc;
-    }
-    p.noise_seed = seed;
-    if (fresh) {
-        p.noise_round = 0;
-        restart_round_plain(p);
-    }
-    return FA_OK;
-}
-
 // The end of a phase: wait for the submits, reduce on every GPU (unless the round's reduction is done
 // already: accumulate on arrival reached D, or fa_reduce_parts), copy the result out, reset the round.
 int finalize_impl(fa_ctx* ctx, int part_id, const Gather& dst, bool pinned) {
@@ -2431,7 +1035,7 @@ int reduce_parts_impl(fa_ctx* ctx, int n_parts, const int* ids, const float* con
     for (int i = 0; i < n_parts; ++i) {
         Part& p = *ps[(size_t)i];
         bool batch = !p.rs && p.mode == FA_FEDAVG && p.D <= fa::kMaxClients && p.n_host == 0 &&
-                     !staged(p);  // a part with a server-optimizer or clip stage: its own launches
+                     !staged(p);  // a part with a stage: its own launches
         for (int g = 0; batch && g < ctx->G; ++g) {
             DeviceGuard dg(ctx->gpu[(size_t)g].dev);
             batch = p.npiece[(size_t)g] == 1 &&
@@ -2565,102 +1169,6 @@ int reduce_parts_impl(fa_ctx* ctx, int n_parts, const int* ids, const float* con
     return FA_OK;
 }
 
-// ------------------------------------------------------------------ MX8 receipts (fa.h "MX8 receipts")
-
-// The scale bytes GPU g's range [off, off + cnt) touches: blocks off >> 5 .. (off + cnt - 1) >> 5.
-inline size_t mx8_scales(size_t off, size_t cnt) { return cnt ? ((off + cnt - 1) >> 5) - (off >> 5) + 1 : 0; }
-
-// The shadows of an MX8 part, allocated once: per GPU held x stride bytes.  q lies at the shadow's start, which
-// keeps the 16-byte phase of the slots and the output (all 16-byte aligned: the vector form applies).
-int ensure_mx8_buf(fa_ctx* ctx, Part& p) {
-    const size_t G = (size_t)ctx->G;
-    if (p.mx8_buf.size() == G) return FA_OK;
-    p.mx8_buf.assign(G, nullptr);
-    p.mx8_stride.assign(G, 0);
-    p.mx8_eoff.assign(G, 0);
-    for (size_t g = 0; g < G; ++g) {
-        const size_t held = (size_t)(p.c1[g] - p.c0[g]);
-        p.mx8_eoff[g] = (p.cnt[g] + 15) / 16 * 16;
-        p.mx8_stride[g] = (p.mx8_eoff[g] + mx8_scales(p.off[g], p.cnt[g]) + 255) / 256 * 256;
-        const size_t bytes = std::max<size_t>(256, held * p.mx8_stride[g]);
-        DeviceGuard dg(ctx->gpu[g].dev);
-        if (hipMalloc((void**)&p.mx8_buf[g], bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            p.mx8_buf[g] = nullptr;
-            const bool on = p.mx8, ref = p.mx8_ref;
-            free_mx8(ctx, p);  // what this attempt did allocate; the part stays an MX8 part
-            p.mx8 = on;
-            p.mx8_ref = ref;
-            return fail(FA_ERR_NOMEM, "mx8: shadow alloc of %zu B failed on GPU %zu", bytes, g);
-        }
-    }
-    return FA_OK;
-}
-
-// H2D of `bytes` host bytes into dev on GPU r's copy stream: straight from pinned memory, else through the pinned
-// chunks, double-buffered as a pageable submit.
-int mx8_h2d(GpuRes& r, char* dev, const char* src, size_t bytes, bool pinned) {
-    if (pinned) {
-        if (bytes) FA_HIP(hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, r.copy));
-        return FA_OK;
-    }
-    for (size_t o = 0; o < bytes; o += kStageBytes) {
-        const size_t b = std::min(kStageBytes, bytes - o);
-        const int i = r.stage_i;
-        r.stage_i ^= 1;
-        FA_HIP(hipEventSynchronize(r.stage_ev[i]));
-        r.pool->copy(r.stage[i], b, [&](size_t lo, size_t len, char* d) { std::memcpy(d, src + o + lo, len); });
-        FA_HIP(hipMemcpyAsync(dev + o, r.stage[i], b, hipMemcpyHostToDevice, r.copy));
-        FA_HIP(hipEventRecord(r.stage_ev[i], r.copy));
-    }
-    return FA_OK;
-}
-
-int submit_mx8_impl(fa_ctx* ctx, int part_id, int slot, const int8_t* q, const uint8_t* e, float weight, int flags) {
-    Trace tr("fa_submit_mx8 part %d slot %d", part_id, slot);
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (flags & ~(FA_HOST_PINNED | FA_MX8_ABSOLUTE)) return fail(FA_ERR_ARG, "mx8: unknown flags 0x%x", flags);
-    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
-    if (!p->mx8) return fail(FA_ERR_STATE, "mx8: part %d does not take MX8 receipts (fa_set_mx8)", part_id);
-    if (p->n > 0 && (!q || !e)) return fail(FA_ERR_ARG, "mx8: %s is null", !q ? "q" : "e");
-    const bool pinned = (flags & FA_HOST_PINNED) != 0, absolute = (flags & FA_MX8_ABSOLUTE) != 0;
-    if (!absolute && !p->mx8_ref)
-        return fail(FA_ERR_STATE, "mx8: part %d has no reference (no round reduced with fa_set_mx8 on, no "
-                                  "fa_mx8_set_reference): send a full receipt, or FA_MX8_ABSOLUTE", part_id);
-    if ((rc = ensure_mx8_buf(ctx, *p))) return rc;
-    if ((rc = host_flush(ctx, *p))) return rc;  // none is kept while mx8 is on; the plain path from here on
-    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
-        GpuRes& r = ctx->gpu[(size_t)g];
-        DeviceGuard dg(r.dev);
-        const size_t off = p->off[(size_t)g], cnt = p->cnt[(size_t)g];
-        if (cnt == 0) return FA_OK;
-        // after the part's last reducing call: it read the slot and wrote the reference
-        if (hipStream_t ds = p->done_stream[(size_t)g]) {
-            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
-            FA_HIP(hipStreamWaitEvent(r.copy, p->done[(size_t)g], 0));
-        }
-        char* dq = p->mx8_buf[(size_t)g] + (size_t)(slot - p->c0[(size_t)g]) * p->mx8_stride[(size_t)g];
-        char* de = dq + p->mx8_eoff[(size_t)g];
-        ++r.copy_gen;  // the next reducing call waits for the copy stream: the copies and the expansion
-        int rc2 = mx8_h2d(r, dq, reinterpret_cast<const char*>(q) + off, cnt, pinned);
-        if (!rc2) rc2 = mx8_h2d(r, de, reinterpret_cast<const char*>(e) + (off >> 5), mx8_scales(off, cnt), pinned);
-        if (rc2) return rc2;
-        for (int j = 0; j < p->npiece[(size_t)g]; ++j) {
-            const size_t lo = piece_lo(*p, g, j), pc = piece_cnt(*p, g, j);
-            const void* ref = absolute ? nullptr : static_cast<const char*>(p->dout[(size_t)g]) + lo * dsize(p->out);
-            FA_HIP(fa::launch_mx8_expand(reinterpret_cast<const int8_t*>(dq) + lo,
-                                         reinterpret_cast<const uint8_t*>(de) + (((off + lo) >> 5) - (off >> 5)),
-                                         (uint64_t)(off + lo), (int64_t)pc, ref, p->out, piece_ptr(*p, g, slot, j), p->in,
-                                         r.copy));
-        }
-        return FA_OK;
-    });
-    if (rc) return rc;
-    return mark_submitted(ctx, *p, slot, weight);
-}
-
 int tuning_from(const fa_tuning* t, CtxTuning* io) {
     if (!t) return fail(FA_ERR_ARG, "tuning is null");
     CtxTuning nt = *io;
@@ -2719,7 +1227,9 @@ void tuning_to(const CtxTuning& c, fa_tuning* t) {
     t->piece_split_kib = c.piece_split ? (int)(c.piece_split >> 10) : -1;
 }
 
-}  // namespace
+}  // namespace fah
+
+using namespace fah;
 
 extern "C" {
 
@@ -2906,16 +1416,9 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
                                     "FA_SHARD_CLIENT_RS context (use FA_SHARD_RANGE)");
         if (int rc = check_trim(ctx->trim, n_clients)) return rc;
     }
-    const bool krummed = ctx->krum_m != 0 && mode == FA_FEDAVG && !rs;  // takes the context's Krum stage
-    int krum_m = 0;
-    if (krummed)
-        if (int rc = check_krum(n_clients, ctx->krum_f, ctx->krum_m, &krum_m)) return rc;
-    const bool geomedded = ctx->geomed_iters != 0 && mode == FA_FEDAVG && !rs;  // takes the context's geomed stage
-    if (geomedded)
-        if (int rc = check_geomed(n_clients, ctx->geomed_iters, ctx->geomed_nu)) return rc;
-    const bool bulyaned = ctx->bulyan_f >= 0 && mode == FA_TRIMMED;  // takes the context's Bulyan stage
-    if (bulyaned)
-        if (int rc = check_bulyan(n_clients, ctx->bulyan_f)) return rc;
+    StageCfgs dflt;      // the context's default stages, and which of them this part takes: checked against
+    unsigned taken = 0;  // n_clients before the part of the same id goes
+    if (int rc = taken_defaults(ctx, mode, n_clients, &dflt, &taken)) return rc;
     auto it = ctx->parts.find(part_id);
     if (it != ctx->parts.end()) {
         free_part(ctx, it->second);
@@ -2935,11 +1438,7 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
     p.submitted.assign((size_t)n_clients, 0);
     p.host_src.assign((size_t)n_clients, {});
     const size_t G = (size_t)ctx->G;
-    const bool staged = ctx->opt.rule != FA_OPT_NONE && mode != FA_LITERAL && !rs;  // takes the context's stage
-    const bool clipped = ctx->clip > 0.0f && mode == FA_FEDAVG && !rs;  // takes the context's clip bound
-    const bool noisy = ctx->noise > 0.0f && mode != FA_LITERAL && !rs;  // takes the context's noise stage
-    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !staged && !clipped &&
-                       !krummed && !geomedded && !noisy && !ctx->mx8 && !ctx->mx8_reply;
+    const bool eager = (ctx->flags & FA_ACCUMULATE_ON_ARRIVAL) && !rs && mode == FA_FEDAVG && !taken;
     if (rs) {
         const size_t unit = G * kShardUnit;
         p.npad = (n_elems + unit - 1) / unit * unit;
@@ -3018,867 +1517,15 @@ int fa_bucket_define(fa_ctx* ctx, int part_id, size_t n_elems, fa_dtype in, fa_d
             p.acc[g] = reinterpret_cast<float*>(p.pool[g] + extra_off);
         }
     }
-    if (staged) {
-        if (int rc = set_part_opt(ctx, p, ctx->opt)) {
-            const std::string why = g_err;
-            free_part(ctx, p);
-            g_err = why;
-            return rc;
-        }
-    }
-    if (clipped) {
-        if (int rc = set_part_clip(ctx, p, ctx->clip)) {
-            const std::string why = g_err;
-            free_part(ctx, p);
-            g_err = why;
-            return rc;
-        }
-    }
-    if (krummed) {
-        p.krum_f = ctx->krum_f;
-        p.krum_m = krum_m;
-    }
-    if (geomedded) {
-        p.geomed_iters = ctx->geomed_iters;
-        p.geomed_nu = ctx->geomed_nu;
-    }
-    if (bulyaned) p.bulyan_f = ctx->bulyan_f;
-    if (noisy) {
-        if (int rc = set_part_noise(ctx, p, ctx->noise, ctx->noise_seed)) {
-            const std::string why = g_err;
-            free_part(ctx, p);
-            g_err = why;
-            return rc;
-        }
-    }
-    p.mx8 = ctx->mx8 && mode != FA_LITERAL && !rs;
-    p.reply = ctx->mx8_reply && mode != FA_LITERAL && !rs;
+    for (int id = 0; id < kStages; ++id)
+        if (taken >> id & 1)
+            if (int rc = set_part_stage(ctx, p, (StageId)id, dflt)) {
+                const std::string why = g_err;
+                free_part(ctx, p);
+                g_err = why;
+                return rc;
+            }
     ctx->parts.emplace(part_id, std::move(p));
-    return FA_OK;
-}
-
-int fa_set_server_opt(fa_ctx* ctx, int part_id, const fa_server_opt* opt) {
-    g_err.clear();
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    const fa_server_opt o = opt ? *opt : fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (int rc = check_opt(o)) return rc;
-    if (o.rule != FA_OPT_NONE && (ctx->flags & FA_SHARD_CLIENT_RS))
-        return fail(FA_ERR_ARG, "server opt: not on an FA_SHARD_CLIENT_RS context (its aggregate is not bit-specified)");
-    if (part_id < 0) {
-        ctx->opt = o;
-        return FA_OK;
-    }
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (o.rule != FA_OPT_NONE && p->mode == FA_LITERAL)
-        return fail(FA_ERR_ARG, "server opt: part %d is an FA_LITERAL part", part_id);
-    return set_part_opt(ctx, *p, o);
-}
-
-int fa_server_opt_set_state(fa_ctx* ctx, int part_id, const float* x, const float* m, const float* v, uint64_t steps) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (p->opt.rule == FA_OPT_NONE) return fail(FA_ERR_STATE, "part %d has no server-optimizer stage", part_id);
-    if ((rc = opt_quiesce(ctx))) return rc;
-    for (int g = 0; g < ctx->G; ++g) {
-        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
-        const size_t off = p->off[(size_t)g], bytes = p->cnt[(size_t)g] * 4;
-        if (!bytes) continue;
-        if (x) FA_HIP(hipMemcpy(p->ox[(size_t)g], x + off, bytes, hipMemcpyHostToDevice));
-        if (m) FA_HIP(hipMemcpy(p->om[(size_t)g], m + off, bytes, hipMemcpyHostToDevice));
-        if (v && opt_adaptive(p->opt.rule)) FA_HIP(hipMemcpy(p->ov[(size_t)g], v + off, bytes, hipMemcpyHostToDevice));
-    }
-    if ((rc = opt_quiesce(ctx))) return rc;  // the copies land before any later launch on the ctx streams
-    if (x) p->opt_master = true;
-    p->opt_steps = steps;
-    return FA_OK;
-}
-
-int fa_server_opt_get_state(fa_ctx* ctx, int part_id, float* x, float* m, float* v, uint64_t* steps) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (p->opt.rule == FA_OPT_NONE) return fail(FA_ERR_STATE, "part %d has no server-optimizer stage", part_id);
-    if (steps) *steps = p->opt_steps;
-    if (!x && !m && !v) return FA_OK;  // the step count alone is host state: no device wait
-    if ((rc = opt_quiesce(ctx))) return rc;
-    for (int g = 0; g < ctx->G; ++g) {
-        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
-        const size_t off = p->off[(size_t)g], bytes = p->cnt[(size_t)g] * 4;
-        if (!bytes) continue;
-        if (x) FA_HIP(hipMemcpy(x + off, p->ox[(size_t)g], bytes, hipMemcpyDeviceToHost));
-        if (m) FA_HIP(hipMemcpy(m + off, p->om[(size_t)g], bytes, hipMemcpyDeviceToHost));
-        if (v && opt_adaptive(p->opt.rule)) FA_HIP(hipMemcpy(v + off, p->ov[(size_t)g], bytes, hipMemcpyDeviceToHost));
-    }
-    return FA_OK;
-}
-
-int fa_get_server_opt(fa_ctx* ctx, int part_id, fa_server_opt* opt) {
-    g_err.clear();
-    if (!ctx || !opt) return fail(FA_ERR_ARG, "ctx or opt is null");
-    if (part_id < 0) {
-        *opt = ctx->opt;
-        return FA_OK;
-    }
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    *opt = p->opt;
-    return FA_OK;
-}
-
-int fa_server_opt_device(fa_ctx* ctx, int gpu, const fa_server_opt* opt, const float* d_avg, float* d_x, float* d_m,
-                         float* d_v, size_t n, void* d_out, fa_dtype out, void* hip_stream) {
-    g_err.clear();
-    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
-    if (!opt) return fail(FA_ERR_ARG, "server opt: opt is null");
-    if (int rc = check_opt(*opt)) return rc;
-    if (opt->rule == FA_OPT_NONE) return fail(FA_ERR_ARG, "server opt: rule FA_OPT_NONE takes no step");
-    if (!dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
-    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    if (n == 0) return FA_OK;
-    const bool needs_v = opt_adaptive(opt->rule);
-    if (!d_avg || !d_x || !d_m || (needs_v && !d_v))
-        return fail(FA_ERR_ARG, "server opt: %s pointer is null", !d_avg ? "d_avg" : !d_x ? "d_x" : !d_m ? "d_m" : "d_v");
-    if (!aligned(d_avg, 4) || !aligned(d_x, 4) || !aligned(d_m, 4) || (needs_v && !aligned(d_v, 4)))
-        return fail(FA_ERR_ALIGN, "server opt: aggregate or state not 4-byte aligned");
-    if (d_out && !aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
-    const DeviceCall c = device_call(ctx, gpu, hip_stream);
-    DeviceGuard dg(c.dev);
-    return opt_on(c.tu, opt->rule, *opt, d_avg, d_x, d_m, needs_v ? d_v : nullptr, n, d_out, out, c.s);
-}
-
-int fa_set_clip(fa_ctx* ctx, int part_id, float max_norm) {
-    g_err.clear();
-    if (!finite_f(max_norm) || max_norm < 0.0f)
-        return fail(FA_ERR_ARG, "clip: max_norm %g must be finite and >= 0", (double)max_norm);
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    if (max_norm > 0.0f && (ctx->flags & FA_SHARD_CLIENT_RS))
-        return fail(FA_ERR_ARG, "clip: not on an FA_SHARD_CLIENT_RS context (its aggregate is not bit-specified; use "
-                                "FA_SHARD_RANGE)");
-    if (part_id < 0) {
-        if (max_norm > 0.0f && ctx->krum_m != 0)
-            return fail(FA_ERR_ARG, "clip: the context default has a Krum stage (the two stages do not compose)");
-        if (max_norm > 0.0f && ctx->geomed_iters != 0)
-            return fail(FA_ERR_ARG, "clip: the context default has a geomed stage (the two stages do not compose)");
-        ctx->clip = max_norm;
-        return FA_OK;
-    }
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (max_norm > 0.0f && p->mode != FA_FEDAVG)
-        return fail(FA_ERR_ARG, "clip: part %d is an %s part (the stage clips FA_FEDAVG updates)", part_id,
-                    p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_TRIMMED");
-    if (max_norm > 0.0f && p->krum_m != 0)
-        return fail(FA_ERR_ARG, "clip: part %d has a Krum stage (the two stages do not compose)", part_id);
-    if (max_norm > 0.0f && p->geomed_iters != 0)
-        return fail(FA_ERR_ARG, "clip: part %d has a geomed stage (the two stages do not compose)", part_id);
-    return set_part_clip(ctx, *p, max_norm);
-}
-
-int fa_clip_set_reference(fa_ctx* ctx, int part_id, const float* g) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (!(p->clip > 0.0f)) return fail(FA_ERR_STATE, "part %d has no clip stage", part_id);
-    if ((rc = opt_quiesce(ctx))) return rc;
-    for (int gi = 0; g && gi < ctx->G; ++gi) {
-        DeviceGuard dg(ctx->gpu[(size_t)gi].dev);
-        const size_t bytes = p->cnt[(size_t)gi] * 4;
-        if (bytes) FA_HIP(hipMemcpy(p->cref[(size_t)gi], g + p->off[(size_t)gi], bytes, hipMemcpyHostToDevice));
-    }
-    if (g && (rc = opt_quiesce(ctx))) return rc;  // the copies land before any later launch on the ctx streams
-    p->clip_has_ref = g != nullptr;
-    return FA_OK;
-}
-
-int fa_clip_get_reference(fa_ctx* ctx, int part_id, float* g) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (!(p->clip > 0.0f)) return fail(FA_ERR_STATE, "part %d has no clip stage", part_id);
-    if (!p->clip_has_ref) return fail(FA_ERR_STATE, "part %d has no clip reference yet", part_id);
-    if (!g && p->n) return fail(FA_ERR_ARG, "g is null");
-    if ((rc = opt_quiesce(ctx))) return rc;
-    for (int gi = 0; gi < ctx->G; ++gi) {
-        DeviceGuard dg(ctx->gpu[(size_t)gi].dev);
-        const size_t bytes = p->cnt[(size_t)gi] * 4;
-        if (bytes) FA_HIP(hipMemcpy(g + p->off[(size_t)gi], p->cref[(size_t)gi], bytes, hipMemcpyDeviceToHost));
-    }
-    return FA_OK;
-}
-
-int fa_clip_get_round(fa_ctx* ctx, int part_id, double* sumsq, float* scales, int* included, int* n_clipped) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (!(p->clip > 0.0f)) return fail(FA_ERR_STATE, "part %d has no clip stage", part_id);
-    if (!p->clip_reported) return fail(FA_ERR_STATE, "part %d: no round reduced with the clip stage yet", part_id);
-    for (size_t k = 0; k < (size_t)p->D; ++k) {
-        if (sumsq) sumsq[k] = p->clip_q[k];
-        if (scales) scales[k] = p->clip_in[k] ? p->clip_s[k] : 0.0f;
-        if (included) included[k] = p->clip_in[k];
-    }
-    if (n_clipped) *n_clipped = p->clip_n;
-    return FA_OK;
-}
-
-float fa_clip_scale(double sumsq, float max_norm, int* excluded) { return clip_scale(sumsq, max_norm, excluded); }
-
-int fa_clip_sumsq_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in,
-                         const float* d_ref, double* h_sumsq, void* hip_stream) {
-    g_err.clear();
-    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
-    if (D < 1) return fail(FA_ERR_ARG, "clip: D must be >= 1");
-    if (!dvalid(in)) return fail(FA_ERR_ARG, "bad dtype");
-    if (!h_sumsq) return fail(FA_ERR_ARG, "clip: h_sumsq is null");
-    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    if (n == 0) {
-        std::fill(h_sumsq, h_sumsq + D, 0.0);
-        return FA_OK;
-    }
-    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
-    if (!d_ref) return fail(FA_ERR_ARG, "clip: d_ref is null");
-    if (!aligned(d_ref, 4)) return fail(FA_ERR_ALIGN, "clip: reference not 4-byte aligned");
-    return measure_device(ctx, gpu, hip_stream, (size_t)D, kClipParts, "clip: norm-pass", h_sumsq,
-                          [&](const DeviceCall& c, double* d_part, double* d_out) {
-                              return clip_sumsq_on(c.tu, d_clients, D, n, in, d_ref, d_part, d_out, c.s);
-                          });
-}
-
-int fa_set_krum(fa_ctx* ctx, int part_id, int f, int m) {
-    g_err.clear();
-    if (f < 0 || m < -1) return fail(FA_ERR_ARG, "krum: f = %d, m = %d (f >= 0; m >= 1, -1 for D - f, 0 removes the stage)", f, m);
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    if (m != 0 && (ctx->flags & FA_SHARD_CLIENT_RS))
-        return fail(FA_ERR_ARG, "krum: not on an FA_SHARD_CLIENT_RS context (a pair's distance needs both clients on one "
-                                "GPU; use FA_SHARD_RANGE)");
-    if (part_id < 0) {
-        if (m != 0 && ctx->clip > 0.0f)
-            return fail(FA_ERR_ARG, "krum: the context default has a clip stage (the two stages do not compose)");
-        if (m != 0 && ctx->geomed_iters != 0)
-            return fail(FA_ERR_ARG, "krum: the context default has a geomed stage (the two stages do not compose)");
-        ctx->krum_f = m != 0 ? f : 0;
-        ctx->krum_m = m;
-        return FA_OK;
-    }
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (m == 0) {  // the stage and its report go
-        p->krum_f = p->krum_m = 0;
-        p->krum_reported = false;
-        p->krum_q.clear();
-        p->krum_s.clear();
-        p->krum_sel.clear();
-        return FA_OK;
-    }
-    if (p->mode != FA_FEDAVG)
-        return fail(FA_ERR_ARG, "krum: part %d is an %s part (the stage selects the owners of an FA_FEDAVG average)", part_id,
-                    p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_TRIMMED");
-    if (p->clip > 0.0f)
-        return fail(FA_ERR_ARG, "krum: part %d has a clip stage (the two stages do not compose)", part_id);
-    if (p->geomed_iters != 0)
-        return fail(FA_ERR_ARG, "krum: part %d has a geomed stage (the two stages do not compose)", part_id);
-    int mm = 0;
-    if ((rc = check_krum(p->D, f, m, &mm))) return rc;
-    const bool fresh = p->krum_m == 0;
-    p->krum_f = f;
-    p->krum_m = mm;
-    if (fresh) {
-        p->krum_reported = false;
-        restart_round_plain(*p);
-    }
-    return FA_OK;
-}
-
-int fa_krum_get_round(fa_ctx* ctx, int part_id, double* dist, double* scores, int* selected, int* n_selected) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (p->krum_m == 0) return fail(FA_ERR_STATE, "part %d has no Krum stage", part_id);
-    if (!p->krum_reported) return fail(FA_ERR_STATE, "part %d: no round reduced with the Krum stage yet", part_id);
-    const size_t D = (size_t)p->D;
-    if (dist) std::copy(p->krum_q.begin(), p->krum_q.end(), dist);
-    for (size_t k = 0; k < D; ++k) {
-        if (scores) scores[k] = p->krum_s[k];
-        if (selected) selected[k] = p->krum_sel[k];
-    }
-    if (n_selected) *n_selected = p->krum_n;
-    return FA_OK;
-}
-
-int fa_krum_select(const double* dist, int D, int f, int m, double* scores, int* selected, int* n_selected) {
-    g_err.clear();
-    if (!dist) return fail(FA_ERR_ARG, "krum: dist is null");
-    if (D < 1) return fail(FA_ERR_ARG, "krum: D must be >= 1");
-    int mm = 0;
-    if (int rc = check_krum(D, f, m, &mm)) return rc;
-    krum_select(dist, D, f, mm, scores, selected, n_selected);
-    return FA_OK;
-}
-
-int fa_krum_weights(const float* w, const int* selected, int D, float* w_out) {
-    g_err.clear();
-    if (!w || !selected || !w_out) return fail(FA_ERR_ARG, "krum: w, selected or w_out is null");
-    if (D < 1) return fail(FA_ERR_ARG, "krum: D must be >= 1");
-    krum_weights(w, selected, D, w_out);
-    return FA_OK;
-}
-
-int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, double* h_dist,
-                       void* hip_stream) {
-    g_err.clear();
-    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
-    if (D < 1 || D > FA_KRUM_MAX_CLIENTS) return fail(FA_ERR_ARG, "krum: D = %d outside 1..%d", D, FA_KRUM_MAX_CLIENTS);
-    if (!dvalid(in)) return fail(FA_ERR_ARG, "bad dtype");
-    if (!h_dist) return fail(FA_ERR_ARG, "krum: h_dist is null");
-    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    const size_t DD = (size_t)D * (size_t)D;
-    if (n == 0) {
-        std::fill(h_dist, h_dist + DD, 0.0);
-        return FA_OK;
-    }
-    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
-    return measure_device(ctx, gpu, hip_stream, DD, krum_parts(D), "krum: distance-pass", h_dist,
-                          [&](const DeviceCall& c, double* d_part, double* d_out) {
-                              return pairdist_on(c.tu, d_clients, D, n, in, d_part, d_out, c.s);
-                          });
-}
-
-int fa_set_geomed(fa_ctx* ctx, int part_id, int iters, float nu) {
-    g_err.clear();
-    if (int rc = check_geomed(0, iters, nu)) return rc;
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    if (iters != 0 && (ctx->flags & FA_SHARD_CLIENT_RS))
-        return fail(FA_ERR_ARG, "geomed: not on an FA_SHARD_CLIENT_RS context (a distance needs every client of an element "
-                                "on one GPU; use FA_SHARD_RANGE)");
-    if (part_id < 0) {
-        if (iters != 0 && ctx->clip > 0.0f)
-            return fail(FA_ERR_ARG, "geomed: the context default has a clip stage (the two stages do not compose)");
-        if (iters != 0 && ctx->krum_m != 0)
-            return fail(FA_ERR_ARG, "geomed: the context default has a Krum stage (the two stages do not compose)");
-        ctx->geomed_iters = iters;
-        ctx->geomed_nu = iters != 0 ? nu : 0.0f;
-        return FA_OK;
-    }
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (iters == 0) {  // the stage and its trace go
-        p->geomed_iters = 0;
-        p->geomed_nu = 0.0f;
-        p->geomed_reported = false;
-        p->geomed_passes = 0;
-        p->geomed_q.clear();
-        p->geomed_w.clear();
-        p->geomed_obj.clear();
-        p->geomed_in.clear();
-        return FA_OK;
-    }
-    if (p->mode != FA_FEDAVG)
-        return fail(FA_ERR_ARG, "geomed: part %d is an %s part (the stage re-weights the owners of an FA_FEDAVG average)",
-                    part_id, p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_TRIMMED");
-    if (p->clip > 0.0f) return fail(FA_ERR_ARG, "geomed: part %d has a clip stage (the two stages do not compose)", part_id);
-    if (p->krum_m != 0) return fail(FA_ERR_ARG, "geomed: part %d has a Krum stage (the two stages do not compose)", part_id);
-    if ((rc = check_geomed(p->D, iters, nu))) return rc;
-    const bool fresh = p->geomed_iters == 0;
-    p->geomed_iters = iters;
-    p->geomed_nu = nu;
-    if (fresh) {
-        p->geomed_reported = false;
-        restart_round_plain(*p);
-    }
-    return FA_OK;
-}
-
-int fa_get_geomed(fa_ctx* ctx, int part_id, int* iters, float* nu) {
-    g_err.clear();
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    int it = ctx->geomed_iters;
-    float v = ctx->geomed_nu;
-    if (part_id >= 0) {
-        Part* p;
-        int rc = check_part(ctx, part_id, &p);
-        if (rc) return rc;
-        it = p->geomed_iters;
-        v = p->geomed_nu;
-    }
-    if (iters) *iters = it;
-    if (nu) *nu = v;
-    return FA_OK;
-}
-
-int fa_geomed_get_round(fa_ctx* ctx, int part_id, int* n_passes, double* sumsq, float* weights, int* included,
-                        double* objective) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (p->geomed_iters == 0) return fail(FA_ERR_STATE, "part %d has no geomed stage", part_id);
-    if (!p->geomed_reported) return fail(FA_ERR_STATE, "part %d: no round reduced with the geomed stage yet", part_id);
-    const size_t D = (size_t)p->D, np = (size_t)p->geomed_passes;
-    if (n_passes) *n_passes = p->geomed_passes;
-    if (sumsq) std::copy(p->geomed_q.begin(), p->geomed_q.begin() + (ptrdiff_t)(np * D), sumsq);
-    if (weights) std::copy(p->geomed_w.begin(), p->geomed_w.begin() + (ptrdiff_t)((np + 1) * D), weights);
-    if (included) std::copy(p->geomed_in.begin(), p->geomed_in.end(), included);
-    if (objective) std::copy(p->geomed_obj.begin(), p->geomed_obj.begin() + (ptrdiff_t)np, objective);
-    return FA_OK;
-}
-
-int fa_geomed_weights(const float* w, const double* sumsq, int* included, int D, float nu, float* w_out) {
-    g_err.clear();
-    if (!w || !sumsq || !included || !w_out) return fail(FA_ERR_ARG, "geomed: w, sumsq, included or w_out is null");
-    if (D < 1) return fail(FA_ERR_ARG, "geomed: D must be >= 1");
-    if (!finite_f(nu) || !(nu > 0.0f)) return fail(FA_ERR_ARG, "geomed: nu %g must be finite and > 0", (double)nu);
-    geomed_weights(w, sumsq, included, D, nu, w_out, nullptr);
-    return FA_OK;
-}
-
-int fa_geomed_pass_device(fa_ctx* ctx, int gpu, const void* const* d_clients, const float* h_weights, int D, size_t n,
-                          fa_dtype in, float* d_v, double* h_sumsq, double* h_nonfinite, void* hip_stream) {
-    g_err.clear();
-    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
-    if (D < 1 || D > FA_GEOMED_MAX_CLIENTS)
-        return fail(FA_ERR_ARG, "geomed: D = %d outside 1..%d", D, FA_GEOMED_MAX_CLIENTS);
-    if (!dvalid(in)) return fail(FA_ERR_ARG, "bad dtype");
-    if (!h_weights) return fail(FA_ERR_ARG, "geomed: h_weights is null");
-    if (!h_sumsq || !h_nonfinite) return fail(FA_ERR_ARG, "geomed: %s is null", !h_sumsq ? "h_sumsq" : "h_nonfinite");
-    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    if (n == 0) {
-        std::fill(h_sumsq, h_sumsq + D, 0.0);
-        std::fill(h_nonfinite, h_nonfinite + D, 0.0);
-        return FA_OK;
-    }
-    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
-    if (d_v && !aligned(d_v, 4)) return fail(FA_ERR_ALIGN, "geomed: d_v not 4-byte aligned");
-    std::vector<double> res(2 * (size_t)D);
-    if (int rc = measure_device(ctx, gpu, hip_stream, 2 * (size_t)D, kGeomedParts, "geomed: fused pass", res.data(),
-                                [&](const DeviceCall& c, double* d_part, double* d_out) {
-                                    return geomed_pass_on(c.tu, d_clients, h_weights, D, n, in, d_v, d_part, d_out, c.s);
-                                }))
-        return rc;
-    std::copy(res.begin(), res.begin() + D, h_sumsq);
-    std::copy(res.begin() + D, res.end(), h_nonfinite);
-    return FA_OK;
-}
-
-int fa_set_bulyan(fa_ctx* ctx, int part_id, int f) {
-    g_err.clear();
-    if (f < -1) return fail(FA_ERR_ARG, "bulyan: f = %d (f >= 0; -1 removes the stage)", f);
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    if (f >= 0 && (ctx->flags & FA_SHARD_CLIENT_RS))
-        return fail(FA_ERR_ARG, "bulyan: not on an FA_SHARD_CLIENT_RS context (the rule needs every client on one GPU; "
-                                "use FA_SHARD_RANGE)");
-    if (part_id < 0) {
-        ctx->bulyan_f = f;
-        return FA_OK;
-    }
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (f < 0) {  // the stage and its report go
-        if (p->bulyan_f >= 0) p->ready = false;
-        p->bulyan_f = -1;
-        p->bulyan_reported = false;
-        p->bulyan_q.clear();
-        p->bulyan_s.clear();
-        p->bulyan_order.clear();
-        p->bulyan_sel.clear();
-        return FA_OK;
-    }
-    if (p->mode != FA_TRIMMED)
-        return fail(FA_ERR_ARG, "bulyan: part %d is an %s part (the stage replaces the window of an FA_TRIMMED part)", part_id,
-                    p->mode == FA_LITERAL ? "FA_LITERAL" : "FA_FEDAVG");
-    if ((rc = check_bulyan(p->D, f))) return rc;
-    if (p->bulyan_f < 0) p->bulyan_reported = false;
-    p->bulyan_f = f;
-    p->ready = false;
-    return FA_OK;
-}
-
-int fa_bulyan_get_round(fa_ctx* ctx, int part_id, double* dist, int* order, double* pick_scores, int* selected,
-                        int* n_selected) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (p->bulyan_f < 0) return fail(FA_ERR_STATE, "part %d has no Bulyan stage", part_id);
-    if (!p->bulyan_reported) return fail(FA_ERR_STATE, "part %d: no round reduced with the Bulyan stage yet", part_id);
-    const size_t D = (size_t)p->D;
-    if (dist) std::copy(p->bulyan_q.begin(), p->bulyan_q.end(), dist);
-    for (size_t k = 0; k < D; ++k) {
-        if (order) order[k] = p->bulyan_order[k];
-        if (pick_scores) pick_scores[k] = p->bulyan_s[k];
-        if (selected) selected[k] = p->bulyan_sel[k];
-    }
-    if (n_selected) *n_selected = p->bulyan_n;
-    return FA_OK;
-}
-
-int fa_bulyan_select(const double* dist, int D, int f, int* order, double* pick_scores, int* selected, int* n_selected) {
-    g_err.clear();
-    if (!dist) return fail(FA_ERR_ARG, "bulyan: dist is null");
-    if (D < 1) return fail(FA_ERR_ARG, "bulyan: D must be >= 1");
-    if (int rc = check_bulyan(D, f)) return rc;
-    bulyan_select(dist, D, f, order, pick_scores, selected, n_selected);
-    return FA_OK;
-}
-
-int fa_centered_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, void* d_out,
-                       fa_dtype out, int keep, void* hip_stream) {
-    g_err.clear();
-    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
-    if (D < 1 || D > FA_TRIMMED_MAX_CLIENTS)
-        return fail(FA_ERR_ARG, "D = %d: a centred mean takes 1..%d clients", D, FA_TRIMMED_MAX_CLIENTS);
-    if (keep < 1 || keep > D) return fail(FA_ERR_ARG, "keep %d does not fit D = %d clients (1 <= keep <= D)", keep, D);
-    if (!dvalid(in) || !dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
-    FA_PAIR(in, out);
-    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    if (n == 0) return FA_OK;
-    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
-    if (!d_out) return fail(FA_ERR_ARG, "output pointer is null");
-    if (!aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
-    const DeviceCall c = device_call(ctx, gpu, hip_stream);
-    DeviceGuard dg(c.dev);
-    return centered_on(c.tu, d_clients, D, n, in, d_out, out, keep, c.s);
-}
-
-int fa_set_noise(fa_ctx* ctx, int part_id, float stddev, uint64_t seed) {
-    g_err.clear();
-    if (!finite_f(stddev) || stddev < 0.0f) return fail(FA_ERR_ARG, "noise: stddev %g must be finite and >= 0", (double)stddev);
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    if (stddev > 0.0f && (ctx->flags & FA_SHARD_CLIENT_RS))
-        return fail(FA_ERR_ARG, "noise: not on an FA_SHARD_CLIENT_RS context (its aggregate is not bit-specified; use "
-                                "FA_SHARD_RANGE)");
-    if (part_id < 0) {
-        ctx->noise = stddev;
-        ctx->noise_seed = stddev > 0.0f ? seed : 0;
-        return FA_OK;
-    }
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (stddev > 0.0f && p->mode == FA_LITERAL) return fail(FA_ERR_ARG, "noise: part %d is an FA_LITERAL part", part_id);
-    return set_part_noise(ctx, *p, stddev, seed);
-}
-
-int fa_get_noise(fa_ctx* ctx, int part_id, float* stddev, uint64_t* seed) {
-    g_err.clear();
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    float sd = ctx->noise;
-    uint64_t sv = ctx->noise_seed;
-    if (part_id >= 0) {
-        Part* p;
-        int rc = check_part(ctx, part_id, &p);
-        if (rc) return rc;
-        sd = p->noise;
-        sv = p->noise_seed;
-    }
-    if (stddev) *stddev = sd;
-    if (seed) *seed = sv;
-    return FA_OK;
-}
-
-int fa_noise_get_round(fa_ctx* ctx, int part_id, uint64_t* round) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (!(p->noise > 0.0f)) return fail(FA_ERR_STATE, "part %d has no noise stage", part_id);
-    if (!round) return fail(FA_ERR_ARG, "round is null");
-    *round = p->noise_round;
-    return FA_OK;
-}
-
-int fa_noise_set_round(fa_ctx* ctx, int part_id, uint64_t round) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (!(p->noise > 0.0f)) return fail(FA_ERR_STATE, "part %d has no noise stage", part_id);
-    if (round > kNoiseRounds) return fail(FA_ERR_ARG, "noise: round %llu beyond 2^32", (unsigned long long)round);
-    p->noise_round = round;
-    return FA_OK;
-}
-
-int fa_noise_device(fa_ctx* ctx, int gpu, const float* d_avg, size_t n, void* d_out, fa_dtype out, float stddev,
-                    uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, void* hip_stream) {
-    g_err.clear();
-    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
-    if (!finite_f(stddev) || !(stddev > 0.0f)) return fail(FA_ERR_ARG, "noise: stddev %g must be finite and > 0", (double)stddev);
-    if (!dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
-    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "noise: idx0 + n beyond 2^64");
-    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    if (n == 0) return FA_OK;
-    if (!d_avg || !d_out) return fail(FA_ERR_ARG, "noise: %s pointer is null", !d_avg ? "d_avg" : "d_out");
-    if (!aligned(d_avg, 4)) return fail(FA_ERR_ALIGN, "noise: aggregate not 4-byte aligned");
-    if (!aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
-    const DeviceCall c = device_call(ctx, gpu, hip_stream);
-    DeviceGuard dg(c.dev);
-    return noise_on(c.tu, d_avg, d_out, out, stddev, seed, stream, round, idx0, n, c.s);
-}
-
-int fa_noise_host(uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, size_t n, float* z) {
-    g_err.clear();
-    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "noise: idx0 + n beyond 2^64");
-    if (n == 0) return FA_OK;
-    if (!z) return fail(FA_ERR_ARG, "noise: z is null");
-    fa::noise_host(seed, stream, round, idx0, n, z);
-    return FA_OK;
-}
-
-size_t fa_mx8_scale_bytes(size_t n) { return n / FA_MX8_BLOCK + (n % FA_MX8_BLOCK ? 1 : 0); }
-
-int fa_mx8_encode(const float* delta, size_t n, int8_t* q, uint8_t* e) {
-    g_err.clear();
-    if (n == 0) return FA_OK;
-    if (!delta || !q || !e) return fail(FA_ERR_ARG, "mx8: %s is null", !delta ? "delta" : !q ? "q" : "e");
-    fa::mx8_encode_host(delta, n, q, e);
-    return FA_OK;
-}
-
-int fa_mx8_decode(const int8_t* q, const uint8_t* e, size_t n, uint64_t idx0, float* d) {
-    g_err.clear();
-    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "mx8: idx0 + n beyond 2^64");
-    if (n == 0) return FA_OK;
-    if (!q || !e || !d) return fail(FA_ERR_ARG, "mx8: %s is null", !q ? "q" : !e ? "e" : "d");
-    fa::mx8_decode_host(q, e, n, idx0, d);
-    return FA_OK;
-}
-
-int fa_mx8_expand_device(fa_ctx* ctx, int gpu, const int8_t* d_q, const uint8_t* d_e, size_t n, uint64_t idx0,
-                         const void* d_ref, fa_dtype ref_dtype, void* d_dst, fa_dtype dst_dtype, void* hip_stream) {
-    g_err.clear();
-    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
-    if (!dvalid(dst_dtype) || !dvalid(ref_dtype)) return fail(FA_ERR_ARG, "bad dtype");
-    if (!fa::dtype_pair_ok(dst_dtype, ref_dtype))
-        return fail(FA_ERR_ARG, "mx8: no %s slot against a %s reference (a 16-bit slot takes its own type or f32)",
-                    fa::dtype_name(dst_dtype), fa::dtype_name(ref_dtype));
-    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "mx8: idx0 + n beyond 2^64");
-    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    if (n == 0) return FA_OK;
-    if (!d_q || !d_e || !d_dst) return fail(FA_ERR_ARG, "mx8: %s pointer is null", !d_q ? "d_q" : !d_e ? "d_e" : "d_dst");
-    if (d_ref && !aligned(d_ref, dsize(ref_dtype)))
-        return fail(FA_ERR_ALIGN, "mx8: reference not %zu-byte aligned", dsize(ref_dtype));
-    if (!aligned(d_dst, dsize(dst_dtype))) return fail(FA_ERR_ALIGN, "mx8: slot not %zu-byte aligned", dsize(dst_dtype));
-    const DeviceCall c = device_call(ctx, gpu, hip_stream);
-    DeviceGuard dg(c.dev);
-    FA_HIP(fa::launch_mx8_expand(d_q, d_e, idx0, (int64_t)n, d_ref, ref_dtype, d_dst, dst_dtype, c.s));
-    return FA_OK;
-}
-
-int fa_set_mx8(fa_ctx* ctx, int part_id, int on) {
-    g_err.clear();
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    if (on && (ctx->flags & FA_SHARD_CLIENT_RS))
-        return fail(FA_ERR_ARG, "mx8: not on an FA_SHARD_CLIENT_RS context (a GPU holding a whole slot does not hold "
-                                "the matching output; use FA_SHARD_RANGE)");
-    if (part_id < 0) {
-        ctx->mx8 = on != 0;
-        return FA_OK;
-    }
-    Part* p;
-    if (int rc = check_part(ctx, part_id, &p)) return rc;
-    if (on && p->mode == FA_LITERAL) return fail(FA_ERR_ARG, "mx8: part %d is an FA_LITERAL part", part_id);
-    if (!on) {
-        if (p->mx8)  // the shadows may still be in use
-            if (int rc = opt_quiesce(ctx)) return rc;
-        free_mx8(ctx, *p);
-        return FA_OK;
-    }
-    if (p->mx8) return FA_OK;
-    // what this round kept host-side or chained so far goes back to the plain path
-    if (int rc = host_flush(ctx, *p)) return rc;
-    restart_round_plain(*p);
-    p->mx8 = true;
-    p->mx8_ref = false;
-    return FA_OK;
-}
-
-int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags) {
-    g_err.clear();
-    return submit_mx8_impl(ctx, part_id, client_slot, q, e, weight, flags);
-}
-
-int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
-    g_err.clear();
-    Part* p;
-    if (int rc = check_part(ctx, part_id, &p)) return rc;
-    if (!p->mx8 && !p->reply)
-        return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
-                                  "(fa_set_mx8_reply)", part_id);
-    if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
-    if (int rc = opt_quiesce(ctx)) return rc;  // the part's pending work, on whatever stream
-    if (p->reply)
-        if (int rc = ensure_reply_buf(ctx, *p)) return rc;
-    const size_t so = dsize(p->out);
-    for (int g = 0; g < ctx->G; ++g) {
-        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
-        if (!p->cnt[(size_t)g]) continue;
-        const char* src = static_cast<const char*>(host_src) + p->off[(size_t)g] * so;
-        FA_HIP(hipMemcpy(p->dout[(size_t)g], src, p->cnt[(size_t)g] * so, hipMemcpyHostToDevice));
-        if (p->reply)  // the owners hold it: the next reply is taken against it
-            FA_HIP(hipMemcpy(p->reply_sent[(size_t)g], src, p->cnt[(size_t)g] * so, hipMemcpyHostToDevice));
-    }
-    if (p->reply) p->reply_has_sent = true;
-    set_range_runs(*p, ctx->G);  // as a round's output: the reference, and what fa_copy_output hands out
-    return FA_OK;
-}
-
-int fa_mx8_encode_device(fa_ctx* ctx, int gpu, const void* d_new, fa_dtype new_dtype, const void* d_sent,
-                         fa_dtype sent_dtype, size_t n, uint64_t idx0, int8_t* d_q, uint8_t* d_e, void* d_out, int flags,
-                         void* hip_stream) {
-    g_err.clear();
-    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
-    if (!dvalid(new_dtype) || !dvalid(sent_dtype)) return fail(FA_ERR_ARG, "bad dtype");
-    if (new_dtype != sent_dtype)
-        return fail(FA_ERR_ARG, "mx8 reply: the new model is %s, the sent one %s: one dtype", fa::dtype_name(new_dtype),
-                    fa::dtype_name(sent_dtype));
-    if (flags & ~(FA_MX8_SCALES_ONLY | FA_MX8_SCALES_GIVEN)) return fail(FA_ERR_ARG, "mx8 reply: unknown flags 0x%x", flags);
-    if ((flags & FA_MX8_SCALES_ONLY) && (flags & FA_MX8_SCALES_GIVEN))
-        return fail(FA_ERR_ARG, "mx8 reply: FA_MX8_SCALES_ONLY and FA_MX8_SCALES_GIVEN exclude each other");
-    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "mx8 reply: idx0 + n beyond 2^64");
-    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
-    if (n == 0) return FA_OK;
-    const bool only = (flags & FA_MX8_SCALES_ONLY) != 0;
-    if (!d_new || !d_sent || !d_e || (!only && !d_q))
-        return fail(FA_ERR_ARG, "mx8 reply: %s pointer is null", !d_new ? "d_new" : !d_sent ? "d_sent" : !d_e ? "d_e" : "d_q");
-    const size_t es = dsize(new_dtype);
-    if (!aligned(d_new, es) || !aligned(d_sent, es) || (!only && d_out && !aligned(d_out, es)))
-        return fail(FA_ERR_ALIGN, "mx8 reply: %s not %zu-byte aligned", !aligned(d_new, es) ? "d_new" : !aligned(d_sent, es) ? "d_sent" : "d_out", es);
-    if (!only && d_out) {  // the same address as an input, or apart from it
-        const uintptr_t o = (uintptr_t)d_out, bytes = (uintptr_t)(n * es);
-        for (const void* in : {d_new, d_sent}) {
-            const uintptr_t a = (uintptr_t)in;
-            if (o != a && o < a + bytes && a < o + bytes)
-                return fail(FA_ERR_ARG, "mx8 reply: d_out overlaps %s without being it", in == d_new ? "d_new" : "d_sent");
-        }
-    }
-    const DeviceCall c = device_call(ctx, gpu, hip_stream);
-    DeviceGuard dg(c.dev);
-    const int mode = only ? fa::kMx8EncScalesOnly : (flags & FA_MX8_SCALES_GIVEN) ? fa::kMx8EncScalesGiven : fa::kMx8EncFused;
-    FA_HIP(fa::launch_mx8_encode(d_new, d_sent, new_dtype, idx0, (int64_t)n, d_q, d_e, only ? nullptr : d_out, nullptr, mode,
-                                 c.s));
-    return FA_OK;
-}
-
-int fa_set_mx8_reply(fa_ctx* ctx, int part_id, int on) {
-    g_err.clear();
-    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
-    if (on && (ctx->flags & FA_SHARD_CLIENT_RS))
-        return fail(FA_ERR_ARG, "mx8 reply: not on an FA_SHARD_CLIENT_RS context (use FA_SHARD_RANGE)");
-    if (part_id < 0) {
-        ctx->mx8_reply = on != 0;
-        return FA_OK;
-    }
-    Part* p;
-    if (int rc = check_part(ctx, part_id, &p)) return rc;
-    if (on && p->mode == FA_LITERAL) return fail(FA_ERR_ARG, "mx8 reply: part %d is an FA_LITERAL part", part_id);
-    if (!on) {
-        if (p->reply)  // the buffers may still be in use
-            if (int rc = opt_quiesce(ctx)) return rc;
-        free_reply(ctx, *p);
-        return FA_OK;
-    }
-    if (p->reply) return FA_OK;
-    // what this round kept host-side or chained so far goes back to the plain path
-    if (int rc = host_flush(ctx, *p)) return rc;
-    restart_round_plain(*p);
-    p->reply = true;
-    return FA_OK;
-}
-
-namespace {
-
-// D2H of the codes of the part's last reducing call, ordered after it as copy_output is; counts the E = 255 blocks
-// on the way.  A block's scale byte lies in one GPU's range (reply_stage), so the copies do not overlap.
-int copy_mx8_codes(fa_ctx* ctx, Part& p, int8_t* q, uint8_t* e) {
-    const int G = ctx->G;
-    for (int g = 0; g < G; ++g) {
-        GpuRes& r = ctx->gpu[(size_t)g];
-        const size_t cnt = p.cnt[(size_t)g], off = p.off[(size_t)g];
-        if (!cnt) continue;
-        DeviceGuard dg(r.dev);
-        hipStream_t ds = p.done_stream[(size_t)g];
-        if (ds && ds != r.compute) {
-            FA_HIP(hipEventRecord(p.done[(size_t)g], ds));
-            FA_HIP(hipStreamWaitEvent(r.compute, p.done[(size_t)g], 0));
-        }
-        const char* src = p.reply_codes[(size_t)g];
-        if (q) FA_HIP(hipMemcpyAsync(q + off, src, cnt, hipMemcpyDeviceToHost, r.compute));
-        FA_HIP(hipMemcpyAsync(e + (off >> 5), src + p.reply_eoff[(size_t)g], ((off + cnt - 1) >> 5) - (off >> 5) + 1,
-                              hipMemcpyDeviceToHost, r.compute));
-    }
-    for (int g = 0; g < G; ++g) {
-        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
-        FA_HIP(hipStreamSynchronize(ctx->gpu[(size_t)g].compute));
-    }
-    uint64_t nan = 0;
-    for (size_t b = 0, B = fa_mx8_scale_bytes(p.n); b < B; ++b) nan += e[b] == 255;
-    p.reply_nan = nan;
-    p.reply_counted = true;
-    return FA_OK;
-}
-
-int check_mx8_dst(const Part& p, const void* q, const void* e, int flags) {
-    if (flags & ~FA_HOST_PINNED) return fail(FA_ERR_ARG, "unknown flags 0x%x", flags);
-    if (p.n && (!q || !e)) return fail(FA_ERR_ARG, "mx8 reply: %s is null", !q ? "q" : "e");
-    return FA_OK;
-}
-
-}  // namespace
-
-int fa_finalize_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags) {
-    g_err.clear();
-    Trace tr("fa_finalize_mx8 part %d", part_id);
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc || (rc = check_mx8_dst(*p, q, e, flags))) return rc;
-    // the round as it stands decides, before any work: reduced already, it has codes or not; else it will have
-    // them if the owners hold a model
-    if (!p->reply || (p->ready ? !p->reply_has_codes : !p->reply_has_sent))
-        return fail(FA_ERR_STATE, "mx8 reply: part %d has %s: finish the round with fa_finalize", part_id,
-                    !p->reply ? "no reply stage (fa_set_mx8_reply)" : "no sent model yet (the bootstrap round)");
-    if (p->n_submitted != p->D)
-        return fail(FA_ERR_STATE, "part %d: %d of %d clients submitted", part_id, p->n_submitted, p->D);
-    if (!p->ready && (rc = reduce_part(ctx, *p, p->w.data(), nullptr))) return rc;
-    if (p->n && (rc = copy_mx8_codes(ctx, *p, q, e))) return rc;
-    reset_round(*p);
-    return FA_OK;
-}
-
-int fa_copy_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc || (rc = check_mx8_dst(*p, q, e, flags))) return rc;
-    if (!p->reply || !p->reply_has_codes)
-        return fail(FA_ERR_STATE, "mx8 reply: part %d has no codes (%s)", part_id,
-                    !p->reply ? "no reply stage" : "no reducing call yet, or the last one was the bootstrap");
-    return p->n ? copy_mx8_codes(ctx, *p, q, e) : FA_OK;
-}
-
-int fa_mx8_reply_stats(fa_ctx* ctx, int part_id, uint64_t* nan_blocks) {
-    g_err.clear();
-    Part* p;
-    int rc = check_part(ctx, part_id, &p);
-    if (rc) return rc;
-    if (!p->reply) return fail(FA_ERR_STATE, "mx8 reply: part %d has no reply stage (fa_set_mx8_reply)", part_id);
-    if (!p->reply_counted && p->n) {  // nobody fetched the codes yet: the scale bytes alone
-        std::vector<uint8_t> e(fa_mx8_scale_bytes(p->n));
-        if ((rc = copy_mx8_codes(ctx, *p, nullptr, e.data()))) return rc;
-    }
-    if (nan_blocks) *nan_blocks = p->reply_nan;
     return FA_OK;
 }
 

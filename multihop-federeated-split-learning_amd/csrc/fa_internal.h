@@ -117,7 +117,7 @@ hipError_t launch_server_opt(int rule, const OptHyper& h, const float* avg, floa
 // clients writes one fp64 partial per (client, workgroup) into `partials` (room for nc * kClipMaxPartials
 // doubles; a client's are the np of measure_grid, fa_split.h, stored np apart), a second one adds each client's
 // partials in a fixed order.  No atomics.  sp: the Split (fa_split.h) led by the first client, ref required as
-// well.  The caller's scratch holds results and partials of either pass (MeasureScratch, fa_api.hip).
+// well.  The caller's scratch holds results and partials of either pass (MeasureScratch, fa_host.h).
 constexpr int64_t kClipMaxBlocks = 2048;  // 8 workgroups per CU on 256 CUs; tiles beyond it are strided
 constexpr int64_t kClipMaxPartials = kClipMaxBlocks + 1;  // per client: the grid's, plus one for head and tail
 hipError_t launch_clip_sumsq(const ClientTable& t, int nc, fa_dtype in, const float* ref, const Split& sp,

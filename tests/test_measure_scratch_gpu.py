@@ -1,5 +1,5 @@
 """GPU: the clip stage's norm pass and the Krum stage's distance pass share one scratch per GPU of a context
-(MeasureScratch in csrc/fa_api.hip).  One context holds a clip part (D = 8) and two Krum parts (D = 33, f = 10 and
+(MeasureScratch in csrc/fa_host.h).  One context holds a clip part (D = 8) and two Krum parts (D = 33, f = 10 and
 D = 5, f = 1), reduced together round after round, so the scratch grows from the clip stage's layout (8 sums) to a
 Krum one (33 x 33 matrix, 528 pairs of partials) and then serves a smaller one (5 x 5), and the raw entries run
 on it afterwards.  Every output and every report must be bit-equal to the same part alone on a context of its
