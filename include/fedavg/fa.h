@@ -339,6 +339,42 @@
  *                 refuses a range that starts inside a block (FA_ERR_STATE).
  *              Added without a new FA_ABI_VERSION: fa_mx8_encode_device with n == 0 touches no device and answers
  *              FA_OK -- that is how a caller probes for it.
+ *   Secagg stage (fa_set_secagg, fa_secagg_set_terms, fa_secagg_unmask_device, fa_secagg_mask_host,
+ *              fa_secagg_quantize): the server's arithmetic of secure aggregation (Bonawitz et al., "Practical Secure
+ *              Aggregation for Privacy-Preserving Machine Learning", CCS 2017).  The slots of an FA_FEDAVG part with
+ *              `in` FA_F32 hold uint32 words: an owner's fixed-point update plus its masks modulo 2^32.  A reducing
+ *              call sums them, removes the masks the caller names and decodes the sum.  The library knows nothing of
+ *              the protocol around it (key agreement, secret sharing, who dropped out).
+ *              1. Terms.  A round has T terms, 0 <= T <= FA_SECAGG_MAX_TERMS.  A term is a key of 8 uint32 words, a
+ *                 nonce of 3 words and a sign, +1 or -1.  The caller decides which masks to cancel and with which
+ *                 sign.
+ *              2. Mask word.  Element i is the element's index in the whole bucket, never the index within a shard or
+ *                 a piece.  Its mask under a term is word i & 15 of the ChaCha20 block (RFC 8439 2.3: constants, key,
+ *                 counter, nonce; 20 rounds; the final addition) with that key and nonce and block counter i >> 4 as
+ *                 a uint32.  The word is taken as the state holds it after the final addition: no byte
+ *                 serialisation is involved.  idx0 + n <= 2^36 everywhere; more is FA_ERR_ARG.  Known answer: key
+ *                 bytes 00 01 .. 1f (words 03020100 07060504 .. 1f1e1d1c), nonce words 09000000 4a000000 00000000,
+ *                 counter 1: e4e7f110 15593bd1 1fdd0f50 c47120a3 c7f4d1c7 0368c033 9aaa2204 4e6cd4c3 466482d2 09aa9f07
+ *                 05d7c214 a2028bd9 d19c12b5 b94e16de e883d0cb 4e3c50a2 -- as bytes 10 f1 e7 e4 d1 3b 59 15 .., the key
+ *                 stream of RFC 8439 2.3.2.
+ *              3. Sum.  u_i = sum_k y_{k,i} + sum_t sign_t m_{t,i} modulo 2^32, over the clients the part's plain
+ *                 round would reduce.  The order is free: the arithmetic is exact.  Weights are ignored, as for
+ *                 FA_TRIMMED: owners put their weight into what they encode.
+ *              4. Decode.  a_i = fl32((float)(int32_t)u_i * scale): one conversion to nearest-even and one IEEE fp32
+ *                 multiply.  scale is fp32, finite and > 0.
+ *              5. Place in the round.  a stands exactly where the chain's result stands: it feeds the noise stage
+ *                 and the server optimizer if the part has them, otherwise it is rounded once to the out dtype; MX8
+ *                 replies, range shards and range pieces work as for any part.
+ *              6. Admission.  The stage belongs to the measure-then-select family: it does not compose with the clip,
+ *                 Krum or geomed stage, which need plaintext.  Not with MX8 receipts, not on an FA_SHARD_CLIENT_RS
+ *                 context, not as a context default.  Like the other stage parts the part is never kept host-side,
+ *                 FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager, and a reducing call needs every client submitted.
+ *                 Terms are per round: a reducing call without fa_secagg_set_terms since the last one fails with
+ *                 FA_ERR_STATE, so a stale list is never applied; T = 0 is set explicitly.
+ *              Owner's side: fa_secagg_quantize makes the fixed-point codes, fa_secagg_mask_host the mask words; both
+ *              are pure host arithmetic.  No cryptographic review of the construction is claimed here.  Added without
+ *              a new FA_ABI_VERSION: fa_secagg_unmask_device with n == 0 touches no device and answers FA_OK -- that
+ *              is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -884,6 +920,40 @@ int fa_finalize_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags);
 int fa_copy_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags);
 /* *nan_blocks = the E = 255 blocks among the codes of the part's last reducing call (0 after a bootstrap). */
 int fa_mx8_reply_stats(fa_ctx* ctx, int part_id, uint64_t* nan_blocks);
+
+/* Secagg stage (the header comment, "Secagg stage"): masked uint32 sums unmasked and decoded on the GPU. */
+#define FA_SECAGG_MAX_TERMS 4096
+/* Gives a part the stage with the decoding scale (part_id >= 0; again: only the scale changes); scale <= 0 removes it
+ * with its term table.  FA_ERR_ARG, naming the cause: scale NaN or +inf, part_id < 0 (no context default), a part
+ * whose mode is not FA_FEDAVG or whose `in` is not FA_F32, a part of more than 2^36 elements, a part with a clip,
+ * Krum, geomed or MX8 stage (those setters refuse a secagg part in turn), an FA_SHARD_CLIENT_RS context. */
+int fa_set_secagg(fa_ctx* ctx, int part_id, float scale);
+/* The terms of the part's next reducing call: keys (8 T words), nonces (3 T words), signs (T ints, each +1 or -1), all
+ * host arrays, copied before the return; NULL allowed with T == 0.  FA_ERR_ARG: T outside 0 .. FA_SECAGG_MAX_TERMS, a
+ * null array, another sign.  FA_ERR_STATE on a part without the stage.  A reducing call uses the terms and drops
+ * them. */
+int fa_secagg_set_terms(fa_ctx* ctx, int part_id, int T, const uint32_t* keys, const uint32_t* nonces, const int* signs);
+/* Rules 2-4 on raw device pointers: d_out[i] (n of `out`, one rounding) = the decoded sum of the D buckets d_clients
+ * (n uint32 words each, bucket elements idx0 .. idx0 + n - 1) and the T terms, on device `gpu`.  ctx may be NULL (then
+ * `gpu` is the HIP device; D > 128 with a 16-bit output needs one, for scratch).  Every argument is checked before any
+ * device call: D >= 1, the out dtype, scale (finite, > 0), the terms as above, idx0 + n <= 2^36, and for n > 0 null
+ * pointers and element alignment (FA_ERR_ALIGN); with n == 0 and valid arguments it returns FA_OK without touching a
+ * device.  Otherwise it uploads the terms, enqueues on hip_stream (NULL = the ctx's compute stream of `gpu`, or the
+ * null stream) and waits for it.  Any element phase of the pointers is correct; 16-byte loads are used where every
+ * pointer is 16-byte aligned at the first multiple of 16 of the bucket index. */
+int fa_secagg_unmask_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, uint64_t idx0, int T,
+                            const uint32_t* keys, const uint32_t* nonces, const int* signs, float scale, void* d_out,
+                            fa_dtype out, void* hip_stream);
+/* Rule 2, pure host arithmetic, usable without a device: out[0, n) = the mask words of bucket elements idx0 .. idx0 +
+ * n - 1 under key (8 words) and nonce (3 words) -- the owner's side, and the bits the kernel removes. */
+int fa_secagg_mask_host(const uint32_t* key, const uint32_t* nonce, uint64_t idx0, size_t n, uint32_t* out);
+/* The owner's fixed-point codes, pure host arithmetic: out[i] = rint((double)v[i] * (double)q), ties to even,
+ * saturated at +-(2^31 - 1); a NaN gives 0 and is counted in *n_bad (nullable).  q finite and > 0; the server decodes
+ * with scale = 1 / q. */
+int fa_secagg_quantize(const float* v, size_t n, float q, int32_t* out, uint64_t* n_bad);
+/* Which vector form a launch over n elements and T terms takes: 0 = a tile per wave, 1 = the term split (the four
+ * waves of a workgroup share a tile's terms).  Pure host arithmetic; the bits do not depend on it. */
+int fa_secagg_form(size_t n, int T);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

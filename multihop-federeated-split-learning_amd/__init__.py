@@ -130,6 +130,13 @@ def lib():
         "fa_finalize_mx8": (I, [P, I, P, P, I]),
         "fa_copy_mx8": (I, [P, I, P, P, I]),
         "fa_mx8_reply_stats": (I, [P, I, P]),
+        "fa_set_secagg": (I, [P, I, F]),
+        "fa_secagg_set_terms": (I, [P, I, I, P, P, P]),
+        "fa_secagg_unmask_device": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, P]),
+        "fa_secagg_mask_host": (I, [P, P, U64, S, P]),
+        "fa_secagg_quantize": (I, [P, S, F, P, ctypes.POINTER(U64)]),
+        "fa_secagg_form": (I, [S, I]),
+        "fa_diag_secagg_unmask": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, I, P]),  # diagnostic (outside fa.h)
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
         "fa_submit_gather": (I, [P, I, I, I, P, P, F]),
@@ -470,6 +477,62 @@ def mx8_encode_device(new, sent, n, q, e, out=None, dtype=F32, sent_dtype=None, 
     check(lib().fa_mx8_encode_device(ctx.handle if ctx is not None else None, gpu, _addr(new), dtype, _addr(sent),
                                      dtype if sent_dtype is None else sent_dtype, n, int(idx0), _addr(q), _addr(e),
                                      _addr(out), flags, _stream(stream)))
+
+
+SECAGG_MAX_TERMS = 4096  # FA_SECAGG_MAX_TERMS
+SECAGG_TILE, SECAGG_SPLIT = 0, 1  # secagg_form
+
+
+def _secagg_terms(keys, nonces, signs):
+    """(T, keys uint32[T, 8], nonces uint32[T, 3], signs intc[T]) as contiguous arrays."""
+    keys = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(-1, 8))
+    nonces = np.ascontiguousarray(np.asarray(nonces, np.uint32).reshape(-1, 3))
+    signs = np.ascontiguousarray(np.asarray(signs, np.intc).reshape(-1))
+    if not keys.shape[0] == nonces.shape[0] == signs.size:
+        raise ValueError("need one key, one nonce and one sign per term")
+    return signs.size, keys, nonces, signs
+
+
+def secagg_unmask_device(clients, n, out, out_dtype=F32, keys=(), nonces=(), signs=(), scale=1.0, idx0=0, form=None,
+                         stream=None, gpu=0, ctx=None):
+    """fa_secagg_unmask_device (fa.h "Secagg stage", rules 2-4): out[i] = (int32)(the sum modulo 2^32 of the D
+    device-resident uint32 buckets and the signed ChaCha20 words of the terms at bucket element idx0 + i) * scale, in
+    out_dtype.  Enqueued on `stream` and waited for.  form: None, or SECAGG_TILE / SECAGG_SPLIT to force a vector form
+    (the diagnostic entry; the same bits).  With n == 0 no device is touched: the feature probe."""
+    D = len(clients)
+    arr = (ctypes.c_void_p * max(1, D))(*[_addr(c) for c in clients])
+    T, keys, nonces, signs = _secagg_terms(keys, nonces, signs)
+    args = [ctx.handle if ctx is not None else None, gpu, arr, D, n, int(idx0), T, keys.ctypes.data, nonces.ctypes.data,
+            signs.ctypes.data, float(scale), _addr(out), out_dtype]
+    if form is None:
+        check(lib().fa_secagg_unmask_device(*args, _stream(stream)))
+    else:
+        check(lib().fa_diag_secagg_unmask(*args, int(form), _stream(stream)))
+
+
+def secagg_mask_host(key, nonce, idx0, n):
+    """fa_secagg_mask_host (host arithmetic): the n mask words (np.uint32) of bucket elements idx0 .. idx0 + n - 1 under
+    key (8 words) and nonce (3 words): the owner's side, and the bits the kernel removes."""
+    key = np.ascontiguousarray(np.asarray(key, np.uint32).reshape(8))
+    nonce = np.ascontiguousarray(np.asarray(nonce, np.uint32).reshape(3))
+    out = np.empty(n, np.uint32)
+    check(lib().fa_secagg_mask_host(key.ctypes.data, nonce.ctypes.data, int(idx0), n, out.ctypes.data))
+    return out
+
+
+def secagg_quantize(v, q):
+    """fa_secagg_quantize (host arithmetic, the owner's side): (codes int32[n], n_bad) -- rint(v * q) in fp64, ties to
+    even, saturated at +-(2^31 - 1); a NaN gives 0 and is counted."""
+    v = np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1))
+    out, bad = np.empty(v.size, np.int32), ctypes.c_uint64()
+    check(lib().fa_secagg_quantize(v.ctypes.data, v.size, float(q), out.ctypes.data, ctypes.byref(bad)))
+    return out, bad.value
+
+
+def secagg_form(n, T):
+    """fa_secagg_form (host arithmetic): SECAGG_TILE or SECAGG_SPLIT, the vector form a launch over n elements and T
+    terms takes."""
+    return lib().fa_secagg_form(n, int(T))
 
 
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
@@ -826,6 +889,18 @@ class Aggregator:
     def set_noise_round(self, part_id, r):
         """fa_noise_set_round: replay a round, or continue a sequence after a restart."""
         check(lib().fa_noise_set_round(self.handle, part_id, int(r)))
+
+    def set_secagg(self, scale, part_id):
+        """fa_set_secagg: the part's slots hold masked uint32 words (submit them as 4-byte elements: a uint32 array, or
+        its float32 view); a reducing call sums them modulo 2^32, removes the round's terms and decodes with `scale`.
+        scale <= 0 removes the stage."""
+        check(lib().fa_set_secagg(self.handle, part_id, float(scale)))
+
+    def secagg_terms(self, part_id, keys, nonces, signs):
+        """fa_secagg_set_terms: the terms of the part's next reducing call -- keys uint32[T, 8], nonces uint32[T, 3],
+        signs (+1 / -1)[T]; T = 0 (three empty sequences) is set explicitly."""
+        T, keys, nonces, signs = _secagg_terms(keys, nonces, signs)
+        check(lib().fa_secagg_set_terms(self.handle, part_id, T, keys.ctypes.data, nonces.ctypes.data, signs.ctypes.data))
 
     def submit(self, part_id, slot, host, weight=1.0, pinned=False):
         host = np.ascontiguousarray(host)

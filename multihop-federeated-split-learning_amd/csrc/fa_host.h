@@ -273,7 +273,8 @@ struct DevArrays {
 //   krum geomed      restart_round_plain                  the round stays    the round stays (`ready` too)
 //   bulyan           ready = false                        ready = false      ready = false, if it was on
 //   mx8 reply        host_flush, restart_round_plain      nothing            the round stays
-enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kStages };
+//   secagg           restart_round_plain, no terms        the round stays    the round stays, the terms go
+enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kStages };
 
 struct OptCfg : fa_server_opt {  // fa.h "Server optimizer"
     OptCfg(const fa_server_opt& o = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f}) : fa_server_opt(o) {}
@@ -305,6 +306,10 @@ struct FlagCfg {  // fa.h "MX8 receipts", "MX8 replies"
     bool flag = false;
     bool on() const { return flag; }
 };
+struct SecaggCfg {  // fa.h "Secagg stage"
+    float scale = 0.0f;
+    bool on() const { return scale > 0.0f; }
+};
 struct StageCfgs {
     OptCfg opt;
     ClipCfg clip;
@@ -313,6 +318,7 @@ struct StageCfgs {
     BulyanCfg bulyan;
     NoiseCfg noise;
     FlagCfg mx8, reply;
+    SecaggCfg secagg;
 };
 
 // Per GPU the fp32 state over its cnt elements (v only for the adaptive rules).
@@ -391,11 +397,23 @@ struct ReplyStage {
     uint64_t nan = 0;
     bool on() const { return cfg.on(); }
 };
+// tab: the round's term table as secagg_table packs it (fa_internal.h), kept until the next fa_secagg_set_terms; dev:
+// per GPU its device copy, room for FA_SECAGG_MAX_TERMS terms, uploaded by each reducing call.  have: terms were set
+// since the last reducing call.
+struct SecaggStage {
+    SecaggCfg cfg;
+    bool have = false;
+    int T = 0, npos = 0;
+    uint32_t cnet = 0;
+    std::vector<uint32_t> tab;
+    DevArrays dev;
+    bool on() const { return cfg.on(); }
+};
 // The stages that are on in a StageCfgs or a Part, one bit per StageId.
 template <class S>
 inline unsigned stages_on(const S& s) {
     return s.opt.on() << kOpt | s.clip.on() << kClip | s.krum.on() << kKrum | s.geomed.on() << kGeomed |
-           s.bulyan.on() << kBulyan | s.noise.on() << kNoise | s.mx8.on() << kMx8 | s.reply.on() << kReply;
+           s.bulyan.on() << kBulyan | s.noise.on() << kNoise | s.mx8.on() << kMx8 | s.reply.on() << kReply | s.secagg.on() << kSecagg;
 }
 
 struct Part {
@@ -451,6 +469,7 @@ struct Part {
     NoiseStage noise;
     Mx8Stage mx8;
     ReplyStage reply;
+    SecaggStage secagg;
     DevArrays oavg;
 };
 
@@ -528,6 +547,7 @@ P* const* piece_ptrs(const Part& p, int g, int j, int k0, int k1, std::vector<P*
 
 // fa_api.hip, for the stages (each is described where it is defined)
 int check_part(fa_ctx* ctx, int part_id, Part** out);
+int ensure_scratch(fa_ctx* ctx, int g, size_t bytes);
 int wait_copies(fa_ctx* ctx, int g, hipStream_t s);
 void set_range_runs(Part& p, int G);
 int host_flush(fa_ctx* ctx, Part& p);

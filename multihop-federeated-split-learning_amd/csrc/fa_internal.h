@@ -155,6 +155,28 @@ hipError_t launch_noise(const float* avg, void* out, fa_dtype odt, float stddev,
                         uint32_t round, uint64_t idx0, const Split& sp, const Tuning& tu, hipStream_t s);
 // The same normals on the host (fa_noise_host): z[0, n) := z_{idx0} .. z_{idx0 + n - 1}.  The kernel's own source.
 void noise_host(uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0, size_t n, float* z);
+// The secagg stage (fa.h "Secagg stage"), fa_secagg.hip.  out[i] := fl32((float)(int32_t)u_i * scale) rounded once to
+// odt, u_i = init[i] + the nc buckets' words + the signed ChaCha20 words of the T terms at bucket element idx0 + i,
+// modulo 2^32 (raw: out[i] := u_i as uint32, no terms, the sums a later pass continues; out may be init).  tab: the
+// device copy of secagg_table's words, with npos and cnet as it gave them.  sp: secagg_split of the first bucket,
+// every other bucket and out required as well.  form: kSecaggTile or kSecaggSplit, anything else = secagg_form(n, T).
+enum { kSecaggTile = 0, kSecaggSplit = 1 };
+int secagg_form(int64_t n, int T);  // host rule: which vector form a launch over n elements and T terms takes
+// The split of a launch over bucket elements [idx0, idx0 + n) whose first bucket lies at `lead` (host-only): the head
+// ends at a multiple of 16 of the bucket index, which brings `lead` to 16 bytes iff the two phases agree modulo 4;
+// else the launch takes the element form throughout.
+Split secagg_split(const void* lead, uint64_t idx0, size_t n);
+// The term table (host-only): tab (secagg_table_words(T) words) := the uniform sums of the initial states, then the
+// terms (key: 8 words each, nonce: 3) with the +1 terms first; *npos their count, *cnet = npos - (T - npos).
+size_t secagg_table_words(int T);
+void secagg_table(int T, const uint32_t* keys, const uint32_t* nonces, const int* signs, uint32_t* tab, int* npos,
+                  uint32_t* cnet);
+hipError_t launch_secagg(const ClientTable& t, int nc, const uint32_t* tab, int T, int npos, uint32_t cnet,
+                         const uint32_t* init, void* out, fa_dtype odt, bool raw, float scale, uint64_t idx0,
+                         const Split& sp, int form, const Tuning& tu, hipStream_t s);
+// The mask words on the host (fa_secagg_mask_host): out[0, n) := the words of elements idx0 .. idx0 + n - 1.  The
+// kernel's own rounds.
+void secagg_mask_host(const uint32_t* key, const uint32_t* nonce, uint64_t idx0, size_t n, uint32_t* out);
 // MX8 receipts (fa.h "MX8 receipts"), fa_mx8.hip.  dst[i] (dtype ddt, one rounding) := fl(widen(ref[i]) + d_i), or d_i
 // without a reference (ref null), over n elements, d_i = fl((float)q[i] * 2^(E - 133)) with E = e[((idx0 + i) >> 5) -
 // (idx0 >> 5)]: e[0] is the scale of the block that bucket element idx0 lies in.  (ddt, rdt) as dtype_pair_ok(in, out).

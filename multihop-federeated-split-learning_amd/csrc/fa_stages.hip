@@ -1,5 +1,5 @@
 // fa_stages.hip -- the aggregation stages of libfa (fa.h: server optimizer, clip, Krum, geomed, Bulyan, noise, MX8
-// receipts, MX8 replies) and their entries of the C ABI.  A stage is one struct (fa_host.h), one row of the admission
+// receipts, MX8 replies, secagg) and their entries of the C ABI.  A stage is one struct (fa_host.h), one row of the admission
 // rule (kRules, admit), its set_part_* / free_* pair, and its share of the four calls reduce_part (fa_api.hip) makes
 // around a range part's launches: stage_round_begin, stage_piece, stage_gpu_end, stage_round_end.
 #include "fa_host.h"
@@ -420,8 +420,13 @@ void free_reply(fa_ctx* ctx, Part& p) {
     for (DevArrays* a : {&p.reply.sent, &p.reply.codes}) a->free(ctx->gpu);
     p.reply = ReplyStage{};
 }
+void free_secagg(fa_ctx* ctx, Part& p) {
+    p.secagg.dev.free(ctx->gpu);
+    p.secagg = SecaggStage{};
+}
 void free_stages(fa_ctx* ctx, Part& p) {
     p.noise = NoiseStage{};
+    free_secagg(ctx, p);
     free_mx8(ctx, p);
     free_reply(ctx, p);
     free_opt(ctx, p);
@@ -741,6 +746,104 @@ int bulyan_piece(fa_ctx* ctx, Part& p, int g, int j, const SubsetPlan& plan, voi
     return centered_on(ctx->tuning.tu, ptrs.data(), nc, cnt, p.in, dst, odt, std::max(1, nc - 2 * p.bulyan.cfg.f), st);
 }
 
+// ------------------------------------------------------------------ secagg stage
+
+constexpr uint64_t kSecaggMaxIndex = (uint64_t)1 << 36;  // idx0 + n: the block counter i >> 4 is a uint32
+
+// The refusals shared by fa_set_secagg and fa_secagg_unmask_device.
+int check_secagg_scale(float scale) {
+    if (!finite_f(scale) || !(scale > 0.0f)) return fail(FA_ERR_ARG, "secagg: scale %g must be finite and > 0", (double)scale);
+    return FA_OK;
+}
+int check_secagg_range(uint64_t idx0, size_t n) {
+    if (idx0 > kSecaggMaxIndex || (uint64_t)n > kSecaggMaxIndex - idx0)
+        return fail(FA_ERR_ARG, "secagg: idx0 + n beyond 2^36 (the ChaCha20 block counter has 32 bits)");
+    return FA_OK;
+}
+int check_secagg_terms(int T, const uint32_t* keys, const uint32_t* nonces, const int* signs) {
+    if (T < 0 || T > FA_SECAGG_MAX_TERMS) return fail(FA_ERR_ARG, "secagg: T = %d terms outside 0..%d", T, FA_SECAGG_MAX_TERMS);
+    if (T > 0 && (!keys || !nonces || !signs))
+        return fail(FA_ERR_ARG, "secagg: %s is null", !keys ? "keys" : !nonces ? "nonces" : "signs");
+    for (int t = 0; t < T; ++t)
+        if (signs[t] != 1 && signs[t] != -1) return fail(FA_ERR_ARG, "secagg: sign %d of term %d is neither +1 nor -1", signs[t], t);
+    return FA_OK;
+}
+
+// The unmasking on the current device: D buckets of n uint32 words that are bucket elements idx0 .., the T terms of
+// the device table d_tab -> dst (dtype odt).  D beyond kMaxClients: passes that continue the uint32 sums, in dst
+// itself for an f32 output, else in the context's scratch; the terms go into the last one.
+int secagg_on(fa_ctx* ctx, int g, const fa::Tuning& tu, const void* const* clients, int D, size_t n, uint64_t idx0,
+              const uint32_t* d_tab, int T, int npos, uint32_t cnet, float scale, void* dst, fa_dtype odt, int form,
+              hipStream_t s) {
+    if (n == 0) return FA_OK;
+    const size_t so = dsize(odt);
+    if (int rc = check_clients(clients, D, 4, "client")) return rc;
+    if (!dst) return fail(FA_ERR_ARG, "output pointer is null");
+    if (!aligned(dst, so)) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", so);
+    fa::Split sp = fa::secagg_split(clients[0], idx0, n);
+    for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
+    sp.require(dst, so);
+    const int passes = (D + fa::kMaxClients - 1) / fa::kMaxClients;
+    uint32_t* acc = nullptr;
+    if (passes > 1) {
+        if (odt == FA_F32) {
+            acc = static_cast<uint32_t*>(dst);
+        } else {
+            if (!ctx) return fail(FA_ERR_ARG, "%s output with D > %d needs a ctx for scratch", fa::dtype_name(odt), fa::kMaxClients);
+            if (int rc = ensure_scratch(ctx, g, n * 4)) return rc;
+            acc = static_cast<uint32_t*>(ctx->gpu[(size_t)g].scratch);
+            sp.require(acc, 4);
+        }
+    }
+    for (int p = 0; p < passes; ++p) {
+        const int k0 = p * fa::kMaxClients, nc = std::min(fa::kMaxClients, D - k0);
+        const fa::ClientTable t = client_table(clients, nullptr, k0, nc);
+        const bool last = p == passes - 1;
+        FA_HIP(fa::launch_secagg(t, nc, d_tab, T, npos, cnet, p ? acc : nullptr, last ? dst : (void*)acc, odt, !last, scale,
+                                 idx0, sp, form, tu, s));
+    }
+    return FA_OK;
+}
+
+// The device tables of a secagg part, allocated once: room for FA_SECAGG_MAX_TERMS terms per GPU.
+int ensure_secagg_tab(fa_ctx* ctx, Part& p) {
+    if (p.secagg.dev) return FA_OK;
+    const size_t bytes = fa::secagg_table_words(FA_SECAGG_MAX_TERMS) * 4;
+    const int g = p.secagg.dev.alloc(ctx->gpu, [&](size_t) { return bytes; });
+    if (g < 0) return FA_OK;
+    return fail(FA_ERR_NOMEM, "secagg: term table alloc of %zu B failed on GPU %zu", bytes, (size_t)g);
+}
+
+// The round's terms onto every GPU that holds elements, on the stream its pieces will run on and after the part's
+// last reducing call, which may have read the table on another stream.
+int secagg_round_begin(fa_ctx* ctx, Part& p, hipStream_t s) {
+    SecaggStage& sa = p.secagg;
+    if (!sa.have)
+        return fail(FA_ERR_STATE, "secagg: part %d has no terms for this round (fa_secagg_set_terms before every reducing "
+                                  "call; T = 0 is set explicitly)", p.id);
+    if (int rc = ensure_secagg_tab(ctx, p)) return rc;
+    for (int g = 0; g < ctx->G; ++g) {
+        if (p.cnt[(size_t)g] == 0) continue;
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        hipStream_t st = s ? s : r.compute;
+        if (hipStream_t ds = p.done_stream[(size_t)g]; ds && ds != st) {
+            FA_HIP(hipEventRecord(p.done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(st, p.done[(size_t)g], 0));
+        }
+        FA_HIP(hipMemcpyAsync(sa.dev.at((size_t)g), sa.tab.data(), sa.tab.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    return FA_OK;
+}
+
+// Rules 2-4 for piece j of GPU g (the current device), into dst (dtype odt): every client of the part, the round's terms.
+int secagg_piece(fa_ctx* ctx, Part& p, int g, int j, std::vector<const void*>& ptrs, void* dst, fa_dtype odt, hipStream_t st) {
+    const SecaggStage& sa = p.secagg;
+    return secagg_on(ctx, g, ctx->tuning.tu, piece_ptrs(p, g, j, 0, p.D, ptrs), p.D, piece_cnt(p, g, j),
+                     (uint64_t)(p.off[(size_t)g] + piece_lo(p, g, j)), sa.dev.at<uint32_t>((size_t)g), sa.T, sa.npos, sa.cnet,
+                     sa.cfg.scale, dst, odt, -1, st);
+}
+
 // ------------------------------------------------------------------ one reducing call, as the stages see it
 
 int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, StageRound* rd) {
@@ -765,10 +868,12 @@ int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, Stage
     if (p.krum.on()) return krum_plan(ctx, p, w, s, &rd->plan);
     if (p.geomed.on()) return geomed_plan(ctx, p, w, s, &rd->plan);
     if (p.bulyan.on()) return bulyan_plan(ctx, p, s, &rd->plan);
+    if (p.secagg.on()) return secagg_round_begin(ctx, p, s);
     return FA_OK;
 }
 
-// The aggregate into adst (dst without a server optimizer or a noise stage; with one in fp32 -- an f32 part: in its
+// The aggregate (the plain chain, a plan's chain, Bulyan's centred mean or the unmasked sum of a secagg part)
+// into adst (dst without a server optimizer or a noise stage; with one in fp32 -- an f32 part: in its
 // output, where the stages then run in place), then the noise (in place before a server optimizer, else into dst with the
 // one rounding), then one step or the bootstrap of a part without a master, then the new clip reference.
 int stage_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, const StageRound& rd, std::vector<const void*>& ptrs,
@@ -785,6 +890,8 @@ int stage_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, const StageR
         rc = subset_chain(ctx, p, g, j, rd.plan, adst, adt, st);
     else if (p.bulyan.on())
         rc = bulyan_piece(ctx, p, g, j, rd.plan, adst, adt, st);
+    else if (p.secagg.on())
+        rc = secagg_piece(ctx, p, g, j, ptrs, adst, adt, st);
     else
         rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                        mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
@@ -815,6 +922,7 @@ void stage_round_end(Part& p) {
     }
     if (p.clip.on()) p.clip.has_ref = true;  // what this round sent out
     if (p.noise.on()) ++p.noise.round;       // one reducing call = one round of the generator
+    if (p.secagg.on()) p.secagg.have = false;  // terms are per round: a stale list is never applied
 }
 
 // ------------------------------------------------------------------ setting a stage on a part
@@ -961,6 +1069,24 @@ int set_part_flag(fa_ctx* ctx, Part& p, bool reply, bool on) {
     return FA_OK;
 }
 
+// fa_set_secagg on a part (scale checked; an FA_FEDAVG part with f32 slots, not rs).  Off: the table and the terms go,
+// after the devices' pending work.  A part that has the stage: only the scale changes.  Else the round so far goes
+// back to the plain path; the round has no terms until fa_secagg_set_terms.
+int set_part_secagg(fa_ctx* ctx, Part& p, const SecaggCfg& c) {
+    if (!c.on()) {
+        if (p.secagg.on())
+            if (int rc = wait_devices(ctx)) return rc;
+        free_secagg(ctx, p);
+        return FA_OK;
+    }
+    if (!p.secagg.on()) {
+        if (int rc = host_flush(ctx, p)) return rc;
+        restart_round_plain(p);
+    }
+    p.secagg.cfg = c;
+    return FA_OK;
+}
+
 int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
     switch (id) {
         case kOpt: return set_part_opt(ctx, p, c.opt);
@@ -969,6 +1095,7 @@ int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
         case kGeomed: return set_part_select(p, p.geomed, c.geomed);
         case kBulyan: return set_part_bulyan(p, c.bulyan);
         case kNoise: return set_part_noise(ctx, p, c.noise);
+        case kSecagg: return set_part_secagg(ctx, p, c.secagg);
         default: return set_part_flag(ctx, p, id == kReply, id == kReply ? c.reply.flag : c.mx8.flag);
     }
 }
@@ -977,26 +1104,30 @@ int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
 
 // One row per stage, in StageId order: its name as the refusals begin, its name as in "has a Krum stage", the bucket
 // modes it applies to (a bit per fa_mode), whether it belongs to the measure-then-select family (at most one per part,
-// and at most one among the context defaults), and the tails of its refusals of an rs context and of a part's mode.
+// and at most one among the context defaults), the stages outside the family it never shares a part with, and the
+// tails of its refusals of an rs context and of a part's mode.
 struct StageRule {
     const char *name, *title;
     unsigned modes;
     bool family;
+    unsigned never;
     const char *rs_tail, *mode_tail;
 };
 constexpr unsigned kAvg = 1u << FA_FEDAVG, kTrim = 1u << FA_TRIMMED;
 const StageRule kRules[kStages] = {
-    {"server opt", "server-optimizer", kAvg | kTrim, false, "its aggregate is not bit-specified", ""},
-    {"clip", "clip", kAvg, true, "its aggregate is not bit-specified; use FA_SHARD_RANGE", " (the stage clips FA_FEDAVG updates)"},
-    {"krum", "Krum", kAvg, true, "a pair's distance needs both clients on one GPU; use FA_SHARD_RANGE",
+    {"server opt", "server-optimizer", kAvg | kTrim, false, 0, "its aggregate is not bit-specified", ""},
+    {"clip", "clip", kAvg, true, 0, "its aggregate is not bit-specified; use FA_SHARD_RANGE", " (the stage clips FA_FEDAVG updates)"},
+    {"krum", "Krum", kAvg, true, 0, "a pair's distance needs both clients on one GPU; use FA_SHARD_RANGE",
      " (the stage selects the owners of an FA_FEDAVG average)"},
-    {"geomed", "geomed", kAvg, true, "a distance needs every client of an element on one GPU; use FA_SHARD_RANGE",
+    {"geomed", "geomed", kAvg, true, 0, "a distance needs every client of an element on one GPU; use FA_SHARD_RANGE",
      " (the stage re-weights the owners of an FA_FEDAVG average)"},
-    {"bulyan", "Bulyan", kTrim, false, "the rule needs every client on one GPU; use FA_SHARD_RANGE",
+    {"bulyan", "Bulyan", kTrim, false, 0, "the rule needs every client on one GPU; use FA_SHARD_RANGE",
      " (the stage replaces the window of an FA_TRIMMED part)"},
-    {"noise", "noise", kAvg | kTrim, false, "its aggregate is not bit-specified; use FA_SHARD_RANGE", ""},
-    {"mx8", "MX8", kAvg | kTrim, false, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
-    {"mx8 reply", "reply", kAvg | kTrim, false, "use FA_SHARD_RANGE", ""},
+    {"noise", "noise", kAvg | kTrim, false, 0, "its aggregate is not bit-specified; use FA_SHARD_RANGE", ""},
+    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
+    {"mx8 reply", "reply", kAvg | kTrim, false, 0, "use FA_SHARD_RANGE", ""},
+    {"secagg", "secagg", kAvg, true, 1u << kMx8, "its sum is taken over every client of an element; use FA_SHARD_RANGE",
+     " (the stage unmasks the sum of an FA_FEDAVG part)"},
 };
 
 // The request "turn stage id on (or off), on the context default (part_id < 0, *out = null) or on this part (*out)"
@@ -1021,6 +1152,13 @@ int admit(fa_ctx* ctx, StageId id, bool on, int part_id, Part** out) {
         if (!p) return fail(FA_ERR_ARG, "%s: the context default has a %s stage (the two stages do not compose)", r.name, kRules[o].title);
         return fail(FA_ERR_ARG, "%s: part %d has a %s stage (the two stages do not compose)", r.name, part_id, kRules[o].title);
     }
+    for (int o = 0; p && o < kStages; ++o)  // masked words are no MX8 deltas, and MX8 slots hold no masked words
+        if (have & r.never & (1u << o))
+            return fail(FA_ERR_ARG, "%s: part %d has a %s stage (the two stages do not compose)", r.name, part_id, kRules[o].title);
+    if (id == kSecagg && p && p->in != FA_F32)
+        return fail(FA_ERR_ARG, "secagg: part %d has %s slots (masked uint32 words lie in FA_F32 slots)", part_id, fa::dtype_name(p->in));
+    if (id == kSecagg && p && (uint64_t)p->n > kSecaggMaxIndex)
+        return fail(FA_ERR_ARG, "secagg: part %d holds more than 2^36 elements (the ChaCha20 block counter has 32 bits)", part_id);
     return FA_OK;
 }
 
@@ -1570,6 +1708,118 @@ int fa_noise_host(uint64_t seed, uint32_t stream, uint32_t round, uint64_t idx0,
     fa::noise_host(seed, stream, round, idx0, n, z);
     return FA_OK;
 }
+
+int fa_set_secagg(fa_ctx* ctx, int part_id, float scale) {
+    g_err.clear();
+    StageCfgs c = requested(ctx);
+    c.secagg.scale = 0.0f;
+    if (scale > 0.0f || scale != scale) {  // <= 0 turns the stage off
+        if (int rc = check_secagg_scale(scale)) return rc;
+        if (ctx && part_id < 0)
+            return fail(FA_ERR_ARG, "secagg: set on a part, not as a context default (a round's terms belong to one part)");
+        c.secagg.scale = scale;
+    }
+    return set_stage(ctx, part_id, kSecagg, c);
+}
+
+int fa_secagg_set_terms(fa_ctx* ctx, int part_id, int T, const uint32_t* keys, const uint32_t* nonces, const int* signs) {
+    g_err.clear();
+    Part* p;
+    if (int rc = check_part(ctx, part_id, &p)) return rc;
+    if (int rc = check_secagg_terms(T, keys, nonces, signs)) return rc;
+    if (!p->secagg.on()) return fail(FA_ERR_STATE, "part %d has no secagg stage", part_id);
+    SecaggStage& sa = p->secagg;
+    sa.tab.resize(fa::secagg_table_words(T));
+    fa::secagg_table(T, keys, nonces, signs, sa.tab.data(), &sa.npos, &sa.cnet);
+    sa.T = T;
+    sa.have = true;
+    p->ready = false;  // new terms invalidate a finished reduction, as a new receipt does
+    return FA_OK;
+}
+
+// The body of fa_secagg_unmask_device; form: as launch_secagg's (the diagnostic entry forces one).
+static int secagg_unmask_impl(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, uint64_t idx0, int T,
+                              const uint32_t* keys, const uint32_t* nonces, const int* signs, float scale, void* d_out,
+                              fa_dtype out, int form, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (D < 1) return fail(FA_ERR_ARG, "secagg: D must be >= 1");
+    if (!dvalid(out)) return fail(FA_ERR_ARG, "bad dtype");
+    if (int rc = check_secagg_scale(scale)) return rc;
+    if (int rc = check_secagg_terms(T, keys, nonces, signs)) return rc;
+    if (int rc = check_secagg_range(idx0, n)) return rc;
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) return FA_OK;
+    if (int rc = check_clients(d_clients, D, 4, "client")) return rc;
+    if (!d_out) return fail(FA_ERR_ARG, "output pointer is null");
+    if (!aligned(d_out, dsize(out))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(out));
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    std::vector<uint32_t> tab(fa::secagg_table_words(T));
+    int npos = 0;
+    uint32_t cnet = 0;
+    fa::secagg_table(T, keys, nonces, signs, tab.data(), &npos, &cnet);
+    uint32_t* d_tab = nullptr;  // a table of its own, freed before the return: the entry waits for its stream
+    if (hipMalloc((void**)&d_tab, tab.size() * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FA_ERR_NOMEM, "secagg: term table alloc of %zu B failed", tab.size() * 4);
+    }
+    hipError_t e = hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+    int rc = FA_OK;
+    if (e == hipSuccess) rc = secagg_on(ctx, c.g, c.tu, d_clients, D, n, idx0, d_tab, T, npos, cnet, scale, d_out, out, form, c.s);
+    const hipError_t es = hipStreamSynchronize(c.s);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d_tab);
+    if (rc) return rc;
+    FA_HIP(e);
+    return FA_OK;
+}
+
+int fa_secagg_unmask_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, uint64_t idx0, int T,
+                            const uint32_t* keys, const uint32_t* nonces, const int* signs, float scale, void* d_out,
+                            fa_dtype out, void* hip_stream) {
+    return secagg_unmask_impl(ctx, gpu, d_clients, D, n, idx0, T, keys, nonces, signs, scale, d_out, out, -1, hip_stream);
+}
+
+// Diagnostic, outside fa.h: fa_secagg_unmask_device in the vector form `form` (0 tile per wave, 1 term split)
+// whatever fa_secagg_form says -- the same bits; for measuring one form against the other.
+int fa_diag_secagg_unmask(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, uint64_t idx0, int T,
+                          const uint32_t* keys, const uint32_t* nonces, const int* signs, float scale, void* d_out,
+                          fa_dtype out, int form, void* hip_stream) {
+    if (form != fa::kSecaggTile && form != fa::kSecaggSplit) {
+        g_err.clear();
+        return fail(FA_ERR_ARG, "secagg: form %d is neither 0 nor 1", form);
+    }
+    return secagg_unmask_impl(ctx, gpu, d_clients, D, n, idx0, T, keys, nonces, signs, scale, d_out, out, form, hip_stream);
+}
+
+int fa_secagg_mask_host(const uint32_t* key, const uint32_t* nonce, uint64_t idx0, size_t n, uint32_t* out) {
+    g_err.clear();
+    if (int rc = check_secagg_range(idx0, n)) return rc;
+    if (n == 0) return FA_OK;
+    if (!key || !nonce || !out) return fail(FA_ERR_ARG, "secagg: %s is null", !key ? "key" : !nonce ? "nonce" : "out");
+    fa::secagg_mask_host(key, nonce, idx0, n, out);
+    return FA_OK;
+}
+
+int fa_secagg_quantize(const float* v, size_t n, float q, int32_t* out, uint64_t* n_bad) {
+    g_err.clear();
+    if (!finite_f(q) || !(q > 0.0f)) return fail(FA_ERR_ARG, "secagg: q %g must be finite and > 0", (double)q);
+    if (n_bad) *n_bad = 0;
+    if (n == 0) return FA_OK;
+    if (!v || !out) return fail(FA_ERR_ARG, "secagg: %s is null", !v ? "v" : "out");
+    const double lim = 2147483647.0;
+    uint64_t bad = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const double c = std::nearbyint((double)v[i] * (double)q);  // to nearest, ties to even
+        if (c != c) ++bad;
+        out[i] = c != c ? 0 : c > lim ? INT32_MAX : c < -lim ? -INT32_MAX : (int32_t)c;
+    }
+    if (n_bad) *n_bad = bad;
+    return FA_OK;
+}
+
+int fa_secagg_form(size_t n, int T) { return fa::secagg_form((int64_t)n, T); }
 
 size_t fa_mx8_scale_bytes(size_t n) { return n / FA_MX8_BLOCK + (n % FA_MX8_BLOCK ? 1 : 0); }
 
