@@ -142,6 +142,54 @@
  *              stream round trip more than a plain round), selects on the host and then enqueues the chain.  Added
  *              without a new FA_ABI_VERSION: fa_pairdist_device with n == 0 touches no device, writes D * D zeros
  *              and answers FA_OK -- that is how a caller probes for it.
+ *   Gram pass (fa_gram_device): the D x D matrix of inner products of D client buckets, optionally against an fp32
+ *              reference -- norms, cosines and pairwise distances of updates all come from it.  D <=
+ *              FA_DNC_MAX_CLIENTS.
+ *              y_k,i is x_k,i widened exactly to fp32 (bf16; fp16 with its subnormals); with a reference y_k,i =
+ *              fl32(widen(x_k,i) - ref_i), one IEEE subtract, subnormals kept.  G_ab = sum_i (double)y_a,i *
+ *              (double)y_b,i for all a <= b.  Every product is exact in fp64 (24 x 24 significand bits).  The order
+ *              and grouping of the fp64 adds is NOT specified, the four-term sum inside a matrix instruction
+ *              included; whatever the order |G_ab - exact| <= n * 2^-53 * sum_i |y_a,i y_b,i|.  No floating-point
+ *              atomics: for one layout (GPU count, tuning, n, D, pointer phases) the result is the same bits on every
+ *              run.  Each pair is computed once and mirrored: the matrix is bit-symmetric.  The diagonal is computed:
+ *              G_kk is the squared norm of y_k.  NaN and inf propagate by IEEE rules (0 * inf is NaN); a non-finite
+ *              element of client k can only reach row and column k.  On range shards and range pieces the per-shard /
+ *              per-piece matrices are added on the host in fp64, in GPU order and then piece order.  Added without a
+ *              new FA_ABI_VERSION: fa_gram_device with n == 0 touches no device, writes D * D zeros and answers FA_OK
+ *              -- that is how a caller probes for it.
+ *   DnC stage (fa_set_dnc): spectral selection of the owners of an FA_FEDAVG part (Divide-and-Conquer: Shejwalkar and
+ *              Houmansadr, "Manipulating the Byzantine: Optimizing Model Poisoning Attacks and Defenses for Federated
+ *              Learning", NDSS 2021).  Distance rules miss a group of owners that all shift by the same modest
+ *              vector; DnC projects the centred buckets on their top singular direction and removes the owners with
+ *              the largest projections.  Here the direction comes from the full Gram matrix, not from subsampled
+ *              coordinates.  No part-level state and no reference model.  Parameters: drop, the number of owners to
+ *              remove (the paper's c f), 0 <= drop, 2 drop < D <= FA_DNC_MAX_CLIENTS; and P, the power iterations,
+ *              1 <= P <= FA_DNC_MAX_ITERS.  Rules 2-7 are fa_dnc_select: pure host arithmetic in fp64, every multiply
+ *              and add rounded separately (no contraction), sums in client order from +0.  Per round, with weights w_k:
+ *              1. Gram.  G is the Gram pass, without a reference (centring removes any common vector), over the
+ *                 clients the plain round would reduce.
+ *              2. Non-finite buckets.  A client whose G_kk is NaN or +inf is excluded for the round.  R is the rest,
+ *                 ascending, r = |R|; by Cauchy-Schwarz every G_ab with a, b in R is finite.  r == 0: the aggregate
+ *                 is +0.
+ *              3. Centring (unweighted, as in the paper).  rho_a = (sum_{b in R} G_ab) / r, mu = (sum_{a in R}
+ *                 rho_a) / r, C_ab = ((G_ab - rho_a) - rho_b) + mu.
+ *              4. Start.  a* = the lowest index in R that maximises C_aa.  If C_a*a* is not > 0 (all buckets equal)
+ *                 every score is +0 and rules 5-6 are skipped.  Otherwise u_b = C_b,a*.
+ *              5. Power iteration, P times.  t_k = sum_{b in R} C_kb u_b, M = max_k |t_k| (NaN if any t_k is).  If M
+ *                 is 0 or not finite: stop and keep u.  Otherwise u_k = t_k / M.
+ *              6. Scores.  t = C u once more, s_k = t_k t_k: lambda times the squared projection of the centred
+ *                 bucket on the top singular direction, which orders the owners as the paper's scores do.
+ *              7. Selection.  Excluded clients count against the budget: q = max(0, min(drop - (D - r), r - 1)).  The
+ *                 q clients of R with the largest (s_k, k) are removed (ties remove the higher index; a NaN score
+ *                 counts as +inf); the rest are selected.  The report: the scores (+inf for an excluded client),
+ *                 the flags and their count.
+ *              8. Weights and aggregate.  Exactly rules 4 and 5 of the Krum stage: fa_krum_weights, then the chain
+ *                 over the selected owners in client order.  With nobody removed it is the plain FA_FEDAVG aggregate
+ *                 bit for bit.  It is the part's fp32 aggregate a, as a Krum part's.
+ *              A reducing call of such a part enqueues the Gram pass on every GPU, waits for the matrices (one stream
+ *              round trip more than a plain round, one more read of the slots), selects on the host and then enqueues
+ *              the chain.  Buckets that agree closely leave C with fewer good digits than G; a caller
+ *              that holds the last global model can run fa_gram_device against it and fa_dnc_select itself.
  *   Bulyan stage (fa_set_bulyan): iterated Krum, then a median-centred mean, on an FA_TRIMMED part (El Mhamdi,
  *              Guerraoui, Rouault, "The Hidden Vulnerability of Distributed Learning in Byzantium", ICML 2018).  Krum
  *              alone lets one coordinate of a selected owner be arbitrarily wrong; a trimmed mean alone ignores how
@@ -410,6 +458,9 @@ typedef enum { FA_FEDAVG = 0, FA_LITERAL = 1, FA_TRIMMED = 2 /* trimmed mean / m
 #define FA_TRIMMED_MAX_CLIENTS 128
 /* Most clients of a part with the Krum stage, and of fa_pairdist_device (more: FA_ERR_ARG). */
 #define FA_KRUM_MAX_CLIENTS 128
+/* Most clients of a part with the DnC stage, and of fa_gram_device (more: FA_ERR_ARG); most power iterations. */
+#define FA_DNC_MAX_CLIENTS 128
+#define FA_DNC_MAX_ITERS 1024
 /* Most clients of a part with the geomed stage, and of fa_geomed_pass_device; most Weiszfeld passes per round. */
 #define FA_GEOMED_MAX_CLIENTS 128
 #define FA_GEOMED_MAX_ITERS 64
@@ -729,6 +780,35 @@ int fa_krum_weights(const float* w, const int* selected, int D, float* w_out);
  * stream), waits for it and returns the matrix. */
 int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, double* h_dist,
                        void* hip_stream);
+
+/* The Gram pass on raw device pointers (the header comment, "Gram pass"): h_gram (D * D doubles, row-major) = the
+ * matrix G of the D client buckets (n elements of `in`) on device `gpu`, against d_ref (n fp32) unless it is NULL, 1
+ * <= D <= FA_DNC_MAX_CLIENTS.  ctx may be NULL (then `gpu` is the HIP device).  Every argument is checked before any
+ * device call: D, the dtype, h_gram, and for n > 0 null pointers and element alignment (FA_ERR_ALIGN); with n == 0
+ * and valid arguments it touches no device, writes D * D zeros and answers FA_OK.  Otherwise it enqueues on
+ * hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream), waits for it and returns the matrix. */
+int fa_gram_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, const float* d_ref,
+                   double* h_gram, void* hip_stream);
+/* DnC stage: spectral selection of an FA_FEDAVG part's owners (the header comment, "DnC stage").  Gives a part the
+ * stage with parameters drop and iters (part_id >= 0; calling again changes them), or sets the context default that
+ * FA_FEDAVG parts defined later take (part_id < 0; checked against D when such a part is defined, where a misfit
+ * makes fa_bucket_define fail).  iters == 0 removes the stage.  FA_ERR_ARG, naming the cause: drop < 0, iters outside
+ * 0..FA_DNC_MAX_ITERS, a drop that does not fit the part's D (2 drop < D), D > FA_DNC_MAX_CLIENTS, an FA_LITERAL or
+ * FA_TRIMMED part, an FA_SHARD_CLIENT_RS context, a part (or context default) that has the clip, Krum, geomed or secagg
+ * stage -- and those setters on a DnC part: they do not compose.  The noise stage, the server optimizers, MX8 receipts
+ * and replies compose, in either call order; range shards and range pieces work.  As a Krum part it is never kept
+ * host-side, never eager, gets its own launches in fa_reduce_parts, and a reducing call needs every client submitted
+ * and waits on the host for the Gram pass before it enqueues the chain.  The stage keeps no state across rounds. */
+int fa_set_dnc(fa_ctx* ctx, int part_id, int drop, int iters);
+/* What the part's last reducing call did: gram = the D x D matrix G (row-major), scores[k] = s_k (+inf: excluded),
+ * selected[k] = 0 / 1, *n_selected = how many are selected.  Any pointer may be NULL.  FA_ERR_STATE on a part without
+ * the stage or never reduced with it. */
+int fa_dnc_get_round(fa_ctx* ctx, int part_id, double* gram, double* scores, int* selected, int* n_selected);
+/* Rules 2-7 of the stage, pure host arithmetic, usable without a device: the scores and the selection flags (D
+ * entries each, either may be NULL) of the D x D row-major matrix gram under drop and iters.  FA_ERR_ARG for a null
+ * gram, D < 1 or D > FA_DNC_MAX_CLIENTS, drop < 0 or 2 drop >= D, iters outside 1..FA_DNC_MAX_ITERS.  The weights of the
+ * round are fa_krum_weights of the flags. */
+int fa_dnc_select(const double* gram, int D, int drop, int iters, double* scores, int* selected, int* n_selected);
 
 /* Bulyan stage: iterated Krum, then a median-centred mean, on an FA_TRIMMED part (the header comment, "Bulyan
  * stage").  Gives a part the stage with f owners assumed Byzantine (part_id >= 0; calling again changes f), or sets

@@ -24,6 +24,7 @@ TRIM_MEDIAN = -1  # FA_TRIM_MEDIAN: the largest valid trim, (D-1)/2
 TRIMMED_MAX_CLIENTS = 128
 KRUM_MAX_CLIENTS = 128  # FA_KRUM_MAX_CLIENTS: the Krum stage and pairdist_device
 GEOMED_MAX_CLIENTS, GEOMED_MAX_ITERS = 128, 64  # FA_GEOMED_MAX_*: the geomed stage and geomed_pass_device
+DNC_MAX_CLIENTS, DNC_MAX_ITERS = 128, 1024  # FA_DNC_MAX_*: the DnC stage, gram_device and dnc_select
 # fa_opt_rule: the server-optimizer stage (FedAvgM, FedAdagrad, FedAdam, FedYogi; fa.h "Server optimizer")
 OPT_NONE, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 0, 1, 2, 3, 4
 SHARD_RANGE, SHARD_CLIENT_RS, ACCUMULATE_ON_ARRIVAL, TEST_SHARED_DEVICE = 0x1, 0x2, 0x4, 0x100
@@ -103,6 +104,10 @@ def lib():
         "fa_krum_select": (I, [P, I, I, I, P, P, ctypes.POINTER(I)]),
         "fa_krum_weights": (I, [P, P, I, P]),
         "fa_pairdist_device": (I, [P, I, P, I, S, I, P, P]),
+        "fa_gram_device": (I, [P, I, P, I, S, I, P, P, P]),
+        "fa_set_dnc": (I, [P, I, I, I]),
+        "fa_dnc_get_round": (I, [P, I, P, P, P, ctypes.POINTER(I)]),
+        "fa_dnc_select": (I, [P, I, I, I, P, P, ctypes.POINTER(I)]),
         "fa_set_geomed": (I, [P, I, I, F]),
         "fa_get_geomed": (I, [P, I, ctypes.POINTER(I), ctypes.POINTER(F)]),
         "fa_geomed_get_round": (I, [P, I, ctypes.POINTER(I), P, P, P, P]),
@@ -354,6 +359,33 @@ def krum_weights(weights, selected):
     out = np.empty(w.size, np.float32)
     check(lib().fa_krum_weights(w.ctypes.data, sel.ctypes.data, w.size, out.ctypes.data))
     return out
+
+
+def gram_device(clients, n, in_dtype, ref=None, stream=None, gpu=0, ctx=None):
+    """fa_gram_device: the Gram matrix G_ab = sum_i y_a,i y_b,i (np.float64, shape (D, D), bit-symmetric, the
+    diagonal the squared norms) of D device-resident client buckets, y the widened input or, with the fp32 device
+    reference `ref`, fl32(x - ref) (fa.h "Gram pass").  Enqueued on `stream` and waited for.  With n == 0 no device is
+    touched and the matrix is zeros: the feature probe."""
+    D = len(clients)
+    arr = (ctypes.c_void_p * max(1, D))(*[_addr(c) for c in clients])
+    g = np.empty((D, D), np.float64)
+    check(lib().fa_gram_device(ctx.handle if ctx is not None else None, gpu, arr, D, n, in_dtype, _addr(ref),
+                               g.ctypes.data, _stream(stream)))
+    return g
+
+
+def dnc_select(gram, drop, iters=32):
+    """fa_dnc_select (host arithmetic, rules 2-7 of fa.h "DnC stage"): (scores float64[D], selected bool[D]) of the
+    (D, D) Gram matrix with `drop` owners to remove and `iters` power iterations."""
+    gram = np.ascontiguousarray(gram, np.float64)
+    D = gram.shape[0] if gram.ndim == 2 else 0
+    if gram.ndim != 2 or gram.shape[1] != D:
+        raise ValueError("need a square matrix")
+    scores, sel = np.empty(D, np.float64), np.empty(D, np.intc)
+    ns = ctypes.c_int()
+    check(lib().fa_dnc_select(gram.ctypes.data, D, int(drop), int(iters), scores.ctypes.data, sel.ctypes.data,
+                              ctypes.byref(ns)))
+    return scores, sel.astype(bool)
 
 
 def geomed_pass_device(clients, weights, n, in_dtype, v=None, stream=None, gpu=0, ctx=None):
@@ -826,6 +858,22 @@ class Aggregator:
         check(lib().fa_krum_get_round(self.handle, part_id, q.ctypes.data, s.ctypes.data, sel.ctypes.data,
                                       ctypes.byref(ns)))
         return q, s, sel.astype(bool)
+
+    def set_dnc(self, drop, iters=32, part_id=-1):
+        """fa_set_dnc: DnC spectral selection on a FEDAVG part, removing the `drop` owners that project farthest on
+        the top singular direction of the centred buckets, found by `iters` power iterations on the Gram matrix
+        (part_id < 0: the default of FEDAVG parts defined later); iters=0 removes the stage."""
+        check(lib().fa_set_dnc(self.handle, part_id, int(drop), int(iters)))
+
+    def dnc_round(self, part_id):
+        """fa_dnc_get_round: (gram float64[D, D], scores float64[D], selected bool[D]) of the part's last reducing
+        call."""
+        D = self.parts[part_id][3]
+        g, s, sel = np.empty((D, D), np.float64), np.empty(D, np.float64), np.empty(D, np.intc)
+        ns = ctypes.c_int()
+        check(lib().fa_dnc_get_round(self.handle, part_id, g.ctypes.data, s.ctypes.data, sel.ctypes.data,
+                                     ctypes.byref(ns)))
+        return g, s, sel.astype(bool)
 
     def set_geomed(self, iters, nu=1e-6, part=None):
         """fa_set_geomed: the geometric median (RFA: `iters` smoothed Weiszfeld passes with the distance floor `nu`)

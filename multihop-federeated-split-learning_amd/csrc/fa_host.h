@@ -181,7 +181,7 @@ private:
 int for_each_gpu(CopyPool* workers, int G, const std::function<int(int)>& fn);
 
 // The scratch of a measure pass (the clip stage's norm pass, the Krum and Bulyan stages' distance pass, the geomed
-// stage's fused pass) on one GPU, grown on use (ensure_measure_scratch): `dev` holds room for `outs` fp64 results
+// stage's fused pass, the DnC stage's Gram pass) on one GPU, grown on use (ensure_measure_scratch): `dev` holds room for `outs` fp64 results
 // (a pass's sums or matrices, piece after piece) followed by `parts` per-workgroup partials, `host` is the pinned
 // array the results are read back into.  One instance serves every stage and every part of a context, because
 // every user waits on the host for the stream it enqueued on before it returns, the error returns included
@@ -270,11 +270,11 @@ struct DevArrays {
 //
 //   stage            first set on a part                  set again          removed
 //   opt clip noise   restart_round_plain                  the round stays    the round stays
-//   krum geomed      restart_round_plain                  the round stays    the round stays (`ready` too)
+//   krum geomed dnc  restart_round_plain                  the round stays    the round stays (`ready` too)
 //   bulyan           ready = false                        ready = false      ready = false, if it was on
 //   mx8 reply        host_flush, restart_round_plain      nothing            the round stays
 //   secagg           restart_round_plain, no terms        the round stays    the round stays, the terms go
-enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kStages };
+enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kStages };
 
 struct OptCfg : fa_server_opt {  // fa.h "Server optimizer"
     OptCfg(const fa_server_opt& o = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f}) : fa_server_opt(o) {}
@@ -310,6 +310,10 @@ struct SecaggCfg {  // fa.h "Secagg stage"
     float scale = 0.0f;
     bool on() const { return scale > 0.0f; }
 };
+struct DncCfg {  // fa.h "DnC stage": the owners to remove and P
+    int drop = 0, iters = 0;
+    bool on() const { return iters != 0; }
+};
 struct StageCfgs {
     OptCfg opt;
     ClipCfg clip;
@@ -319,6 +323,7 @@ struct StageCfgs {
     NoiseCfg noise;
     FlagCfg mx8, reply;
     SecaggCfg secagg;
+    DncCfg dnc;
 };
 
 // Per GPU the fp32 state over its cnt elements (v only for the adaptive rules).
@@ -409,11 +414,21 @@ struct SecaggStage {
     DevArrays dev;
     bool on() const { return cfg.on(); }
 };
+// Host state only.  The report: the D x D Gram matrix, the scores, the selection flags and their count.
+struct DncStage {
+    DncCfg cfg;
+    bool reported = false;
+    std::vector<double> q, s;
+    std::vector<int> sel;
+    int n = 0;
+    bool on() const { return cfg.on(); }
+};
 // The stages that are on in a StageCfgs or a Part, one bit per StageId.
 template <class S>
 inline unsigned stages_on(const S& s) {
     return s.opt.on() << kOpt | s.clip.on() << kClip | s.krum.on() << kKrum | s.geomed.on() << kGeomed |
-           s.bulyan.on() << kBulyan | s.noise.on() << kNoise | s.mx8.on() << kMx8 | s.reply.on() << kReply | s.secagg.on() << kSecagg;
+           s.bulyan.on() << kBulyan | s.noise.on() << kNoise | s.mx8.on() << kMx8 | s.reply.on() << kReply | s.secagg.on() << kSecagg |
+           s.dnc.on() << kDnc;
 }
 
 struct Part {
@@ -470,6 +485,7 @@ struct Part {
     Mx8Stage mx8;
     ReplyStage reply;
     SecaggStage secagg;
+    DncStage dnc;
     DevArrays oavg;
 };
 
@@ -578,7 +594,7 @@ struct SubsetPlan {
 // stage follows.  The end of a GPU: the reply stage, then the clip references from g'.  The end: the state across rounds.
 struct StageRound {
     SubsetPlan plan;
-    bool subset = false;  // the aggregate is the plan's chain: a clip stage with a reference, Krum, geomed
+    bool subset = false;  // the aggregate is the plan's chain: a clip stage with a reference, Krum, geomed, DnC
 };
 int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, StageRound* rd);
 int stage_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, const StageRound& rd, std::vector<const void*>& ptrs,

@@ -147,6 +147,20 @@ constexpr int64_t kKrumMaxPartials = kKrumMaxBlocks + 1;  // per pair: the grid'
 inline int64_t krum_pairs(int D) { return (int64_t)D * (D - 1) / 2; }
 hipError_t launch_pairdist(const ClientTable& t, int D, fa_dtype in, const Split& sp, double* partials, double* dist,
                            const Tuning& tu, hipStream_t s);
+// The Gram pass (fa.h "Gram pass"), fa_gram.hip.  gram (device, D * D doubles, row-major) := G_ab = sum_i (double)y_a,i
+// (double)y_b,i over the n elements of clients t.src[0..D), 1 <= D <= kMaxClients (weights not read), y the widened
+// input or, with ref (n fp32, nullable), fl32(widen(x) - ref_i); each entry a <= b computed once on the fp64 MFMA and
+// mirrored, the diagonal included.  One launch over tiles of gram_tile(ceil(D / 16)) elements of all clients writes one
+// fp64 partial per (entry, workgroup) into `partials` (room for gram_entries(D) * kGramMaxPartials doubles, laid out
+// as the clip pass's), a second one adds each entry's partials in a fixed order.  No atomics.  sp: the Split
+// (fa_split.h) led by the first client, ref required as well if given.
+constexpr int64_t kGramMaxBlocks = 768;  // 3 workgroups per CU on 256 CUs, resident at once in every form (at 97 .. 128
+                                         // clients the vector form holds 3 waves per SIMD); tiles beyond it are strided
+constexpr int64_t kGramMaxPartials = kGramMaxBlocks + 1;  // per entry: the grid's, plus one for head and tail
+inline int64_t gram_entries(int D) { return (int64_t)D * (D + 1) / 2; }
+constexpr int gram_tile(int B) { return B == 1 ? 256 : B == 2 ? 128 : B <= 4 ? 64 : 32; }  // elements per tile at B blocks
+hipError_t launch_gram(const ClientTable& t, int D, fa_dtype in, const float* ref, const Split& sp, double* partials,
+                       double* gram, const Tuning& tu, hipStream_t s);
 // The noise stage (fa.h "Noise stage"), fa_noise.hip.  out[i] (dtype odt, one rounding) := fl(avg[i] + fl(stddev z_i))
 // over n elements, z_i the unit normal of bucket element idx0 + i under (seed, stream, round): the result does not
 // depend on how a bucket is cut into launches.  out may be avg itself for FA_F32.  sp: the Split (fa_split.h) led by

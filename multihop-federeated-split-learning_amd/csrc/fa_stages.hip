@@ -1,4 +1,4 @@
-// fa_stages.hip -- the aggregation stages of libfa (fa.h: server optimizer, clip, Krum, geomed, Bulyan, noise, MX8
+// fa_stages.hip -- the aggregation stages of libfa (fa.h: server optimizer, clip, Krum, DnC, geomed, Bulyan, noise, MX8
 // receipts, MX8 replies, secagg) and their entries of the C ABI.  A stage is one struct (fa_host.h), one row of the admission
 // rule (kRules, admit), its set_part_* / free_* pair, and its share of the four calls reduce_part (fa_api.hip) makes
 // around a range part's launches: stage_round_begin, stage_piece, stage_gpu_end, stage_round_end.
@@ -200,6 +200,117 @@ int pairdist_on(const fa::Tuning& tu, const void* const* clients, int D, size_t 
     for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
     const fa::ClientTable t = client_table(clients, nullptr, 0, D);
     FA_HIP(fa::launch_pairdist(t, D, in, sp, d_part, d_dist, tu, s));
+    return FA_OK;
+}
+
+// ------------------------------------------------------------------ DnC stage
+
+inline size_t gram_parts(int D) { return (size_t)fa::gram_entries(D) * (size_t)fa::kGramMaxPartials; }
+
+// The refusals of drop and P for D clients (fa.h "DnC stage"), naming the cause.
+int check_dnc(int D, int drop, int iters) {
+    if (D > FA_DNC_MAX_CLIENTS) return fail(FA_ERR_ARG, "dnc: D = %d clients (at most %d)", D, FA_DNC_MAX_CLIENTS);
+    if (drop < 0 || 2 * drop >= D)
+        return fail(FA_ERR_ARG, "dnc: drop = %d does not fit D = %d clients (0 <= drop and 2 drop < D)", drop, D);
+    if (iters < 1 || iters > FA_DNC_MAX_ITERS) return fail(FA_ERR_ARG, "dnc: iters = %d outside 1..%d", iters, FA_DNC_MAX_ITERS);
+    return FA_OK;
+}
+
+// One rounded fp64 operation each, whatever the host's contraction mode.
+inline double add_r(double a, double b) {
+    volatile double r = a + b;
+    return r;
+}
+inline double mul_r(double a, double b) {
+    volatile double r = a * b;
+    return r;
+}
+inline double div_r(double a, double b) {
+    volatile double r = a / b;
+    return r;
+}
+
+// Rules 2-7 of fa.h "DnC stage" (D, drop, iters checked): scores and selected hold D entries each, any may be null.
+void dnc_select(const double* gram, int D, int drop, int iters, double* scores, int* selected, int* n_selected) {
+    const double inf = HUGE_VAL;
+    const size_t n = (size_t)D;
+    std::vector<int> R;
+    for (int k = 0; k < D; ++k) {
+        const double g = gram[(size_t)k * n + (size_t)k];
+        if (!(g != g || g == inf)) R.push_back(k);
+    }
+    const size_t r = R.size();
+    std::vector<double> sc(n, inf);
+    std::vector<int> sel(n, 0);
+    std::vector<double> C(r * r), rho(r), u(r), t(r);
+    if (r > 0) {  // rule 3
+        double mu = 0.0;
+        for (size_t a = 0; a < r; ++a) {
+            double acc = 0.0;
+            for (size_t b = 0; b < r; ++b) acc = add_r(acc, gram[(size_t)R[a] * n + (size_t)R[b]]);
+            rho[a] = div_r(acc, (double)r);
+            mu = add_r(mu, rho[a]);
+        }
+        mu = div_r(mu, (double)r);
+        for (size_t a = 0; a < r; ++a)
+            for (size_t b = 0; b < r; ++b)
+                C[a * r + b] = add_r(add_r(add_r(gram[(size_t)R[a] * n + (size_t)R[b]], -rho[a]), -rho[b]), mu);
+        size_t star = 0;  // rule 4
+        for (size_t a = 1; a < r; ++a)
+            if (C[a * r + a] > C[star * r + star]) star = a;
+        const auto times_c = [&]() {  // t = C u
+            for (size_t k = 0; k < r; ++k) {
+                double acc = 0.0;
+                for (size_t b = 0; b < r; ++b) acc = add_r(acc, mul_r(C[k * r + b], u[b]));
+                t[k] = acc;
+            }
+        };
+        if (C[star * r + star] > 0.0) {
+            for (size_t b = 0; b < r; ++b) u[b] = C[b * r + star];
+            for (int it = 0; it < iters; ++it) {  // rule 5
+                times_c();
+                double M = 0.0;
+                bool nan = false;
+                for (size_t k = 0; k < r; ++k) {
+                    const double a = std::fabs(t[k]);
+                    if (a != a) nan = true;
+                    if (a > M) M = a;
+                }
+                if (nan || M == 0.0 || M == inf) break;
+                for (size_t k = 0; k < r; ++k) u[k] = div_r(t[k], M);
+            }
+            times_c();  // rule 6
+            for (size_t k = 0; k < r; ++k) sc[(size_t)R[k]] = mul_r(t[k], t[k]);
+        } else {
+            for (size_t k = 0; k < r; ++k) sc[(size_t)R[k]] = 0.0;
+        }
+        // rule 7: the q largest (s_k, k) go; a NaN score counts as +inf
+        const int q = std::max(0, std::min(drop - (D - (int)r), (int)r - 1));
+        std::vector<int> order(R);
+        auto key = [&](int k) { return sc[(size_t)k] != sc[(size_t)k] ? inf : sc[(size_t)k]; };
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return key(a) != key(b) ? key(a) > key(b) : a > b; });
+        for (int k : R) sel[(size_t)k] = 1;
+        for (int i = 0; i < q; ++i) sel[(size_t)order[(size_t)i]] = 0;
+    }
+    int ns = 0;
+    for (int k = 0; k < D; ++k) {
+        if (scores) scores[k] = sc[(size_t)k];
+        if (selected) selected[k] = sel[(size_t)k];
+        ns += sel[(size_t)k];
+    }
+    if (n_selected) *n_selected = ns;
+}
+
+// Enqueues the Gram pass on the current device: d_gram (D * D doubles) = the matrix of clients[0..D) (n > 0 elements
+// of `in`) against ref (nullable); d_part: the partials scratch.  The vector form where every client and ref allow it
+// (fa_split.h).
+int gram_on(const fa::Tuning& tu, const void* const* clients, int D, size_t n, fa_dtype in, const float* ref, double* d_part,
+            double* d_gram, hipStream_t s) {
+    fa::Split sp = fa::split_at(clients[0], dsize(in), n);
+    for (int k = 0; k < D; ++k) sp.require_input(clients[k]);
+    if (ref) sp.require(ref, 4);
+    const fa::ClientTable t = client_table(clients, nullptr, 0, D);
+    FA_HIP(fa::launch_gram(t, D, in, ref, sp, d_part, d_gram, tu, s));
     return FA_OK;
 }
 
@@ -635,6 +746,31 @@ int krum_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* p
     return FA_OK;
 }
 
+// Rules 1-8 of the DnC stage for part p (range layout): the Gram pass (measure_pass, no reference), then the host
+// arithmetic and the Krum stage's weights.  Leaves the round's report in the part.
+int dnc_plan(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, SubsetPlan* plan) {
+    const size_t D = (size_t)p.D;
+    p.dnc.q.assign(D * D, 0.0);
+    if (int rc = measure_pass(ctx, p, s, D * D, gram_parts(p.D), "dnc: gram-pass", p.dnc.q.data(),
+                              [&](int, int, const void* const* clients, size_t cnt, double* d_part, double* d_out,
+                                  hipStream_t st) {
+                                  return gram_on(ctx->tuning.tu, clients, p.D, cnt, p.in, nullptr, d_part, d_out, st);
+                              }))
+        return rc;
+    p.dnc.s.assign(D, 0.0);
+    p.dnc.sel.assign(D, 0);
+    dnc_select(p.dnc.q.data(), p.D, p.dnc.cfg.drop, p.dnc.cfg.iters, p.dnc.s.data(), p.dnc.sel.data(), &p.dnc.n);
+    std::vector<float> wp(D);
+    krum_weights(w, p.dnc.sel.data(), p.D, wp.data());
+    for (size_t k = 0; k < D; ++k)
+        if (p.dnc.sel[k]) {
+            plan->inc.push_back((int)k);
+            plan->w.push_back(wp[k]);
+        }
+    p.dnc.reported = true;
+    return FA_OK;
+}
+
 // Rules 0-4 for part p (range layout): T fused passes (measure_pass over the included clients alone, 2 m results: Q
 // then B), each followed by the host arithmetic; a pass that finds a non-finite bucket is void and repeated without
 // its owner.  The plan is the final chain's: the included clients and alpha^T.  Leaves the round's trace in the part.
@@ -862,10 +998,11 @@ int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, Stage
         if (c.has_ref)
             if (int rc = clip_plan(ctx, p, w, s, &rd->plan)) return rc;
     }
-    // Krum, geomed (never with each other or with clip) and Bulyan (an FA_TRIMMED part: never with those three): the
+    // Krum, geomed, DnC (never with each other or with clip) and Bulyan (an FA_TRIMMED part: never with those three): the
     // passes, the host's waits for their results, and the selection or the new weights
-    if (p.krum.on() || p.geomed.on()) rd->subset = true;
+    if (p.krum.on() || p.geomed.on() || p.dnc.on()) rd->subset = true;
     if (p.krum.on()) return krum_plan(ctx, p, w, s, &rd->plan);
+    if (p.dnc.on()) return dnc_plan(ctx, p, w, s, &rd->plan);
     if (p.geomed.on()) return geomed_plan(ctx, p, w, s, &rd->plan);
     if (p.bulyan.on()) return bulyan_plan(ctx, p, s, &rd->plan);
     if (p.secagg.on()) return secagg_round_begin(ctx, p, s);
@@ -1096,6 +1233,7 @@ int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
         case kBulyan: return set_part_bulyan(p, c.bulyan);
         case kNoise: return set_part_noise(ctx, p, c.noise);
         case kSecagg: return set_part_secagg(ctx, p, c.secagg);
+        case kDnc: return set_part_select(p, p.dnc, c.dnc);
         default: return set_part_flag(ctx, p, id == kReply, id == kReply ? c.reply.flag : c.mx8.flag);
     }
 }
@@ -1128,6 +1266,8 @@ const StageRule kRules[kStages] = {
     {"mx8 reply", "reply", kAvg | kTrim, false, 0, "use FA_SHARD_RANGE", ""},
     {"secagg", "secagg", kAvg, true, 1u << kMx8, "its sum is taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage unmasks the sum of an FA_FEDAVG part)"},
+    {"dnc", "DnC", kAvg, true, 0, "a Gram entry needs both clients on one GPU; use FA_SHARD_RANGE",
+     " (the stage selects the owners of an FA_FEDAVG average)"},
 };
 
 // The request "turn stage id on (or off), on the context default (part_id < 0, *out = null) or on this part (*out)"
@@ -1166,6 +1306,7 @@ int admit(fa_ctx* ctx, StageId id, bool on, int part_id, Part** out) {
 int check_for_clients(StageId id, int D, StageCfgs& c) {
     if (id == kKrum) return check_krum(D, c.krum.f, c.krum.m, &c.krum.m);
     if (id == kGeomed) return check_geomed(D, c.geomed.iters, c.geomed.nu);
+    if (id == kDnc) return check_dnc(D, c.dnc.drop, c.dnc.iters);
     return id == kBulyan ? check_bulyan(D, c.bulyan.f) : FA_OK;
 }
 
@@ -1202,7 +1343,8 @@ int stage_part(fa_ctx* ctx, int part_id, StageId id, Part** out, bool report = f
     if (int rc = check_part(ctx, part_id, out)) return rc;
     const Part& p = **out;
     if (!(stages_on(p) >> id & 1)) return fail(FA_ERR_STATE, "part %d has no %s stage", part_id, kRules[id].title);
-    if (report && !(id == kClip ? p.clip.reported : id == kKrum ? p.krum.reported : id == kGeomed ? p.geomed.reported : p.bulyan.reported))
+    if (report && !(id == kClip ? p.clip.reported : id == kKrum ? p.krum.reported : id == kGeomed ? p.geomed.reported :
+                    id == kDnc ? p.dnc.reported : p.bulyan.reported))
         return fail(FA_ERR_STATE, "part %d: no round reduced with the %s stage yet", part_id, kRules[id].title);
     return FA_OK;
 }
@@ -1516,6 +1658,61 @@ int fa_pairdist_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D
                           [&](const DeviceCall& c, double* d_part, double* d_out) {
                               return pairdist_on(c.tu, d_clients, D, n, in, d_part, d_out, c.s);
                           });
+}
+
+int fa_gram_device(fa_ctx* ctx, int gpu, const void* const* d_clients, int D, size_t n, fa_dtype in, const float* d_ref,
+                   double* h_gram, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (D < 1 || D > FA_DNC_MAX_CLIENTS) return fail(FA_ERR_ARG, "gram: D = %d outside 1..%d", D, FA_DNC_MAX_CLIENTS);
+    if (!dvalid(in)) return fail(FA_ERR_ARG, "bad dtype");
+    if (!h_gram) return fail(FA_ERR_ARG, "gram: h_gram is null");
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    const size_t DD = (size_t)D * (size_t)D;
+    if (n == 0) {
+        std::fill(h_gram, h_gram + DD, 0.0);
+        return FA_OK;
+    }
+    if (int rc = check_clients(d_clients, D, dsize(in), "client")) return rc;
+    if (d_ref && !aligned(d_ref, 4)) return fail(FA_ERR_ALIGN, "gram: reference not 4-byte aligned");
+    return measure_device(ctx, gpu, hip_stream, DD, gram_parts(D), "gram: gram-pass", h_gram,
+                          [&](const DeviceCall& c, double* d_part, double* d_out) {
+                              return gram_on(c.tu, d_clients, D, n, in, d_ref, d_part, d_out, c.s);
+                          });
+}
+
+int fa_set_dnc(fa_ctx* ctx, int part_id, int drop, int iters) {
+    g_err.clear();
+    if (drop < 0 || iters < 0 || iters > FA_DNC_MAX_ITERS)
+        return fail(FA_ERR_ARG, "dnc: drop = %d, iters = %d (drop >= 0; 1 <= iters <= %d, 0 removes the stage)", drop, iters,
+                    FA_DNC_MAX_ITERS);
+    StageCfgs c = requested(ctx);
+    c.dnc = DncCfg{iters != 0 ? drop : 0, iters};
+    return set_stage(ctx, part_id, kDnc, c);
+}
+
+int fa_dnc_get_round(fa_ctx* ctx, int part_id, double* gram, double* scores, int* selected, int* n_selected) {
+    g_err.clear();
+    Part* p;
+    int rc = stage_part(ctx, part_id, kDnc, &p, true);
+    if (rc) return rc;
+    const size_t D = (size_t)p->D;
+    if (gram) std::copy(p->dnc.q.begin(), p->dnc.q.end(), gram);
+    for (size_t k = 0; k < D; ++k) {
+        if (scores) scores[k] = p->dnc.s[k];
+        if (selected) selected[k] = p->dnc.sel[k];
+    }
+    if (n_selected) *n_selected = p->dnc.n;
+    return FA_OK;
+}
+
+int fa_dnc_select(const double* gram, int D, int drop, int iters, double* scores, int* selected, int* n_selected) {
+    g_err.clear();
+    if (!gram) return fail(FA_ERR_ARG, "dnc: gram is null");
+    if (D < 1) return fail(FA_ERR_ARG, "dnc: D must be >= 1");
+    if (int rc = check_dnc(D, drop, iters)) return rc;
+    dnc_select(gram, D, drop, iters, scores, selected, n_selected);
+    return FA_OK;
 }
 
 int fa_set_geomed(fa_ctx* ctx, int part_id, int iters, float nu) {

@@ -120,6 +120,11 @@ struct Options {
     // defined); M defaults to DATA_OWNERS - F
     int krum_f = 0, krum_m = -1;
     bool krum_given = false, krum_m_given = false;
+    // --dnc-drop K [--dnc-iters P]: the DnC stage of every bucket (fa_set_dnc on the context, before any bucket is
+    // defined): per bucket the K owners that project farthest on the top singular direction of the centred receipts
+    // are left out
+    int dnc_drop = 0, dnc_iters = 32;
+    bool dnc_given = false, dnc_iters_given = false;
     // --geomed-iters T [--geomed-nu NU]: the geomed stage of every bucket (fa_set_geomed on the context, before any
     // bucket is defined); NU defaults to 1e-6
     int geomed_iters = 0;
@@ -275,6 +280,7 @@ void usage() {
                  "       [--clip-norm C [--clip-state FILE]]\n"
                  "       [--krum-f F [--krum-m M]]\n"
                  "       [--geomed-iters T [--geomed-nu NU]]\n"
+                 "       [--dnc-drop K [--dnc-iters P]]\n"
                  "       [--dp-noise-multiplier Z [--dp-seed S]]\n"
                  "       [--mx8] [--mx8-reply]\n"
                  "--mode trimmed: per element the T lowest and T highest of the owners' values are dropped and the\n"
@@ -305,6 +311,12 @@ void usage() {
                  "with NU (--geomed-nu, default 1e-6, finite and > 0) as the floor on a distance; nobody is left out but\n"
                  "an owner that sends a NaN or an inf; 1 <= T <= 64, DATA_OWNERS <= 128; not with --clip-norm, --krum-f,\n"
                  "--mode literal|trimmed|median|bulyan or --layout rs.\n"
+                 "--dnc-drop K: per bucket the K owners whose centred receipts project farthest on the receipts' top\n"
+                 "singular direction are left out (DnC: it catches a group that shifts by one common vector, which the\n"
+                 "distance rules miss), the rest are averaged with their weights scaled up to the round's mass; P\n"
+                 "(--dnc-iters, default 32) power iterations find the direction; 0 <= K, 2K < DATA_OWNERS <= 128, 1 <= P\n"
+                 "<= 1024; not with --clip-norm, --krum-f, --geomed-iters, --mode literal|trimmed|median|bulyan or\n"
+                 "--layout rs.\n"
                  "--dp-noise-multiplier Z (with --clip-norm C): Gaussian noise of standard deviation Z * C * max_k w_k (w_k\n"
                  "the round's weights: the sensitivity of the clipped weighted sum to one owner) is added to every bucket's\n"
                  "aggregate before it is stepped or replied: DP-FedAvg.  The seed is drawn from the operating system at\n"
@@ -412,6 +424,12 @@ bool parse_args(int argc, char** argv, Options* o) {
         } else if (a == "--krum-m") {
             o->krum_m = std::atoi(val("--krum-m"));
             o->krum_m_given = true;
+        } else if (a == "--dnc-drop") {
+            o->dnc_drop = std::atoi(val("--dnc-drop"));
+            o->dnc_given = true;
+        } else if (a == "--dnc-iters") {
+            o->dnc_iters = std::atoi(val("--dnc-iters"));
+            o->dnc_iters_given = true;
         } else if (a == "--geomed-iters") {
             o->geomed_iters = std::atoi(val("--geomed-iters"));
             o->geomed_given = true;
@@ -628,6 +646,38 @@ bool parse_args(int argc, char** argv, Options* o) {
             return false;
         }
     }
+    if (!o->dnc_given && o->dnc_iters_given) {
+        std::cerr << "--dnc-iters goes with --dnc-drop\n";
+        return false;
+    }
+    if (o->dnc_given) {
+        if (o->clip_given || o->krum_given || o->geomed_given) {
+            std::cerr << "--dnc-drop and " << (o->clip_given ? "--clip-norm" : o->krum_given ? "--krum-f" : "--geomed-iters")
+                      << " do not compose: one of them\n";
+            return false;
+        }
+        if (o->mode != FA_FEDAVG) {
+            std::cerr << "--dnc-drop selects the owners of a weighted average: not with --mode "
+                      << (o->mode == FA_LITERAL ? "literal" : o->bulyan ? "bulyan" : o->median ? "median" : "trimmed") << "\n";
+            return false;
+        }
+        if (o->rs) {
+            std::cerr << "--dnc-drop needs both owners of a Gram entry on one GPU: not with --layout rs\n";
+            return false;
+        }
+        if (o->data_owners > FA_DNC_MAX_CLIENTS) {
+            std::cerr << "--dnc-drop takes at most " << FA_DNC_MAX_CLIENTS << " data owners\n";
+            return false;
+        }
+        if (o->dnc_drop < 0 || 2 * o->dnc_drop >= o->data_owners) {
+            std::cerr << "--dnc-drop " << o->dnc_drop << ": 0 <= K and 2K < " << o->data_owners << " data owners\n";
+            return false;
+        }
+        if (o->dnc_iters < 1 || o->dnc_iters > FA_DNC_MAX_ITERS) {
+            std::cerr << "--dnc-iters " << o->dnc_iters << ": 1 <= P <= " << FA_DNC_MAX_ITERS << "\n";
+            return false;
+        }
+    }
     return o->data_owners >= 1 && o->stall_report_s > 0 && o->receipt_timeout_s >= 0;
 }
 
@@ -682,6 +732,7 @@ public:
         if (o.clip_given) FA_CHECK(fa_set_clip(ctx_, -1, o.clip_norm));
         if (o.krum_given) FA_CHECK(fa_set_krum(ctx_, -1, o.krum_f, o.krum_m));
         if (o.geomed_given) FA_CHECK(fa_set_geomed(ctx_, -1, o.geomed_iters, o.geomed_nu));
+        if (o.dnc_given) FA_CHECK(fa_set_dnc(ctx_, -1, o.dnc_drop, o.dnc_iters));
         if (o.mx8) FA_CHECK(fa_set_mx8(ctx_, -1, 1));  // before any bucket
         if (o.mx8_reply) FA_CHECK(fa_set_mx8_reply(ctx_, -1, 1));
         if (o.rs_chunks > 0) {
@@ -1103,6 +1154,16 @@ public:
                 std::cerr << "[aggregator] KRUM: part " << mp << ": NO OWNER SELECTED (every score is infinite): the "
                           << "reply of this bucket is all zeros\n";
         }
+        if (o_.dnc_given) {  // what the DnC stage made of this bucket's receipts, for the round line
+            KrumRound& kr = krum_[mp];
+            kr.scores.assign((size_t)o_.data_owners, 0.0);
+            kr.selected.assign((size_t)o_.data_owners, 0);
+            int kept = 0;
+            FA_CHECK(fa_dnc_get_round(ctx_, mp, nullptr, kr.scores.data(), kr.selected.data(), &kept));
+            if (kept == 0)
+                std::cerr << "[aggregator] DNC: part " << mp << ": NO OWNER SELECTED (every receipt holds a NaN or an inf): "
+                          << "the reply of this bucket is all zeros\n";
+        }
         if (o_.geomed_given) {  // what the geomed stage made of this bucket's receipts, for the round line
             const size_t D = (size_t)o_.data_owners;
             GeomedRound& gr = geomed_[mp];
@@ -1294,11 +1355,22 @@ public:
     // slot order (17 significant digits: they read back to the same doubles), the owners' ids in that order once.
     std::string krum_tail() {
         std::ostringstream os;
-        os << ",\"krum_f\":" << o_.krum_f << ",\"krum_m\":" << o_.krum_m << ",\"krum_owners\":[";
+        os << ",\"krum_f\":" << o_.krum_f << ",\"krum_m\":" << o_.krum_m;
+        return os.str() + select_tail("krum");
+    }
+    // --dnc-drop: the same tail under its own names.
+    std::string dnc_tail() {
+        std::ostringstream os;
+        os << ",\"dnc_drop\":" << o_.dnc_drop << ",\"dnc_iters\":" << o_.dnc_iters;
+        return os.str() + select_tail("dnc");
+    }
+    std::string select_tail(const std::string& stage) {
+        std::ostringstream os;
+        os << ",\"" << stage << "_owners\":[";
         for (size_t k = 0; k < expected_.size(); ++k) os << (k ? "," : "") << expected_[k];
         os << "]";
         for (int pass = 0; pass < 2; ++pass) {
-            os << (pass == 0 ? ",\"krum_left_out\":{" : ",\"krum_scores\":{");
+            os << ",\"" << stage << (pass == 0 ? "_left_out\":{" : "_scores\":{");
             bool first = true;
             for (auto& kv : krum_) {
                 os << (first ? "" : ",") << "\"" << kv.first << "\":[";
@@ -1726,7 +1798,7 @@ int main(int argc, char** argv) {
             }
         }
         const std::string clip_tail = mx8_tail +
-            (o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : o.geomed_given ? agg.geomed_tail() : o.bulyan ? agg.bulyan_tail() : std::string()) + (o.dp_given ? agg.dp_tail() : std::string());
+            (o.clip_given ? agg.clip_tail() : o.krum_given ? agg.krum_tail() : o.dnc_given ? agg.dnc_tail() : o.geomed_given ? agg.geomed_tail() : o.bulyan ? agg.bulyan_tail() : std::string()) + (o.dp_given ? agg.dp_tail() : std::string());
         printf("{\"round\":%d,\"phase1\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,"
                "\"absorb_s\":%.6f,\"finalize_s\":%.6f,\"frame_s\":%.6f},"
                "\"phase2\":{\"receive_s\":%.6f,\"reduce_s\":%.6f,\"bytes_in\":%zu,\"layers\":%d,"
