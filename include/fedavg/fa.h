@@ -387,6 +387,34 @@
  *                 refuses a range that starts inside a block (FA_ERR_STATE).
  *              Added without a new FA_ABI_VERSION: fa_mx8_encode_device with n == 0 touches no device and answers
  *              FA_OK -- that is how a caller probes for it.
+ *   Top-k receipts (fa_set_topk, fa_submit_topk, fa_topk_expand_device, fa_topk_encode_device, fa_topk_encode,
+ *              fa_topk_decode): the other common way to shrink an update.  A client sends only the k elements of
+ *              its update x_k - g with the largest magnitude, as (index, value) pairs, and carries the rest over to
+ *              its next round (top-k with error feedback): 8 k bytes where fp32 takes 4 n.  As with MX8 receipts a
+ *              kernel rebuilds the ordinary slot x = g + d, and everything downstream sees an ordinary receipt.
+ *              Format.  A sparse bucket of n elements with k entries is two arrays: idx, k uint32, strictly
+ *              ascending, each < n, the element's position in the whole bucket, never within a shard or a piece;
+ *              val, k fp32.  A bucket with entries needs n <= 2^32 (FA_ERR_ARG beyond).
+ *              Decode (fa_topk_decode): d_i = val_j where i == idx_j, and d_i = +0 everywhere else.
+ *              Expansion is decode rule 3 of MX8 receipts, unchanged: x_i = fl32(widen(g_i) + d_i), one IEEE add,
+ *              the same add for absent elements, so -0 + +0 is +0; a 16-bit slot stores x_i rounded once more to
+ *              nearest-even; without a reference (absolute mode) x_i = d_i, rounded the same way; NaN and inf
+ *              propagate, NaN payloads are unspecified; (slot, ref) pairs are the (in, out) pairs below.
+ *              Selection (the encoder: fa_topk_encode on given deltas, fa_topk_encode_device on `new` and `sent`
+ *              of one dtype), for n elements and k:
+ *              1. delta_i = fl32(widen(new_i) - widen(sent_i)), one IEEE subtract, no contraction.
+ *              2. key_i = bits(delta_i) & 0x7FFFFFFF: the magnitude order, any NaN above inf, +-0 equal.
+ *              3. k' = min(k, n); tau is the k'-th largest key.
+ *              4. Selected are all elements with key > tau, plus the lowest-indexed elements with key == tau, until
+ *                 exactly k' elements are selected.
+ *              5. The entries are written in ascending index order with val_j = delta_i, sign kept, a NaN some quiet
+ *                 NaN.  Zeros are selected like any other value when fewer than k' deltas are non-zero.
+ *              6. g'_i is the expansion of the selected entries against `sent`, in the same dtype: the model the
+ *                 owners hold after the reply.
+ *              Every output is specified bit for bit (NaN as NaN) and depends on no grid, tile or run: the kernels
+ *              use integer atomics only, whose sums are exact.
+ *              Added without a new FA_ABI_VERSION: fa_topk_expand_device and fa_topk_encode_device with n == 0 touch
+ *              no device and answer FA_OK -- that is how a caller probes for them.
  *   Secagg stage (fa_set_secagg, fa_secagg_set_terms, fa_secagg_unmask_device, fa_secagg_mask_host,
  *              fa_secagg_quantize): the server's arithmetic of secure aggregation (Bonawitz et al., "Practical Secure
  *              Aggregation for Privacy-Preserving Machine Learning", CCS 2017).  The slots of an FA_FEDAVG part with
@@ -959,8 +987,8 @@ int fa_set_mx8(fa_ctx* ctx, int part_id, int on);
 int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags);
 /* Writes the part's device output on every GPU from host_src (n elements of the out dtype), as if a round had
  * produced it: the reference of the next relative submits (a restarted aggregator; tests).  Waits for the part's
- * pending work.  On a part with the reply stage it also sets `sent`.  FA_ERR_STATE on a part with neither
- * fa_set_mx8 nor fa_set_mx8_reply. */
+ * pending work.  On a part with the reply stage it also sets `sent`.  FA_ERR_STATE on a part with none of
+ * fa_set_mx8, fa_set_topk and fa_set_mx8_reply. */
 int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src);
 
 /* MX8 replies (the header comment, "MX8 replies"): the new model as block-scaled int8 deltas, encoded on the GPU. */
@@ -1000,6 +1028,57 @@ int fa_finalize_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags);
 int fa_copy_mx8(fa_ctx* ctx, int part_id, int8_t* q, uint8_t* e, int flags);
 /* *nan_blocks = the E = 255 blocks among the codes of the part's last reducing call (0 after a bootstrap). */
 int fa_mx8_reply_stats(fa_ctx* ctx, int part_id, uint64_t* nan_blocks);
+
+/* Top-k receipts (the header comment, "Top-k receipts"): the k largest elements of an update, expanded and selected
+ * on the GPU. */
+/* Rules 2-5 on the n given deltas, pure host arithmetic, usable without a device: idx and val get min(k, n) entries,
+ * *k_out (nullable) = min(k, n). */
+int fa_topk_encode(const float* delta, size_t n, size_t k, uint32_t* idx, float* val, size_t* k_out);
+/* The decoder, pure host arithmetic: d[i] = the delta of bucket element idx0 + i over n elements; entries outside
+ * [idx0, idx0 + n) are skipped.  FA_ERR_ARG, naming the entry, if idx is not strictly ascending. */
+int fa_topk_decode(const uint32_t* idx, const float* val, size_t k, uint64_t idx0, size_t n, float* d);
+/* The expansion on raw device pointers, on device `gpu`: d_dst[i] (n of dst_dtype) = fl(widen(d_ref[i]) + d_i), or d_i
+ * with d_ref NULL (absolute mode), over bucket elements idx0 .. idx0 + n - 1.  d_idx and d_val are the k entries to
+ * look at, the whole bucket's or a range's; entries outside the range are ignored; k == 0 is a plain convert/copy of
+ * the reference, or zeros.  Ascending order is the caller's obligation here: with unsorted or duplicate indices the
+ * values written are unspecified, but nothing is written outside d_dst[0, n) -- every entry is range-checked where
+ * it is applied.  ctx may be NULL (then `gpu` is the HIP device).  Every argument is checked before any device call:
+ * the dtypes and their pair ((dst, ref) as (in, out)), idx0 + n < 2^64, and for n > 0 null pointers and element
+ * alignment (FA_ERR_ALIGN); with n == 0 and valid arguments it returns FA_OK without touching a device.  Any element
+ * phase of d_ref and d_dst is correct; 16-byte loads and stores are used where the two phases allow a common head.
+ * d_dst must not overlap d_ref.  Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
+int fa_topk_expand_device(fa_ctx* ctx, int gpu, const uint32_t* d_idx, const float* d_val, size_t k, size_t n,
+                          uint64_t idx0, const void* d_ref, fa_dtype ref_dtype, void* d_dst, fa_dtype dst_dtype,
+                          void* hip_stream);
+/* The bytes of fa_topk_encode_device's scratch for n elements: the histogram and two counters per tile of 4096
+ * elements -- never O(n). */
+size_t fa_topk_encode_workspace(size_t n);
+/* Rules 1-6 on raw device pointers, on device `gpu`: over the n elements of d_new and d_sent (one dtype), d_idx and
+ * d_val get min(k, n) entries and, unless d_out is NULL, d_out gets g' (n elements of the same dtype).  d_out may be
+ * d_sent or d_new exactly or overlap neither (FA_ERR_ARG otherwise).  d_work: fa_topk_encode_workspace(n) bytes,
+ * 16-byte aligned, not initialised by the caller.  All launches are enqueued without a host round trip: the threshold,
+ * the count of ties and the tile offsets travel through d_work, which a later call on the same stream may reuse.  The
+ * checks, ctx == NULL, the n == 0 probe and the stream are fa_topk_expand_device's. */
+int fa_topk_encode_device(fa_ctx* ctx, int gpu, const void* d_new, fa_dtype new_dtype, const void* d_sent,
+                          fa_dtype sent_dtype, size_t n, size_t k, uint32_t* d_idx, float* d_val, void* d_out,
+                          void* d_work, void* hip_stream);
+/* Lets a part take top-k receipts of at most k_max entries (part_id >= 0; 0 = off), or sets the context default for
+ * parts defined later (part_id < 0).  It is the stage of fa_set_mx8 with a second format: admission, the reference,
+ * the refusals (FA_LITERAL, FA_SHARD_CLIENT_RS, a secagg part) and the call ordering are fa_set_mx8's, the part is
+ * never kept host-side and FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager.  A part may have both, and different owners
+ * may send different formats.  Memory: per GPU and client slot a shadow of min(k_max, cnt) * 8 bytes, rounded up to
+ * 256, allocated at the part's first fa_submit_topk; a changed k_max frees it. */
+int fa_set_topk(fa_ctx* ctx, int part_id, size_t k_max);
+/* A top-k receipt of client `client_slot`: k <= k_max entries.  flags: FA_HOST_PINNED as for fa_submit_mx8 (idx and val
+ * stay unchanged until fa_finalize* returns); FA_TOPK_ABSOLUTE = absolute mode (x = d).  Checks on the host, before
+ * anything is enqueued, that idx is strictly ascending and < n (FA_ERR_ARG naming the first bad entry; the round stays
+ * as it was), splits the entries into each GPU's element range and each piece's, enqueues the H2D of each sub-array
+ * and the expansion with that range's idx0, ordered after the part's last reducing call and before the next.  The slot
+ * then counts as the client's receipt exactly as after fa_submit.  The reference and its FA_ERR_STATE are
+ * fa_submit_mx8's; FA_ERR_STATE on a part without fa_set_topk. */
+#define FA_TOPK_ABSOLUTE 0x2
+int fa_submit_topk(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* idx, const float* val, size_t k,
+                   float weight, int flags);
 
 /* Secagg stage (the header comment, "Secagg stage"): masked uint32 sums unmasked and decoded on the GPU. */
 #define FA_SECAGG_MAX_TERMS 4096

@@ -135,6 +135,13 @@ def lib():
         "fa_finalize_mx8": (I, [P, I, P, P, I]),
         "fa_copy_mx8": (I, [P, I, P, P, I]),
         "fa_mx8_reply_stats": (I, [P, I, P]),
+        "fa_topk_encode": (I, [P, S, S, P, P, P]),
+        "fa_topk_decode": (I, [P, P, S, U64, S, P]),
+        "fa_topk_expand_device": (I, [P, I, P, P, S, S, U64, P, I, P, I, P]),
+        "fa_topk_encode_workspace": (S, [S]),
+        "fa_topk_encode_device": (I, [P, I, P, I, P, I, S, S, P, P, P, P, P]),
+        "fa_set_topk": (I, [P, I, S]),
+        "fa_submit_topk": (I, [P, I, I, P, P, S, F, I]),
         "fa_set_secagg": (I, [P, I, F]),
         "fa_secagg_set_terms": (I, [P, I, I, P, P, P]),
         "fa_secagg_unmask_device": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, P]),
@@ -509,6 +516,56 @@ def mx8_encode_device(new, sent, n, q, e, out=None, dtype=F32, sent_dtype=None, 
     check(lib().fa_mx8_encode_device(ctx.handle if ctx is not None else None, gpu, _addr(new), dtype, _addr(sent),
                                      dtype if sent_dtype is None else sent_dtype, n, int(idx0), _addr(q), _addr(e),
                                      _addr(out), flags, _stream(stream)))
+
+
+TOPK_ABSOLUTE = 0x2  # FA_TOPK_ABSOLUTE
+TOPK_TILE = 4096  # the elements of a workgroup's tile in the top-k kernels (fa_topk.hip)
+
+
+def topk_encode(delta, k):
+    """fa_topk_encode (host arithmetic, fa.h "Top-k receipts" rules 2-5): the min(k, n) entries of the fp32 deltas with
+    the largest magnitude as (idx uint32[k'], val float32[k']), ascending in idx."""
+    delta = np.ascontiguousarray(np.asarray(delta, np.float32).reshape(-1))
+    kp = min(int(k), delta.size)
+    idx, val, k_out = np.empty(kp, np.uint32), np.empty(kp, np.float32), ctypes.c_size_t(0)
+    check(lib().fa_topk_encode(delta.ctypes.data, delta.size, int(k), idx.ctypes.data, val.ctypes.data, ctypes.byref(k_out)))
+    return idx[:k_out.value], val[:k_out.value]
+
+
+def topk_decode(idx, val, n, idx0=0):
+    """fa_topk_decode (host arithmetic): the fp32 deltas of bucket elements idx0 .. idx0 + n - 1, +0 where no entry
+    lies; entries outside the range are skipped, idx that is not strictly ascending is refused."""
+    idx = np.ascontiguousarray(np.asarray(idx, np.uint32).reshape(-1))
+    val = np.ascontiguousarray(np.asarray(val, np.float32).reshape(-1))
+    if idx.size != val.size:
+        raise ValueError("%d indices and %d values" % (idx.size, val.size))
+    d = np.empty(n, np.float32)
+    check(lib().fa_topk_decode(idx.ctypes.data, val.ctypes.data, idx.size, int(idx0), n, d.ctypes.data))
+    return d
+
+
+def topk_expand_device(idx, val, k, n, dst, dst_dtype=F32, ref=None, ref_dtype=F32, idx0=0, stream=None, gpu=0, ctx=None):
+    """fa_topk_expand_device: dst[i] = ref[i] + d_i over n device-resident elements, bucket elements idx0 .. (ref None:
+    absolute mode, dst[i] = d_i), from the k device-resident entries (idx, val), of which those outside the range are
+    ignored.  Enqueued, not synchronized.  With n == 0 no device is touched: the feature probe."""
+    check(lib().fa_topk_expand_device(ctx.handle if ctx is not None else None, gpu, _addr(idx), _addr(val), int(k), n,
+                                      int(idx0), _addr(ref), ref_dtype, _addr(dst), dst_dtype, _stream(stream)))
+
+
+def topk_encode_workspace(n):
+    """fa_topk_encode_workspace: the bytes of topk_encode_device's scratch for n elements."""
+    return lib().fa_topk_encode_workspace(n)
+
+
+def topk_encode_device(new, sent, n, k, idx, val, work, out=None, dtype=F32, sent_dtype=None, stream=None, gpu=0,
+                       ctx=None):
+    """fa_topk_encode_device (fa.h "Top-k receipts", rules 1-6): over n device-resident elements of `dtype`, the
+    min(k, n) entries of fl(new - sent) into idx and val, and (out not None) g' = sent + decode(idx, val) into out, which
+    may be `sent` or `new` itself.  work: topk_encode_workspace(n) bytes of device scratch.  Enqueued, not synchronized.
+    With n == 0 no device is touched: the feature probe."""
+    check(lib().fa_topk_encode_device(ctx.handle if ctx is not None else None, gpu, _addr(new), dtype, _addr(sent),
+                                      dtype if sent_dtype is None else sent_dtype, n, int(k), _addr(idx), _addr(val),
+                                      _addr(out), _addr(work), _stream(stream)))
 
 
 SECAGG_MAX_TERMS = 4096  # FA_SECAGG_MAX_TERMS
@@ -979,6 +1036,21 @@ class Aggregator:
                                  % (part_id, n, mx8_scale_bytes(n), q.size, e.size))
         flags = (HOST_PINNED if pinned else 0) | (MX8_ABSOLUTE if absolute else 0)
         check(lib().fa_submit_mx8(self.handle, part_id, slot, q.ctypes.data, e.ctypes.data, float(weight), flags))
+
+    def set_topk(self, k_max, part=None):
+        """fa_set_topk: the part takes top-k receipts of at most k_max entries, on the stage and the reference of
+        set_mx8 (part None: the default of parts defined later); 0 switches them off."""
+        check(lib().fa_set_topk(self.handle, -1 if part is None else part, int(k_max)))
+
+    def submit_topk(self, part, slot, idx, val, weight=1.0, absolute=False, pinned=False):
+        """fa_submit_topk: the client's update against the part's last output as (idx uint32[k] ascending, val
+        float32[k]), expanded into the slot on the GPU.  pinned: views of PinnedBuffers the caller keeps unchanged until
+        finalize returns.  absolute: the values themselves, no reference."""
+        idx, val = np.ascontiguousarray(idx), np.ascontiguousarray(val)
+        if idx.dtype != np.uint32 or val.dtype != np.float32 or idx.size != val.size:
+            raise ValueError("need idx uint32 and val float32 of one length")
+        flags = (HOST_PINNED if pinned else 0) | (TOPK_ABSOLUTE if absolute else 0)
+        check(lib().fa_submit_topk(self.handle, part, slot, idx.ctypes.data, val.ctypes.data, idx.size, float(weight), flags))
 
     def set_mx8_reference(self, part_id, g):
         """fa_mx8_set_reference: the part's device output := g (n elements of the out dtype; bf16 as uint16 bits), the

@@ -272,7 +272,7 @@ struct DevArrays {
 //   opt clip noise   restart_round_plain                  the round stays    the round stays
 //   krum geomed dnc  restart_round_plain                  the round stays    the round stays (`ready` too)
 //   bulyan           ready = false                        ready = false      ready = false, if it was on
-//   mx8 reply        host_flush, restart_round_plain      nothing            the round stays
+//   mx8 topk reply   host_flush, restart_round_plain      nothing            the round stays
 //   secagg           restart_round_plain, no terms        the round stays    the round stays, the terms go
 enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kStages };
 
@@ -302,9 +302,14 @@ struct NoiseCfg {  // fa.h "Noise stage"
     uint64_t seed = 0;
     bool on() const { return stddev > 0.0f; }
 };
-struct FlagCfg {  // fa.h "MX8 receipts", "MX8 replies"
+struct FlagCfg {  // fa.h "MX8 replies"
     bool flag = false;
     bool on() const { return flag; }
+};
+struct ReceiptCfg {  // fa.h "MX8 receipts", "Top-k receipts": the compressed formats a part takes (k_max 0: no top-k)
+    bool flag = false;
+    size_t k_max = 0;
+    bool on() const { return flag || k_max > 0; }
 };
 struct SecaggCfg {  // fa.h "Secagg stage"
     float scale = 0.0f;
@@ -321,7 +326,8 @@ struct StageCfgs {
     GeomedCfg geomed;
     BulyanCfg bulyan;
     NoiseCfg noise;
-    FlagCfg mx8, reply;
+    ReceiptCfg mx8;
+    FlagCfg reply;
     SecaggCfg secagg;
     DncCfg dnc;
 };
@@ -383,11 +389,14 @@ struct NoiseStage {
 // ref: the device output holds a reference -- a reducing call left it there while the stage was on, or
 // fa_mx8_set_reference wrote it.  buf: per GPU the compressed shadows of its held slots, stride[g] bytes apart (q: cnt
 // bytes, then from eoff[g] on the scale bytes of the blocks its range touches), allocated at the first fa_submit_mx8.
+// The stage of both compressed receipt formats (cfg: MX8, top-k or both): one reference, one admission rule.  sparse:
+// per GPU the top-k shadows of its held slots, sstride[g] bytes apart (scap[g] = min(k_max, cnt) indices, then as
+// many values), allocated at the first fa_submit_topk.
 struct Mx8Stage {
-    FlagCfg cfg;
+    ReceiptCfg cfg;
     bool ref = false;
-    DevArrays buf;
-    std::vector<size_t> stride, eoff;
+    DevArrays buf, sparse;
+    std::vector<size_t> stride, eoff, sstride, scap;
     bool on() const { return cfg.on(); }
 };
 // sent: per GPU the model the owners last received, cnt elements of the out dtype (has_sent: it holds one).  codes: per

@@ -212,6 +212,21 @@ Split mx8_enc_split(const void* y, const void* sent, fa_dtype dt, uint64_t idx0,
                     const void* out, const void* out2);
 hipError_t launch_mx8_encode(const void* y, const void* sent, fa_dtype dt, uint64_t idx0, int64_t n, int8_t* q,
                              uint8_t* e, void* out, void* out2, int mode, hipStream_t s);
+// Top-k receipts (fa.h "Top-k receipts"), fa_topk.hip.  Expansion: dst[i] (dtype ddt, one rounding) := fl(widen(ref[i]) +
+// d_i), or d_i without a reference (ref null), over n elements, d_i = val[j] where idx[j] == idx0 + i among the k
+// entries and +0 elsewhere; entries outside [idx0, idx0 + n) are skipped, each is range-checked where it is applied.
+// Selection over n elements of dtype dt (rules 1-6): idx, val := the min(k, n) entries of fl(widen(y) - widen(sent)), out
+// (nullable; y or sent exactly, or apart) := g'; work: topk_workspace(n) bytes, 16-byte aligned, not initialised.
+// Any pointers of element alignment: topk_split (host-only) is the split both take, led by dst / by y.
+constexpr int kTopkTileElems = 4096;  // the elements of a workgroup's tile, in both directions
+Split topk_split(const void* lead, size_t elem, size_t n);
+size_t topk_workspace(size_t n);
+hipError_t launch_topk_expand(const uint32_t* idx, const float* val, uint64_t k, uint64_t idx0, int64_t n, const void* ref,
+                              fa_dtype rdt, void* dst, fa_dtype ddt, hipStream_t s);
+hipError_t launch_topk_encode(const void* y, const void* sent, fa_dtype dt, int64_t n, uint64_t k, uint32_t* idx,
+                              float* val, void* out, void* work, hipStream_t s);
+// Rules 2-5 on the host (fa_topk_encode): the kp <= n entries of the n deltas.
+void topk_encode_host(const float* delta, size_t n, size_t kp, uint32_t* idx, float* val);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
                        const Tuning& tu, hipStream_t s);

@@ -525,6 +525,7 @@ void free_clip(fa_ctx* ctx, Part& p) {
 }
 void free_mx8(fa_ctx* ctx, Part& p) {
     p.mx8.buf.free(ctx->gpu);
+    p.mx8.sparse.free(ctx->gpu);
     p.mx8 = Mx8Stage{};
 }
 void free_reply(fa_ctx* ctx, Part& p) {
@@ -1190,9 +1191,9 @@ int set_part_noise(fa_ctx* ctx, Part& p, const NoiseCfg& c) {
     return FA_OK;
 }
 
-// fa_set_mx8 / fa_set_mx8_reply on a part (not FA_LITERAL, not rs).  Off: what the stage allocated goes, after the
-// devices' pending work.  On, for a part without it: what this round kept host-side or chained so far goes back to the
-// plain path; the buffers come with the first fa_submit_mx8, or the first reducing call.
+// fa_set_mx8 / fa_set_topk / fa_set_mx8_reply on a part (not FA_LITERAL, not rs).  Off: what the stage allocated goes,
+// after the devices' pending work.  On, for a part without it: what this round kept host-side or chained so far goes
+// back to the plain path; the buffers come with the first fa_submit_mx8 / fa_submit_topk, or the first reducing call.
 int set_part_flag(fa_ctx* ctx, Part& p, bool reply, bool on) {
     const bool was = reply ? p.reply.on() : p.mx8.on();
     if (on == was) return FA_OK;
@@ -1202,7 +1203,25 @@ int set_part_flag(fa_ctx* ctx, Part& p, bool reply, bool on) {
         return FA_OK;
     }
     restart_round_plain(p);
-    (reply ? p.reply.cfg : p.mx8.cfg).flag = true;
+    (reply ? p.reply.cfg.flag : p.mx8.cfg.flag) = true;
+    return FA_OK;
+}
+
+// The receipt stage of a part becomes c (MX8, top-k, both or neither).  The stage itself goes on and off as above;
+// while it stays on, a format that leaves, and a k_max that changes, free that format's shadows alone.
+int set_part_receipts(fa_ctx* ctx, Part& p, const ReceiptCfg& c) {
+    const ReceiptCfg was = p.mx8.cfg;
+    if (!c.on() || !was.on()) {
+        if (int rc = set_part_flag(ctx, p, false, c.on())) return rc;
+        if (c.on()) p.mx8.cfg = c;
+        return FA_OK;
+    }
+    const bool drop_q = was.flag && !c.flag && p.mx8.buf, drop_s = was.k_max != c.k_max && p.mx8.sparse;
+    if (drop_q || drop_s)
+        if (int rc = wait_devices(ctx)) return rc;
+    if (drop_q) p.mx8.buf.free(ctx->gpu);
+    if (drop_s) p.mx8.sparse.free(ctx->gpu);
+    p.mx8.cfg = c;
     return FA_OK;
 }
 
@@ -1234,7 +1253,8 @@ int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
         case kNoise: return set_part_noise(ctx, p, c.noise);
         case kSecagg: return set_part_secagg(ctx, p, c.secagg);
         case kDnc: return set_part_select(p, p.dnc, c.dnc);
-        default: return set_part_flag(ctx, p, id == kReply, id == kReply ? c.reply.flag : c.mx8.flag);
+        case kMx8: return set_part_receipts(ctx, p, c.mx8);
+        default: return set_part_flag(ctx, p, true, c.reply.flag);
     }
 }
 
@@ -1398,7 +1418,7 @@ int submit_mx8_impl(fa_ctx* ctx, int part_id, int slot, const int8_t* q, const u
     if (rc) return rc;
     if (flags & ~(FA_HOST_PINNED | FA_MX8_ABSOLUTE)) return fail(FA_ERR_ARG, "mx8: unknown flags 0x%x", flags);
     if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
-    if (!p->mx8.on()) return fail(FA_ERR_STATE, "mx8: part %d does not take MX8 receipts (fa_set_mx8)", part_id);
+    if (!p->mx8.cfg.flag) return fail(FA_ERR_STATE, "mx8: part %d does not take MX8 receipts (fa_set_mx8)", part_id);
     if (p->n > 0 && (!q || !e)) return fail(FA_ERR_ARG, "mx8: %s is null", !q ? "q" : "e");
     const bool pinned = (flags & FA_HOST_PINNED) != 0, absolute = (flags & FA_MX8_ABSOLUTE) != 0;
     if (!absolute && !p->mx8.ref)
@@ -1434,6 +1454,87 @@ int submit_mx8_impl(fa_ctx* ctx, int part_id, int slot, const int8_t* q, const u
     });
     if (rc) return rc;
     return mark_submitted(ctx, *p, slot, weight);
+}
+
+// ------------------------------------------------------------------ top-k receipts (fa.h "Top-k receipts")
+
+// The sparse shadows of a part, allocated once per k_max: per GPU held x sstride bytes, a shadow scap[g] = min(k_max,
+// cnt) indices followed by as many values.  On failure the part keeps the stage.
+int ensure_topk_buf(fa_ctx* ctx, Part& p) {
+    Mx8Stage& s = p.mx8;
+    if (s.sparse) return FA_OK;
+    s.scap.clear();
+    s.sstride.clear();
+    for (size_t g = 0; g < (size_t)ctx->G; ++g) {
+        s.scap.push_back(std::min(s.cfg.k_max, p.cnt[g]));
+        s.sstride.push_back((s.scap[g] * 8 + 255) / 256 * 256);
+    }
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.sstride[g]); };
+    const int g = s.sparse.alloc(ctx->gpu, bytes);
+    if (g < 0) return FA_OK;
+    return fail(FA_ERR_NOMEM, "topk: shadow alloc of %zu B failed on GPU %zu", bytes((size_t)g), (size_t)g);
+}
+
+int submit_topk_impl(fa_ctx* ctx, int part_id, int slot, const uint32_t* idx, const float* val, size_t k, float weight,
+                     int flags) {
+    Trace tr("fa_submit_topk part %d slot %d", part_id, slot);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (flags & ~(FA_HOST_PINNED | FA_TOPK_ABSOLUTE)) return fail(FA_ERR_ARG, "topk: unknown flags 0x%x", flags);
+    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    if (!p->mx8.cfg.k_max) return fail(FA_ERR_STATE, "topk: part %d does not take top-k receipts (fa_set_topk)", part_id);
+    if (k > p->mx8.cfg.k_max) return fail(FA_ERR_ARG, "topk: %zu entries, part %d takes at most %zu (fa_set_topk)", k, part_id, p->mx8.cfg.k_max);
+    if (k && (!idx || !val)) return fail(FA_ERR_ARG, "topk: %s is null", !idx ? "idx" : "val");
+    if (k && (uint64_t)p->n > (1ull << 32)) return fail(FA_ERR_ARG, "topk: part %d holds more than 2^32 elements", part_id);
+    for (size_t j = 0; j < k; ++j) {
+        if ((uint64_t)idx[j] >= (uint64_t)p->n) return fail(FA_ERR_ARG, "topk: idx[%zu] = %u, the bucket holds %zu elements", j, idx[j], p->n);
+        if (j && idx[j] <= idx[j - 1])
+            return fail(FA_ERR_ARG, "topk: idx[%zu] = %u after idx[%zu] = %u: not strictly ascending", j, idx[j], j - 1, idx[j - 1]);
+    }
+    const bool pinned = (flags & FA_HOST_PINNED) != 0, absolute = (flags & FA_TOPK_ABSOLUTE) != 0;
+    if (!absolute && !p->mx8.ref)
+        return fail(FA_ERR_STATE, "topk: part %d has no reference (no round reduced with the stage on, no "
+                                  "fa_mx8_set_reference): send a full receipt, or FA_TOPK_ABSOLUTE", part_id);
+    if ((rc = ensure_topk_buf(ctx, *p))) return rc;
+    if ((rc = host_flush(ctx, *p))) return rc;  // none is kept while the stage is on; the plain path from here on
+    const auto first_at = [&](size_t e) { return (size_t)(std::lower_bound(idx, idx + k, (uint64_t)e, [](uint32_t a, uint64_t b) { return (uint64_t)a < b; }) - idx); };
+    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        const size_t off = p->off[(size_t)g], cnt = p->cnt[(size_t)g];
+        if (cnt == 0) return FA_OK;
+        // after the part's last reducing call: it read the slot and wrote the reference
+        if (hipStream_t ds = p->done_stream[(size_t)g]) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(r.copy, p->done[(size_t)g], 0));
+        }
+        const size_t a = first_at(off), b = first_at(off + cnt);  // the GPU's entries: b - a <= min(k_max, cnt)
+        char* di = p->mx8.sparse.at((size_t)g) + (size_t)(slot - p->c0[(size_t)g]) * p->mx8.sstride[(size_t)g];
+        char* dv = di + p->mx8.scap[(size_t)g] * 4;
+        ++r.copy_gen;  // the next reducing call waits for the copy stream: the copies and the expansion
+        int rc2 = mx8_h2d(r, di, reinterpret_cast<const char*>(idx + a), (b - a) * 4, pinned);
+        if (!rc2) rc2 = mx8_h2d(r, dv, reinterpret_cast<const char*>(val + a), (b - a) * 4, pinned);
+        if (rc2) return rc2;
+        for (int j = 0; j < p->npiece[(size_t)g]; ++j) {
+            const size_t lo = piece_lo(*p, g, j), pc = piece_cnt(*p, g, j);
+            const size_t pa = first_at(off + lo) - a, pb = first_at(off + lo + pc) - a;
+            const void* ref = absolute ? nullptr : static_cast<const char*>(p->dout[(size_t)g]) + lo * dsize(p->out);
+            FA_HIP(fa::launch_topk_expand(reinterpret_cast<const uint32_t*>(di) + pa, reinterpret_cast<const float*>(dv) + pa,
+                                          (uint64_t)(pb - pa), (uint64_t)(off + lo), (int64_t)pc, ref, p->out,
+                                          piece_ptr(*p, g, slot, j), p->in, r.copy));
+        }
+        return FA_OK;
+    });
+    if (rc) return rc;
+    return mark_submitted(ctx, *p, slot, weight);
+}
+
+// The receipt formats a fa_set_mx8 / fa_set_topk starts from: the part's own, or the context default's.
+ReceiptCfg receipts_of(fa_ctx* ctx, int part_id) {
+    if (!ctx) return ReceiptCfg{};
+    const auto it = ctx->parts.find(part_id);
+    return part_id >= 0 && it != ctx->parts.end() ? it->second.mx8.cfg : ctx->defaults.mx8;
 }
 
 }  // namespace fah
@@ -2061,8 +2162,23 @@ int fa_mx8_expand_device(fa_ctx* ctx, int gpu, const int8_t* d_q, const uint8_t*
 int fa_set_mx8(fa_ctx* ctx, int part_id, int on) {
     g_err.clear();
     StageCfgs c = requested(ctx);
+    c.mx8 = receipts_of(ctx, part_id);
     c.mx8.flag = on != 0;
     return set_stage(ctx, part_id, kMx8, c);
+}
+
+int fa_set_topk(fa_ctx* ctx, int part_id, size_t k_max) {
+    g_err.clear();
+    StageCfgs c = requested(ctx);
+    c.mx8 = receipts_of(ctx, part_id);
+    c.mx8.k_max = k_max;
+    return set_stage(ctx, part_id, kMx8, c);
+}
+
+int fa_submit_topk(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* idx, const float* val, size_t k, float weight,
+                   int flags) {
+    g_err.clear();
+    return submit_topk_impl(ctx, part_id, client_slot, idx, val, k, weight, flags);
 }
 
 int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags) {
@@ -2076,7 +2192,7 @@ int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
     if (int rc = check_part(ctx, part_id, &p)) return rc;
     if (!p->mx8.on() && !p->reply.on())
         return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
-                                  "(fa_set_mx8_reply)", part_id);
+                                  "(fa_set_mx8_reply), nor takes top-k receipts (fa_set_topk)", part_id);
     if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
     if (int rc = wait_devices(ctx)) return rc;  // the part's pending work, on whatever stream
     if (p->reply.on())
