@@ -415,6 +415,37 @@
  *              use integer atomics only, whose sums are exact.
  *              Added without a new FA_ABI_VERSION: fa_topk_expand_device and fa_topk_encode_device with n == 0 touch
  *              no device and answer FA_OK -- that is how a caller probes for them.
+ *   Low-rank receipts (fa_set_lowrank, fa_submit_lowrank, fa_lowrank_expand_device, fa_lowrank_len, fa_lowrank_decode,
+ *              fa_lowrank_check, fa_lowrank_plan_bytes, fa_lowrank_plan_build): the third common way to shrink an update.
+ *              The update of a weight matrix M (rows x cols) arrives as P (rows x r) and Q (cols x r) with M ~ P Q^T:
+ *              PowerSGD (Vogels et al., NeurIPS 2019), or the factors a federated LoRA owner trains directly, whose
+ *              exact aggregate is the weighted sum of the products, not the product of averaged factors.  As with
+ *              MX8 and top-k receipts a kernel rebuilds the ordinary slot x = g + d -- here on the matrix unit -- and
+ *              everything downstream sees an ordinary receipt; different owners of a round may use different r.
+ *              Part table.  A part that takes low-rank receipts has a table of M matrices, fa_lowrank_mat {off, rows,
+ *              cols}: rows, cols >= 1; entries ascend by off, do not overlap and satisfy off + rows * cols <= n.
+ *              Matrix j is elements off_j + a * cols_j + b of the whole bucket, row-major -- a named_parameters()
+ *              tensor of shape [rows, ...] flattened.  Element indices are positions in the whole bucket, never
+ *              within a shard or a piece.  `rest` = the elements covered by no matrix (biases, norm layers, matrices
+ *              too small to be worth factoring), in ascending order.
+ *              Receipt.  One rank r, 1 <= r <= r_max <= FA_LOWRANK_MAX_RANK, and one fp32 array f of
+ *              fa_lowrank_len(mats, M, n, r) = r * sum_j (rows_j + cols_j) + |rest| values: for each matrix in table
+ *              order P_j (rows_j x r, row-major) then Q_j (cols_j x r, row-major), then the |rest| dense deltas.
+ *              Decode (fa_lowrank_decode, pure host arithmetic):
+ *              1. For a covered element, S = sum_{t<r} (double)P_j[a,t] * (double)Q_j[b,t].  Every product is exact
+ *                 in fp64.  The order and grouping of the fp64 adds is NOT specified, the four-term sum inside a
+ *                 matrix instruction included; whatever the order, |S - exact| <= r 2^-53 sum_t |p q|.
+ *              2. d = fl32(S), one rounding to nearest-even, subnormals kept.  The host decoder adds in ascending
+ *                 t.  Kernel and decoder agree bit for bit wherever the partial sums are exact; elsewhere they
+ *                 differ by at most one fp32 ulp, and only when S lies that close to a rounding boundary.
+ *              3. For a `rest` element, d is its value.
+ *              4. NaN and inf follow IEEE rules (0 * inf is NaN).  A non-finite P_j[a,.] reaches row a only, a
+ *                 non-finite Q_j[b,.] column b only.
+ *              Expansion is decode rule 3 of MX8 receipts, unchanged: x_i = fl32(widen(g_i) + d_i), one IEEE add; a
+ *              16-bit slot stores x_i rounded once more to nearest-even; without a reference (absolute mode)
+ *              x_i = d_i, rounded the same way; (slot, ref) pairs are the (in, out) pairs below.
+ *              Added without a new FA_ABI_VERSION: fa_lowrank_expand_device with cnt == 0 touches no device and
+ *              answers FA_OK -- that is how a caller probes for it.
  *   Secagg stage (fa_set_secagg, fa_secagg_set_terms, fa_secagg_unmask_device, fa_secagg_mask_host,
  *              fa_secagg_quantize): the server's arithmetic of secure aggregation (Bonawitz et al., "Practical Secure
  *              Aggregation for Privacy-Preserving Machine Learning", CCS 2017).  The slots of an FA_FEDAVG part with
@@ -988,7 +1019,7 @@ int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, co
 /* Writes the part's device output on every GPU from host_src (n elements of the out dtype), as if a round had
  * produced it: the reference of the next relative submits (a restarted aggregator; tests).  Waits for the part's
  * pending work.  On a part with the reply stage it also sets `sent`.  FA_ERR_STATE on a part with none of
- * fa_set_mx8, fa_set_topk and fa_set_mx8_reply. */
+ * fa_set_mx8, fa_set_topk, fa_set_lowrank and fa_set_mx8_reply. */
 int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src);
 
 /* MX8 replies (the header comment, "MX8 replies"): the new model as block-scaled int8 deltas, encoded on the GPU. */
@@ -1079,6 +1110,65 @@ int fa_set_topk(fa_ctx* ctx, int part_id, size_t k_max);
 #define FA_TOPK_ABSOLUTE 0x2
 int fa_submit_topk(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* idx, const float* val, size_t k,
                    float weight, int flags);
+
+/* Low-rank receipts (the header comment, "Low-rank receipts"): factor pairs expanded on the GPU by fp64 MFMA. */
+#define FA_LOWRANK_MAX_RANK 64
+typedef struct {
+    uint64_t off;  /* the matrix's first element in the whole bucket */
+    uint32_t rows; /* >= 1 */
+    uint32_t cols; /* >= 1; element (a, b) is off + a * cols + b */
+} fa_lowrank_mat;
+/* The table rules against a bucket of n elements, pure host arithmetic: FA_ERR_ARG naming the first bad entry (no rows
+ * or columns, descending, overlapping, beyond n).  Every function below that takes a table checks it so. */
+int fa_lowrank_check(const fa_lowrank_mat* mats, size_t M, size_t n);
+/* The fp32 values of a receipt of rank r: r * sum_j (rows_j + cols_j) + |rest|.  0 with fa_last_error set for a bad
+ * table or a rank outside 1 .. FA_LOWRANK_MAX_RANK. */
+size_t fa_lowrank_len(const fa_lowrank_mat* mats, size_t M, size_t n, int r);
+/* The decoder, pure host arithmetic: d[i] = the delta of bucket element idx0 + i over cnt elements (idx0 + cnt <= n),
+ * the fp64 sums added in ascending t. */
+int fa_lowrank_decode(const fa_lowrank_mat* mats, size_t M, size_t n, const float* f, int r, uint64_t idx0, size_t cnt,
+                      float* d);
+/* The plan of one launch over bucket elements [idx0, idx0 + cnt), host-only: the output tiles of every matrix the
+ * range meets and the rest elements against their offsets in f, an opaque blob that the caller puts into device
+ * memory (8-byte aligned).  It does not depend on r.  fa_lowrank_plan_bytes: its size, a multiple of 32 (0 with
+ * fa_last_error set for a bad table or range); fa_lowrank_plan_build writes it, plan_bytes being exactly that size. */
+size_t fa_lowrank_plan_bytes(const fa_lowrank_mat* mats, size_t M, size_t n, uint64_t idx0, size_t cnt);
+int fa_lowrank_plan_build(const fa_lowrank_mat* mats, size_t M, size_t n, uint64_t idx0, size_t cnt, void* plan,
+                          size_t plan_bytes);
+/* The expansion on raw device pointers, on device `gpu`: d_dst[i] (cnt of dst_dtype) = fl(widen(d_ref[i]) + d_i), or d_i
+ * with d_ref NULL (absolute mode), over bucket elements idx0 .. idx0 + cnt - 1, from the whole receipt d_f (rank r) and
+ * the plan built for exactly this range (d_plan, plan_bytes); a plan of another range leaves d_dst untouched.  One
+ * launch: a workgroup per output tile and per chunk of rest elements; every store is checked against the tile, the
+ * matrix and the range, so nothing is written outside d_dst[0, cnt).  ctx may be NULL (then `gpu` is the HIP device).
+ * Every argument is checked before any device call: the dtypes and their pair ((dst, ref) as (in, out)), idx0 + cnt <
+ * 2^64, and for cnt > 0 the rank, the plan size, null pointers, alignment (FA_ERR_ALIGN: d_plan 8 bytes, d_f 4, d_ref
+ * and d_dst their element) and that d_dst does not overlap d_ref (FA_ERR_ARG); with cnt == 0 and valid arguments it
+ * returns FA_OK without touching a device.  Any element phase of d_ref and d_dst is correct; 16-byte loads and stores
+ * are used where the two phases agree.  Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null
+ * stream). */
+int fa_lowrank_expand_device(fa_ctx* ctx, int gpu, const void* d_plan, size_t plan_bytes, const float* d_f, int r,
+                             uint64_t idx0, size_t cnt, const void* d_ref, fa_dtype ref_dtype, void* d_dst,
+                             fa_dtype dst_dtype, void* hip_stream);
+/* Lets a part take low-rank receipts of rank at most r_max over the table mats[0, M) (copied); M == 0 switches them
+ * off.  part_id < 0 is refused (FA_ERR_ARG): a table belongs to one part's layout, there is no context default.  It is
+ * the stage of fa_set_mx8 with a third format: admission, the reference, the refusals (FA_LITERAL, FA_SHARD_CLIENT_RS, a
+ * secagg part) and the call ordering are fa_set_mx8's, the part is never kept host-side and FA_ACCUMULATE_ON_ARRIVAL
+ * leaves it non-eager.  A part may take all three formats, and different owners may send different ones.  The plans of
+ * every GPU's range and piece are built and uploaded here.  Memory: per GPU and client slot a shadow of
+ * fa_lowrank_len(.., r_max) floats, rounded up to 256 bytes, allocated at the part's first fa_submit_lowrank; a changed
+ * table or r_max frees it. */
+int fa_set_lowrank(fa_ctx* ctx, int part_id, const fa_lowrank_mat* mats, size_t M, int r_max);
+/* A low-rank receipt of client `client_slot`: rank r <= r_max and f, len values, where len must be
+ * fa_lowrank_len(.., r) (FA_ERR_ARG otherwise, as for r; the round stays as it was).  flags:
+ * FA_HOST_PINNED as for fa_submit_mx8 (f stays unchanged until fa_finalize* returns); FA_LOWRANK_ABSOLUTE = absolute
+ * mode (x = d).  Copies f to every GPU that holds part of the slot -- a shard needs the rows and columns of every tile
+ * it touches, and factors are small -- and enqueues the expansion per GPU and per piece with that range's plan, ordered
+ * after the part's last reducing call and before the next.  The slot then counts as the client's receipt exactly as
+ * after fa_submit.  The reference and its FA_ERR_STATE are fa_submit_mx8's; FA_ERR_STATE on a part without
+ * fa_set_lowrank. */
+#define FA_LOWRANK_ABSOLUTE 0x2
+int fa_submit_lowrank(fa_ctx* ctx, int part_id, int client_slot, const float* f, size_t len, int r, float weight,
+                      int flags);
 
 /* Secagg stage (the header comment, "Secagg stage"): masked uint32 sums unmasked and decoded on the GPU. */
 #define FA_SECAGG_MAX_TERMS 4096

@@ -142,6 +142,14 @@ def lib():
         "fa_topk_encode_device": (I, [P, I, P, I, P, I, S, S, P, P, P, P, P]),
         "fa_set_topk": (I, [P, I, S]),
         "fa_submit_topk": (I, [P, I, I, P, P, S, F, I]),
+        "fa_lowrank_check": (I, [P, S, S]),
+        "fa_lowrank_len": (S, [P, S, S, I]),
+        "fa_lowrank_decode": (I, [P, S, S, P, I, U64, S, P]),
+        "fa_lowrank_plan_bytes": (S, [P, S, S, U64, S]),
+        "fa_lowrank_plan_build": (I, [P, S, S, U64, S, P, S]),
+        "fa_lowrank_expand_device": (I, [P, I, P, S, P, I, U64, S, P, I, P, I, P]),
+        "fa_set_lowrank": (I, [P, I, P, S, I]),
+        "fa_submit_lowrank": (I, [P, I, I, P, S, I, F, I]),
         "fa_set_secagg": (I, [P, I, F]),
         "fa_secagg_set_terms": (I, [P, I, I, P, P, P]),
         "fa_secagg_unmask_device": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, P]),
@@ -566,6 +574,110 @@ def topk_encode_device(new, sent, n, k, idx, val, work, out=None, dtype=F32, sen
     check(lib().fa_topk_encode_device(ctx.handle if ctx is not None else None, gpu, _addr(new), dtype, _addr(sent),
                                       dtype if sent_dtype is None else sent_dtype, n, int(k), _addr(idx), _addr(val),
                                       _addr(out), _addr(work), _stream(stream)))
+
+
+LOWRANK_ABSOLUTE = 0x2  # FA_LOWRANK_ABSOLUTE
+LOWRANK_MAX_RANK = 64  # FA_LOWRANK_MAX_RANK
+LOWRANK_MAT = np.dtype([("off", np.uint64), ("rows", np.uint32), ("cols", np.uint32)])  # fa_lowrank_mat
+
+
+def _lowrank_table(mats):
+    """A table as a contiguous array of fa_lowrank_mat: a LOWRANK_MAT array, or rows of (off, rows, cols)."""
+    if isinstance(mats, np.ndarray) and mats.dtype == LOWRANK_MAT:
+        return np.ascontiguousarray(mats.reshape(-1))
+    t = np.zeros(len(mats), LOWRANK_MAT)
+    for j, (off, rows, cols) in enumerate(mats):
+        t[j] = (off, rows, cols)
+    return t
+
+
+def lowrank_mats(shapes, min_elems=0):
+    """A table from a list of tensor shapes laid out back to back, as named_parameters() flattens them: [shape[0],
+    prod(shape[1:])] for tensors of at least two dimensions and min_elems elements; the others are rest.  Returns (table,
+    n)."""
+    rows, off = [], 0
+    for shape in shapes:
+        size = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
+        if len(shape) >= 2 and size >= max(1, min_elems):
+            rows.append((off, int(shape[0]), size // int(shape[0])))
+        off += size
+    return _lowrank_table(rows), off
+
+
+def lowrank_check(mats, n):
+    """fa_lowrank_check: FaError(ERR_ARG) naming the first entry that breaks the table rules for a bucket of n elements."""
+    t = _lowrank_table(mats)
+    check(lib().fa_lowrank_check(t.ctypes.data, t.size, n))
+
+
+def lowrank_len(mats, n, r):
+    """fa_lowrank_len: the fp32 values of a receipt of rank r over the table: r * sum (rows + cols) + |rest|."""
+    t = _lowrank_table(mats)
+    size = lib().fa_lowrank_len(t.ctypes.data, t.size, n, int(r))
+    if size == 0:
+        err = lib().fa_last_error().decode(errors="replace")
+        if err:
+            raise FaError(ERR_ARG, err)
+    return size
+
+
+def lowrank_decode(f, mats, n, r, idx0=0, cnt=None):
+    """fa_lowrank_decode (host arithmetic, fa.h "Low-rank receipts"): the fp32 deltas of bucket elements idx0 .. idx0 +
+    cnt - 1 (cnt None: to the end) from the receipt f of rank r."""
+    t = _lowrank_table(mats)
+    f = np.ascontiguousarray(np.asarray(f, np.float32).reshape(-1))
+    if f.size != lowrank_len(t, n, r):
+        raise ValueError("%d values, a receipt of rank %d has %d" % (f.size, r, lowrank_len(t, n, r)))
+    cnt = n - idx0 if cnt is None else cnt
+    d = np.empty(cnt, np.float32)
+    check(lib().fa_lowrank_decode(t.ctypes.data, t.size, n, f.ctypes.data, int(r), int(idx0), cnt, d.ctypes.data))
+    return d
+
+
+def lowrank_plan(mats, n, idx0=0, cnt=None):
+    """fa_lowrank_plan_bytes / fa_lowrank_plan_build: the plan of one launch over bucket elements [idx0, idx0 + cnt) as a
+    uint8 array, for the caller to put into device memory."""
+    t = _lowrank_table(mats)
+    cnt = n - idx0 if cnt is None else cnt
+    size = lib().fa_lowrank_plan_bytes(t.ctypes.data, t.size, n, int(idx0), cnt)
+    if size == 0:
+        raise FaError(ERR_ARG, lib().fa_last_error().decode(errors="replace"))
+    plan = np.zeros(size, np.uint8)
+    check(lib().fa_lowrank_plan_build(t.ctypes.data, t.size, n, int(idx0), cnt, plan.ctypes.data, size))
+    return plan
+
+
+def lowrank_expand_device(plan, f, r, cnt, dst, dst_dtype=F32, ref=None, ref_dtype=F32, idx0=0, plan_bytes=None,
+                          stream=None, gpu=0, ctx=None):
+    """fa_lowrank_expand_device: dst[i] = ref[i] + d_i over cnt device-resident elements, bucket elements idx0 .. (ref
+    None: absolute mode, dst[i] = d_i), from the device-resident receipt f of rank r and the device-resident plan of
+    exactly that range (lowrank_plan).  Enqueued, not synchronized.  With cnt == 0 no device is touched: the feature
+    probe."""
+    if plan_bytes is None:
+        plan_bytes = plan.numel() * plan.element_size() if hasattr(plan, "numel") else getattr(plan, "nbytes", 0)
+    check(lib().fa_lowrank_expand_device(ctx.handle if ctx is not None else None, gpu, _addr(plan), int(plan_bytes),
+                                         _addr(f), int(r), int(idx0), cnt, _addr(ref), ref_dtype, _addr(dst), dst_dtype,
+                                         _stream(stream)))
+
+
+def lowrank_encode(delta, mats, r):
+    """The owner's side in numpy, not specified bit for bit (any f is valid input): per matrix of the table a rank-r
+    truncated SVD of its block of the fp32 deltas, P = U_r S_r and Q = V_r (zero columns beyond the matrix's own rank),
+    then the rest elements copied.  LoRA owners bring their own factors instead."""
+    t = _lowrank_table(mats)
+    delta = np.ascontiguousarray(np.asarray(delta, np.float32).reshape(-1))
+    lowrank_check(t, delta.size)
+    covered = np.zeros(delta.size, bool)
+    out = []
+    for off, rows, cols in t.tolist():
+        covered[off:off + rows * cols] = True
+        u, s, vt = np.linalg.svd(delta[off:off + rows * cols].reshape(rows, cols).astype(np.float64), full_matrices=False)
+        p, q = np.zeros((rows, r), np.float32), np.zeros((cols, r), np.float32)
+        k = min(r, s.size)
+        p[:, :k] = u[:, :k] * s[:k]
+        q[:, :k] = vt[:k].T
+        out += [p.reshape(-1), q.reshape(-1)]
+    return np.concatenate(out + [delta[~covered]]).astype(np.float32)
 
 
 SECAGG_MAX_TERMS = 4096  # FA_SECAGG_MAX_TERMS
@@ -1051,6 +1163,22 @@ class Aggregator:
             raise ValueError("need idx uint32 and val float32 of one length")
         flags = (HOST_PINNED if pinned else 0) | (TOPK_ABSOLUTE if absolute else 0)
         check(lib().fa_submit_topk(self.handle, part, slot, idx.ctypes.data, val.ctypes.data, idx.size, float(weight), flags))
+
+    def set_lowrank(self, part, mats, r_max):
+        """fa_set_lowrank: the part takes low-rank receipts of rank at most r_max over the table (lowrank_mats, or rows
+        of (off, rows, cols)), on the stage and the reference of set_mx8; an empty table switches them off."""
+        t = _lowrank_table(mats)
+        check(lib().fa_set_lowrank(self.handle, part, t.ctypes.data, t.size, int(r_max)))
+
+    def submit_lowrank(self, part, slot, f, r, weight=1.0, absolute=False, pinned=False):
+        """fa_submit_lowrank: the client's update against the part's last output as the fp32 receipt f of rank r (per
+        matrix P then Q, then the rest), expanded into the slot on the GPU.  pinned: a view of a PinnedBuffer the caller
+        keeps unchanged until finalize returns.  absolute: the deltas themselves, no reference."""
+        f = np.ascontiguousarray(f)
+        if f.dtype != np.float32:
+            raise ValueError("need f float32")
+        flags = (HOST_PINNED if pinned else 0) | (LOWRANK_ABSOLUTE if absolute else 0)
+        check(lib().fa_submit_lowrank(self.handle, part, slot, f.ctypes.data, f.size, int(r), float(weight), flags))
 
     def set_mx8_reference(self, part_id, g):
         """fa_mx8_set_reference: the part's device output := g (n elements of the out dtype; bf16 as uint16 bits), the

@@ -272,7 +272,7 @@ struct DevArrays {
 //   opt clip noise   restart_round_plain                  the round stays    the round stays
 //   krum geomed dnc  restart_round_plain                  the round stays    the round stays (`ready` too)
 //   bulyan           ready = false                        ready = false      ready = false, if it was on
-//   mx8 topk reply   host_flush, restart_round_plain      nothing            the round stays
+//   receipts reply   host_flush, restart_round_plain      nothing            the round stays
 //   secagg           restart_round_plain, no terms        the round stays    the round stays, the terms go
 enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kStages };
 
@@ -306,10 +306,19 @@ struct FlagCfg {  // fa.h "MX8 replies"
     bool flag = false;
     bool on() const { return flag; }
 };
-struct ReceiptCfg {  // fa.h "MX8 receipts", "Top-k receipts": the compressed formats a part takes (k_max 0: no top-k)
+// fa.h "MX8 receipts", "Top-k receipts", "Low-rank receipts": the compressed formats a part takes (k_max 0: no top-k;
+// no matrices: no low-rank, which a context default never has).
+struct ReceiptCfg {
     bool flag = false;
     size_t k_max = 0;
-    bool on() const { return flag || k_max > 0; }
+    std::vector<fa_lowrank_mat> mats;
+    int r_max = 0;
+    bool lowrank() const { return !mats.empty(); }
+    bool same_lowrank(const ReceiptCfg& o) const {
+        return r_max == o.r_max && mats.size() == o.mats.size() &&
+               (mats.empty() || !std::memcmp(mats.data(), o.mats.data(), mats.size() * sizeof(fa_lowrank_mat)));
+    }
+    bool on() const { return flag || k_max > 0 || lowrank(); }
 };
 struct SecaggCfg {  // fa.h "Secagg stage"
     float scale = 0.0f;
@@ -391,12 +400,17 @@ struct NoiseStage {
 // bytes, then from eoff[g] on the scale bytes of the blocks its range touches), allocated at the first fa_submit_mx8.
 // The stage of both compressed receipt formats (cfg: MX8, top-k or both): one reference, one admission rule.  sparse:
 // per GPU the top-k shadows of its held slots, sstride[g] bytes apart (scap[g] = min(k_max, cnt) indices, then as
-// many values), allocated at the first fa_submit_topk.
+// many values), allocated at the first fa_submit_topk.  plan: per GPU the low-rank plans of its pieces back to back,
+// piece j at plan_at[g][j] with plan_len[g][j] bytes, built and uploaded by fa_set_lowrank; factors: per GPU the
+// low-rank shadows of its held slots, fstride bytes apart (a whole receipt of rank r_max), allocated at the first
+// fa_submit_lowrank.
 struct Mx8Stage {
     ReceiptCfg cfg;
     bool ref = false;
-    DevArrays buf, sparse;
+    DevArrays buf, sparse, plan, factors;
     std::vector<size_t> stride, eoff, sstride, scap;
+    std::vector<std::vector<size_t>> plan_at, plan_len;
+    size_t fstride = 0;
     bool on() const { return cfg.on(); }
 };
 // sent: per GPU the model the owners last received, cnt elements of the out dtype (has_sent: it holds one).  codes: per

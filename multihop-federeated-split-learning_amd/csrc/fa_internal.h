@@ -227,6 +227,19 @@ hipError_t launch_topk_encode(const void* y, const void* sent, fa_dtype dt, int6
                               float* val, void* out, void* work, hipStream_t s);
 // Rules 2-5 on the host (fa_topk_encode): the kp <= n entries of the n deltas.
 void topk_encode_host(const float* delta, size_t n, size_t kp, uint32_t* idx, float* val);
+// Low-rank receipts (fa.h "Low-rank receipts"), fa_lowrank.hip.  The host side: lowrank_check names the first entry
+// that breaks the table rules (null: none; *bad its index), the others take a checked table.  lowrank_plan_build
+// writes lowrank_plan_bytes bytes: the plan of one launch over bucket elements [idx0, idx0 + cnt).  Expansion: dst[i]
+// (dtype ddt, one rounding) := fl(widen(ref[i]) + d_i), or d_i with ref null, over cnt elements from the whole receipt f
+// of rank r and the plan of exactly that range, both in device memory; every store is checked against [0, cnt).
+const char* lowrank_check(const fa_lowrank_mat* mats, size_t M, uint64_t n, size_t* bad);
+uint64_t lowrank_len(const fa_lowrank_mat* mats, size_t M, uint64_t n, int r);
+size_t lowrank_plan_bytes(const fa_lowrank_mat* mats, size_t M, uint64_t n, uint64_t idx0, uint64_t cnt);
+void lowrank_plan_build(const fa_lowrank_mat* mats, size_t M, uint64_t n, uint64_t idx0, uint64_t cnt, void* plan);
+void lowrank_decode_host(const fa_lowrank_mat* mats, size_t M, uint64_t n, const float* f, int r, uint64_t idx0,
+                         uint64_t cnt, float* d);
+hipError_t launch_lowrank_expand(const void* plan, size_t plan_bytes, const float* f, int r, uint64_t idx0, int64_t cnt,
+                                 const void* ref, fa_dtype rdt, void* dst, fa_dtype ddt, hipStream_t s);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
                        const Tuning& tu, hipStream_t s);

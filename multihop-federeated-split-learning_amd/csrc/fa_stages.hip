@@ -526,6 +526,8 @@ void free_clip(fa_ctx* ctx, Part& p) {
 void free_mx8(fa_ctx* ctx, Part& p) {
     p.mx8.buf.free(ctx->gpu);
     p.mx8.sparse.free(ctx->gpu);
+    p.mx8.plan.free(ctx->gpu);
+    p.mx8.factors.free(ctx->gpu);
     p.mx8 = Mx8Stage{};
 }
 void free_reply(fa_ctx* ctx, Part& p) {
@@ -1191,9 +1193,10 @@ int set_part_noise(fa_ctx* ctx, Part& p, const NoiseCfg& c) {
     return FA_OK;
 }
 
-// fa_set_mx8 / fa_set_topk / fa_set_mx8_reply on a part (not FA_LITERAL, not rs).  Off: what the stage allocated goes,
-// after the devices' pending work.  On, for a part without it: what this round kept host-side or chained so far goes
-// back to the plain path; the buffers come with the first fa_submit_mx8 / fa_submit_topk, or the first reducing call.
+// fa_set_mx8 / fa_set_topk / fa_set_lowrank / fa_set_mx8_reply on a part (not FA_LITERAL, not rs).  Off: what the stage
+// allocated goes, after the devices' pending work.  On, for a part without it: what this round kept host-side or chained
+// so far goes back to the plain path; the buffers come with the first fa_submit_mx8 / fa_submit_topk /
+// fa_submit_lowrank, or the first reducing call.
 int set_part_flag(fa_ctx* ctx, Part& p, bool reply, bool on) {
     const bool was = reply ? p.reply.on() : p.mx8.on();
     if (on == was) return FA_OK;
@@ -1207,21 +1210,63 @@ int set_part_flag(fa_ctx* ctx, Part& p, bool reply, bool on) {
     return FA_OK;
 }
 
-// The receipt stage of a part becomes c (MX8, top-k, both or neither).  The stage itself goes on and off as above;
-// while it stays on, a format that leaves, and a k_max that changes, free that format's shadows alone.
+// The low-rank plans of a part with the table in its config: per GPU one allocation with the plan of every piece's
+// range, uploaded with a plain copy (a setter is no hot path).
+int upload_lowrank_plans(fa_ctx* ctx, Part& p) {
+    Mx8Stage& s = p.mx8;
+    const std::vector<fa_lowrank_mat>& m = s.cfg.mats;
+    std::vector<std::vector<char>> blob((size_t)ctx->G);
+    s.plan_at.assign((size_t)ctx->G, {});
+    s.plan_len.assign((size_t)ctx->G, {});
+    for (int g = 0; g < ctx->G; ++g)
+        for (int j = 0; j < p.npiece[(size_t)g] && p.cnt[(size_t)g]; ++j) {
+            const uint64_t i0 = p.off[(size_t)g] + piece_lo(p, g, j), pc = piece_cnt(p, g, j);
+            const size_t at = blob[(size_t)g].size(), len = fa::lowrank_plan_bytes(m.data(), m.size(), p.n, i0, pc);
+            blob[(size_t)g].resize(at + len);
+            fa::lowrank_plan_build(m.data(), m.size(), p.n, i0, pc, blob[(size_t)g].data() + at);
+            s.plan_at[(size_t)g].push_back(at);
+            s.plan_len[(size_t)g].push_back(len);
+        }
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, blob[g].size()); };
+    const int bad = s.plan.alloc(ctx->gpu, bytes);
+    if (bad >= 0) return fail(FA_ERR_NOMEM, "lowrank: plan alloc of %zu B failed on GPU %d", bytes((size_t)bad), bad);
+    for (size_t g = 0; g < (size_t)ctx->G; ++g) {
+        DeviceGuard dg(ctx->gpu[g].dev);
+        if (!blob[g].empty()) FA_HIP(hipMemcpy(s.plan.at(g), blob[g].data(), blob[g].size(), hipMemcpyHostToDevice));
+    }
+    return FA_OK;
+}
+
+// The receipt stage of a part becomes c (any of MX8, top-k and low-rank, or none).  The stage itself goes on and off as
+// above; while it stays on, a format that leaves, a k_max that changes, and a table or r_max that changes free that
+// format's shadows alone.  A new table's plans are uploaded before the config takes it.
 int set_part_receipts(fa_ctx* ctx, Part& p, const ReceiptCfg& c) {
     const ReceiptCfg was = p.mx8.cfg;
+    const bool new_lr = !c.same_lowrank(was);
     if (!c.on() || !was.on()) {
         if (int rc = set_part_flag(ctx, p, false, c.on())) return rc;
-        if (c.on()) p.mx8.cfg = c;
-        return FA_OK;
+        if (!c.on()) return FA_OK;
+        p.mx8.cfg = c;
+    } else {
+        const bool drop_q = was.flag && !c.flag && p.mx8.buf, drop_s = was.k_max != c.k_max && p.mx8.sparse;
+        const bool drop_f = new_lr && (p.mx8.plan || p.mx8.factors);
+        if (drop_q || drop_s || drop_f)
+            if (int rc = wait_devices(ctx)) return rc;
+        if (drop_q) p.mx8.buf.free(ctx->gpu);
+        if (drop_s) p.mx8.sparse.free(ctx->gpu);
+        if (drop_f) {
+            p.mx8.plan.free(ctx->gpu);
+            p.mx8.factors.free(ctx->gpu);
+        }
+        p.mx8.cfg = c;
     }
-    const bool drop_q = was.flag && !c.flag && p.mx8.buf, drop_s = was.k_max != c.k_max && p.mx8.sparse;
-    if (drop_q || drop_s)
-        if (int rc = wait_devices(ctx)) return rc;
-    if (drop_q) p.mx8.buf.free(ctx->gpu);
-    if (drop_s) p.mx8.sparse.free(ctx->gpu);
-    p.mx8.cfg = c;
+    if (new_lr && c.lowrank())
+        if (int rc = upload_lowrank_plans(ctx, p)) {  // the part keeps the stage without the format
+            p.mx8.cfg.mats.clear();
+            p.mx8.cfg.r_max = 0;
+            if (!p.mx8.cfg.on()) free_mx8(ctx, p);
+            return rc;
+        }
     return FA_OK;
 }
 
@@ -1530,7 +1575,67 @@ int submit_topk_impl(fa_ctx* ctx, int part_id, int slot, const uint32_t* idx, co
     return mark_submitted(ctx, *p, slot, weight);
 }
 
-// The receipt formats a fa_set_mx8 / fa_set_topk starts from: the part's own, or the context default's.
+// ------------------------------------------------------------------ low-rank receipts (fa.h "Low-rank receipts")
+
+// The factor shadows of a part, allocated once per table and r_max: per GPU held x fstride bytes, a shadow the whole
+// receipt at rank r_max.  On failure the part keeps the stage.
+int ensure_lowrank_buf(fa_ctx* ctx, Part& p) {
+    Mx8Stage& s = p.mx8;
+    if (s.factors) return FA_OK;
+    s.fstride = ((size_t)fa::lowrank_len(s.cfg.mats.data(), s.cfg.mats.size(), p.n, s.cfg.r_max) * 4 + 255) / 256 * 256;
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.fstride); };
+    const int g = s.factors.alloc(ctx->gpu, bytes);
+    if (g < 0) return FA_OK;
+    return fail(FA_ERR_NOMEM, "lowrank: shadow alloc of %zu B failed on GPU %zu", bytes((size_t)g), (size_t)g);
+}
+
+int submit_lowrank_impl(fa_ctx* ctx, int part_id, int slot, const float* f, size_t len, int r, float weight, int flags) {
+    Trace tr("fa_submit_lowrank part %d slot %d", part_id, slot);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (flags & ~(FA_HOST_PINNED | FA_LOWRANK_ABSOLUTE)) return fail(FA_ERR_ARG, "lowrank: unknown flags 0x%x", flags);
+    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    const ReceiptCfg& c = p->mx8.cfg;
+    if (!c.lowrank()) return fail(FA_ERR_STATE, "lowrank: part %d does not take low-rank receipts (fa_set_lowrank)", part_id);
+    if (r < 1 || r > c.r_max) return fail(FA_ERR_ARG, "lowrank: rank %d, part %d takes 1 .. %d (fa_set_lowrank)", r, part_id, c.r_max);
+    const size_t need = (size_t)fa::lowrank_len(c.mats.data(), c.mats.size(), p->n, r);
+    if (len != need) return fail(FA_ERR_ARG, "lowrank: %zu values, a receipt of rank %d for part %d has %zu (fa_lowrank_len)", len, r, part_id, need);
+    if (len && !f) return fail(FA_ERR_ARG, "lowrank: f is null");
+    const bool pinned = (flags & FA_HOST_PINNED) != 0, absolute = (flags & FA_LOWRANK_ABSOLUTE) != 0;
+    if (!absolute && !p->mx8.ref)
+        return fail(FA_ERR_STATE, "lowrank: part %d has no reference (no round reduced with the stage on, no "
+                                  "fa_mx8_set_reference): send a full receipt, or FA_LOWRANK_ABSOLUTE", part_id);
+    if ((rc = ensure_lowrank_buf(ctx, *p))) return rc;
+    if ((rc = host_flush(ctx, *p))) return rc;  // none is kept while the stage is on; the plain path from here on
+    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
+        GpuRes& gr = ctx->gpu[(size_t)g];
+        DeviceGuard dg(gr.dev);
+        const size_t off = p->off[(size_t)g], cnt = p->cnt[(size_t)g];
+        if (cnt == 0) return FA_OK;
+        // after the part's last reducing call: it read the slot and wrote the reference
+        if (hipStream_t ds = p->done_stream[(size_t)g]) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(gr.copy, p->done[(size_t)g], 0));
+        }
+        char* df = p->mx8.factors.at((size_t)g) + (size_t)(slot - p->c0[(size_t)g]) * p->mx8.fstride;
+        ++gr.copy_gen;  // the next reducing call waits for the copy stream: the copy and the expansion
+        if (int rc2 = mx8_h2d(gr, df, reinterpret_cast<const char*>(f), len * 4, pinned)) return rc2;
+        for (int j = 0; j < p->npiece[(size_t)g]; ++j) {
+            const size_t lo = piece_lo(*p, g, j), pc = piece_cnt(*p, g, j);
+            const void* ref = absolute ? nullptr : static_cast<const char*>(p->dout[(size_t)g]) + lo * dsize(p->out);
+            FA_HIP(fa::launch_lowrank_expand(p->mx8.plan.at((size_t)g) + p->mx8.plan_at[(size_t)g][(size_t)j],
+                                             p->mx8.plan_len[(size_t)g][(size_t)j], reinterpret_cast<const float*>(df), r,
+                                             (uint64_t)(off + lo), (int64_t)pc, ref, p->out, piece_ptr(*p, g, slot, j), p->in,
+                                             gr.copy));
+        }
+        return FA_OK;
+    });
+    if (rc) return rc;
+    return mark_submitted(ctx, *p, slot, weight);
+}
+
+// The receipt formats a fa_set_mx8 / fa_set_topk / fa_set_lowrank starts from: the part's own, or the context default's.
 ReceiptCfg receipts_of(fa_ctx* ctx, int part_id) {
     if (!ctx) return ReceiptCfg{};
     const auto it = ctx->parts.find(part_id);
@@ -2181,6 +2286,31 @@ int fa_submit_topk(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* id
     return submit_topk_impl(ctx, part_id, client_slot, idx, val, k, weight, flags);
 }
 
+int fa_set_lowrank(fa_ctx* ctx, int part_id, const fa_lowrank_mat* mats, size_t M, int r_max) {
+    g_err.clear();
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (part_id < 0) return fail(FA_ERR_ARG, "lowrank: a table belongs to one part's layout: there is no context default");
+    StageCfgs c = requested(ctx);
+    c.mx8 = receipts_of(ctx, part_id);
+    c.mx8.mats.clear();
+    c.mx8.r_max = 0;
+    if (M) {
+        Part* p;
+        if (int rc = check_part(ctx, part_id, &p)) return rc;
+        if (int rc = fa_lowrank_check(mats, M, p->n)) return rc;
+        if (r_max < 1 || r_max > FA_LOWRANK_MAX_RANK)
+            return fail(FA_ERR_ARG, "lowrank: r_max %d outside 1 .. %d", r_max, FA_LOWRANK_MAX_RANK);
+        c.mx8.mats.assign(mats, mats + M);
+        c.mx8.r_max = r_max;
+    }
+    return set_stage(ctx, part_id, kMx8, c);
+}
+
+int fa_submit_lowrank(fa_ctx* ctx, int part_id, int client_slot, const float* f, size_t len, int r, float weight, int flags) {
+    g_err.clear();
+    return submit_lowrank_impl(ctx, part_id, client_slot, f, len, r, weight, flags);
+}
+
 int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags) {
     g_err.clear();
     return submit_mx8_impl(ctx, part_id, client_slot, q, e, weight, flags);
@@ -2192,7 +2322,7 @@ int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
     if (int rc = check_part(ctx, part_id, &p)) return rc;
     if (!p->mx8.on() && !p->reply.on())
         return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
-                                  "(fa_set_mx8_reply), nor takes top-k receipts (fa_set_topk)", part_id);
+                                  "(fa_set_mx8_reply), nor takes top-k (fa_set_topk) or low-rank receipts (fa_set_lowrank)", part_id);
     if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
     if (int rc = wait_devices(ctx)) return rc;  // the part's pending work, on whatever stream
     if (p->reply.on())
