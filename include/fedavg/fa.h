@@ -446,6 +446,49 @@
  *              x_i = d_i, rounded the same way; (slot, ref) pairs are the (in, out) pairs below.
  *              Added without a new FA_ABI_VERSION: fa_lowrank_expand_device with cnt == 0 touches no device and
  *              answers FA_OK -- that is how a caller probes for it.
+ *   Rot1 receipts (fa_set_rot1, fa_submit_rot1, fa_rot1_expand_device, fa_rot1_encode_device, fa_rot1_encode,
+ *              fa_rot1_decode, fa_rot1_words, fa_rot1_blocks): sign compression under a random rotation (Suresh et al.,
+ *              "Distributed Mean Estimation with Limited Communication", ICML 2017; DRIVE, Vargaftik et al., NeurIPS
+ *              2021): one bit per element and one fp32 scale per block of 4096, 31.8 times fewer bytes than fp32.  The
+ *              rotation, a randomized Walsh-Hadamard transform, gives every coordinate of a block the same scale, which
+ *              is what makes one bit useful on heavy-tailed updates; for Gaussian-like updates the NMSE is 1 - 2/pi.
+ *              As with the other formats a kernel rebuilds the ordinary slot x = g + d.
+ *              Constants.  B = 4096.  Block b is elements [4096 b, 4096 b + 4096) of the whole bucket, never of a
+ *              shard or a piece; nb = ceil(n / 4096) (fa_rot1_blocks).
+ *              Format.  bits: nb * 128 uint32 words (fa_rot1_words), the bit of element i is bit (i & 31) of word
+ *              i >> 5; scale: nb fp32 values; seed: one uint64 chosen by the owner.  In the last block all 4096 bits
+ *              are meaningful: they are the transform of the zero-padded block.
+ *              Diagonal D.  For element i, with j = i >> 7: Philox4x32-10 as in the noise stage with counter (lo32(j),
+ *              hi32(j), 0, 0x524F5431) and key (lo32(seed), hi32(seed)); s_i = bit (i & 31) of output word
+ *              (i >> 5) & 3.  "Apply D" flips the IEEE sign bit where s_i is set.
+ *              Transform W, on 4096 values: for h = 1, 2, 4, .., 2048 in this order, for every i with (i & h) == 0:
+ *              (a, b) = (z_i, z_{i+h}); z_i = fl32(a + b); z_{i+h} = fl32(a - b).  Plain IEEE adds, subnormals kept.
+ *              Decode (fa_rot1_decode, and the kernel):
+ *              1. u_i = -1.0f where the bit is set, +1.0f elsewhere.
+ *              2. v = W(u).  Every intermediate is an integer of magnitude <= 4096, so any order of the stages, or a
+ *                 product with +-1 matrices in fp16 x fp16 -> fp32 (H_4096 = H_16 (x) H_16 (x) H_16, and 256 is exact
+ *                 in fp16), gives the same bits.
+ *              3. d_i = D applied to fl32(v_i * scale_b), one IEEE multiply.  NaN and inf in the scale follow IEEE
+ *                 rules (0 * inf is NaN).
+ *              4. Elements at or beyond n are dropped.
+ *              Expansion is decode rule 3 of MX8 receipts, unchanged: x_i = fl32(widen(g_i) + d_i), one IEEE add; a
+ *              16-bit slot stores x_i rounded once more to nearest-even; without a reference (absolute mode)
+ *              x_i = d_i, rounded the same way; (slot, ref) pairs are the (in, out) pairs below.
+ *              Encode (fa_rot1_encode on given deltas; fa_rot1_encode_device on `new` and `sent` of one dtype), per
+ *              block:
+ *              1. delta_i = fl32(widen(new_i) - widen(sent_i)), one IEEE subtract.  Elements beyond n are +0.
+ *              2. t_i = D applied to delta_i; y = W(t).
+ *              3. The bit of i is set iff y_i < 0, an IEEE compare: false for -0 and NaN.
+ *              4. A is the sum of (double)|y_i| over a fixed tree: A_i = (double)|y_i|; for h = 1, 2, .., 2048, for
+ *                 every i that is a multiple of 2h, A_i += A_{i+h}; A = A_0.
+ *              5. If A is NaN or +inf: scale_b = the quiet NaN 0x7FC00000 and all 4096 bits are 0.  Otherwise
+ *                 scale_b = (float)(A * 2^-24): the product is exact in fp64 and is rounded once.  This is DRIVE's
+ *                 minimum-MSE scale ||Rx||_1 / B folded with the two factors 1/64 of R = H D / 64.
+ *              6. g'_i is the expansion of (bits, scale, seed) against `sent`, into the same dtype.
+ *              An owner may use another scale, for example the unbiased ||x||^2 / ||Rx||_1 form: any (bits, scale)
+ *              is valid decoder input.
+ *              Added without a new FA_ABI_VERSION: fa_rot1_expand_device with cnt == 0 and fa_rot1_encode_device with
+ *              n == 0 touch no device and answer FA_OK -- that is how a caller probes for them.
  *   Secagg stage (fa_set_secagg, fa_secagg_set_terms, fa_secagg_unmask_device, fa_secagg_mask_host,
  *              fa_secagg_quantize): the server's arithmetic of secure aggregation (Bonawitz et al., "Practical Secure
  *              Aggregation for Privacy-Preserving Machine Learning", CCS 2017).  The slots of an FA_FEDAVG part with
@@ -1019,7 +1062,7 @@ int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, co
 /* Writes the part's device output on every GPU from host_src (n elements of the out dtype), as if a round had
  * produced it: the reference of the next relative submits (a restarted aggregator; tests).  Waits for the part's
  * pending work.  On a part with the reply stage it also sets `sent`.  FA_ERR_STATE on a part with none of
- * fa_set_mx8, fa_set_topk, fa_set_lowrank and fa_set_mx8_reply. */
+ * fa_set_mx8, fa_set_topk, fa_set_lowrank, fa_set_rot1 and fa_set_mx8_reply. */
 int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src);
 
 /* MX8 replies (the header comment, "MX8 replies"): the new model as block-scaled int8 deltas, encoded on the GPU. */
@@ -1169,6 +1212,56 @@ int fa_set_lowrank(fa_ctx* ctx, int part_id, const fa_lowrank_mat* mats, size_t 
 #define FA_LOWRANK_ABSOLUTE 0x2
 int fa_submit_lowrank(fa_ctx* ctx, int part_id, int client_slot, const float* f, size_t len, int r, float weight,
                       int flags);
+
+/* Rot1 receipts (the header comment, "Rot1 receipts"): Hadamard sign codes, expanded on the GPU by fp16 MFMA. */
+#define FA_ROT1_BLOCK 4096
+/* The uint32 words of `bits` and the fp32 values of `scale` for a bucket of n elements: 128 and 1 per block. */
+size_t fa_rot1_words(size_t n);
+size_t fa_rot1_blocks(size_t n);
+/* Encode rules 2-5 on the n given deltas of a whole bucket, pure host arithmetic, usable without a device: bits gets
+ * fa_rot1_words(n) words, scale fa_rot1_blocks(n) values. */
+int fa_rot1_encode(const float* delta, size_t n, uint64_t seed, uint32_t* bits, float* scale);
+/* The decoder, pure host arithmetic: d[i] = the delta of bucket element idx0 + i over cnt elements.  bits and scale
+ * start at block idx0 >> 12 and cover the range. */
+int fa_rot1_decode(const uint32_t* bits, const float* scale, uint64_t seed, uint64_t idx0, size_t cnt, float* d);
+/* The expansion on raw device pointers, on device `gpu`: d_dst[i] (cnt of dst_dtype) = fl(widen(d_ref[i]) + d_i), or d_i
+ * with d_ref NULL (absolute mode), over bucket elements idx0 .. idx0 + cnt - 1 with any idx0.  d_bits and d_scale start
+ * at block idx0 >> 12 and cover the range: a block that the range holds part of is transformed whole and stored only
+ * inside the range, and every store is checked against the range.  ctx may be NULL (then `gpu` is the HIP device).
+ * Every argument is checked before any device call: the dtypes and their pair ((dst, ref) as (in, out)), idx0 + cnt <
+ * 2^64, and for cnt > 0 null pointers and alignment (FA_ERR_ALIGN: d_bits and d_scale 4 bytes, d_ref and d_dst their
+ * element); with cnt == 0 and valid arguments it returns FA_OK without touching a device.  Any element phase of d_ref
+ * and d_dst is correct; a lane moves its four consecutive elements in one access (16 bytes of fp32, 8 of a 16-bit type)
+ * where every pointer is so aligned at the bucket's multiples of four.  d_dst must not overlap d_ref.  Async on
+ * hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
+int fa_rot1_expand_device(fa_ctx* ctx, int gpu, const uint32_t* d_bits, const float* d_scale, uint64_t seed, uint64_t idx0,
+                          size_t cnt, const void* d_ref, fa_dtype ref_dtype, void* d_dst, fa_dtype dst_dtype,
+                          void* hip_stream);
+/* Encode rules 1-6 on raw device pointers, on device `gpu`: over the n elements of d_new and d_sent (one dtype), bucket
+ * elements idx0 .. idx0 + n - 1 with idx0 a multiple of 4096 (FA_ERR_ARG otherwise), d_bits gets fa_rot1_words(n) words
+ * and d_scale fa_rot1_blocks(n) values (block idx0 >> 12 first) and, unless d_out is NULL, d_out gets g' (n elements of
+ * the same dtype).  d_out may be d_sent or d_new exactly or overlap neither (FA_ERR_ARG otherwise).  One launch, a
+ * workgroup per block.  The checks, ctx == NULL, the n == 0 probe and the stream are fa_rot1_expand_device's; 16-byte
+ * accesses are used where d_new, d_sent and d_out are 16-byte aligned. */
+int fa_rot1_encode_device(fa_ctx* ctx, int gpu, const void* d_new, fa_dtype new_dtype, const void* d_sent,
+                          fa_dtype sent_dtype, size_t n, uint64_t idx0, uint64_t seed, uint32_t* d_bits, float* d_scale,
+                          void* d_out, void* hip_stream);
+/* Lets a part take rot1 receipts (part_id >= 0), or sets the context default for parts defined later (part_id < 0).  It
+ * is the stage of fa_set_mx8 with a fourth format: admission, the reference, the refusals (FA_LITERAL,
+ * FA_SHARD_CLIENT_RS, a secagg part) and the call ordering are fa_set_mx8's, the part is never kept host-side and
+ * FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager.  A part may take all four formats, and different owners may send
+ * different ones.  Memory: per GPU and client slot a shadow of 516 bytes per block its range touches, rounded up to 256,
+ * allocated at the part's first fa_submit_rot1; on == 0 frees it. */
+int fa_set_rot1(fa_ctx* ctx, int part_id, int on);
+/* A rot1 receipt of client `client_slot`: bits (fa_rot1_words(n) words), scale (fa_rot1_blocks(n) values) and the seed.
+ * flags: FA_HOST_PINNED as for fa_submit_mx8 (bits and scale stay unchanged until fa_finalize* returns);
+ * FA_ROT1_ABSOLUTE = absolute mode (x = d).  Per GPU enqueues the H2D of the words and scales of the blocks its element
+ * range touches, then per piece the expansion with that range's idx0, ordered after the part's last reducing call and
+ * before the next.  The slot then counts as the client's receipt exactly as after fa_submit.  The reference and its
+ * FA_ERR_STATE are fa_submit_mx8's; FA_ERR_STATE on a part without fa_set_rot1. */
+#define FA_ROT1_ABSOLUTE 0x2
+int fa_submit_rot1(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* bits, const float* scale, uint64_t seed,
+                   float weight, int flags);
 
 /* Secagg stage (the header comment, "Secagg stage"): masked uint32 sums unmasked and decoded on the GPU. */
 #define FA_SECAGG_MAX_TERMS 4096

@@ -150,6 +150,14 @@ def lib():
         "fa_lowrank_expand_device": (I, [P, I, P, S, P, I, U64, S, P, I, P, I, P]),
         "fa_set_lowrank": (I, [P, I, P, S, I]),
         "fa_submit_lowrank": (I, [P, I, I, P, S, I, F, I]),
+        "fa_rot1_words": (S, [S]),
+        "fa_rot1_blocks": (S, [S]),
+        "fa_rot1_encode": (I, [P, S, U64, P, P]),
+        "fa_rot1_decode": (I, [P, P, U64, U64, S, P]),
+        "fa_rot1_expand_device": (I, [P, I, P, P, U64, U64, S, P, I, P, I, P]),
+        "fa_rot1_encode_device": (I, [P, I, P, I, P, I, S, U64, U64, P, P, P, P]),
+        "fa_set_rot1": (I, [P, I, I]),
+        "fa_submit_rot1": (I, [P, I, I, P, P, U64, F, I]),
         "fa_set_secagg": (I, [P, I, F]),
         "fa_secagg_set_terms": (I, [P, I, I, P, P, P]),
         "fa_secagg_unmask_device": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, P]),
@@ -574,6 +582,58 @@ def topk_encode_device(new, sent, n, k, idx, val, work, out=None, dtype=F32, sen
     check(lib().fa_topk_encode_device(ctx.handle if ctx is not None else None, gpu, _addr(new), dtype, _addr(sent),
                                       dtype if sent_dtype is None else sent_dtype, n, int(k), _addr(idx), _addr(val),
                                       _addr(out), _addr(work), _stream(stream)))
+
+
+ROT1_ABSOLUTE = 0x2  # FA_ROT1_ABSOLUTE
+ROT1_BLOCK = 4096  # FA_ROT1_BLOCK: elements per scale of a rot1 receipt (fa.h "Rot1 receipts")
+
+
+def rot1_blocks(n):
+    """fa_rot1_blocks: ceil(n / 4096), the scales of a rot1 receipt; its bits are 128 uint32 words per block."""
+    return lib().fa_rot1_blocks(n)
+
+
+def rot1_encode(delta, seed):
+    """fa_rot1_encode (host arithmetic, fa.h "Rot1 receipts" rules 2-5): the fp32 deltas of a whole bucket as (bits
+    uint32[128 nb], scale float32[nb])."""
+    delta = np.ascontiguousarray(np.asarray(delta, np.float32).reshape(-1))
+    nb = rot1_blocks(delta.size)
+    bits, scale = np.empty(nb * 128, np.uint32), np.empty(nb, np.float32)
+    check(lib().fa_rot1_encode(delta.ctypes.data, delta.size, int(seed), bits.ctypes.data, scale.ctypes.data))
+    return bits, scale
+
+
+def rot1_decode(bits, scale, seed, n, idx0=0):
+    """fa_rot1_decode (host arithmetic): the fp32 deltas of bucket elements idx0 .. idx0 + n - 1; bits and scale start at
+    block idx0 >> 12."""
+    bits = np.ascontiguousarray(np.asarray(bits, np.uint32).reshape(-1))
+    scale = np.ascontiguousarray(np.asarray(scale, np.float32).reshape(-1))
+    nb = ((idx0 + n - 1) >> 12) - (idx0 >> 12) + 1 if n else 0
+    if bits.size < nb * 128 or scale.size < nb:
+        raise ValueError("elements [%d, %d) touch %d blocks, got %d words and %d scales" % (idx0, idx0 + n, nb, bits.size, scale.size))
+    d = np.empty(n, np.float32)
+    check(lib().fa_rot1_decode(bits.ctypes.data, scale.ctypes.data, int(seed), int(idx0), n, d.ctypes.data))
+    return d
+
+
+def rot1_expand_device(bits, scale, seed, n, dst, dst_dtype=F32, ref=None, ref_dtype=F32, idx0=0, stream=None, gpu=0,
+                       ctx=None):
+    """fa_rot1_expand_device: dst[i] = ref[i] + d_i over n device-resident elements, bucket elements idx0 .. (ref None:
+    absolute mode, dst[i] = d_i), from the device-resident bits and scales of the blocks the range touches, block
+    idx0 >> 12 first.  Enqueued, not synchronized.  With n == 0 no device is touched: the feature probe."""
+    check(lib().fa_rot1_expand_device(ctx.handle if ctx is not None else None, gpu, _addr(bits), _addr(scale), int(seed),
+                                      int(idx0), n, _addr(ref), ref_dtype, _addr(dst), dst_dtype, _stream(stream)))
+
+
+def rot1_encode_device(new, sent, n, seed, bits, scale, out=None, dtype=F32, sent_dtype=None, idx0=0, stream=None, gpu=0,
+                       ctx=None):
+    """fa_rot1_encode_device (fa.h "Rot1 receipts", rules 1-6): over n device-resident elements of `dtype`, bucket
+    elements idx0 .. (a multiple of 4096), the bits and scales of fl(new - sent), and (out not None) g' = sent +
+    decode(bits, scale) into out, which may be `sent` or `new` itself.  Enqueued, not synchronized.  With n == 0 no device
+    is touched: the feature probe."""
+    check(lib().fa_rot1_encode_device(ctx.handle if ctx is not None else None, gpu, _addr(new), dtype, _addr(sent),
+                                      dtype if sent_dtype is None else sent_dtype, n, int(idx0), int(seed), _addr(bits),
+                                      _addr(scale), _addr(out), _stream(stream)))
 
 
 LOWRANK_ABSOLUTE = 0x2  # FA_LOWRANK_ABSOLUTE
@@ -1179,6 +1239,26 @@ class Aggregator:
             raise ValueError("need f float32")
         flags = (HOST_PINNED if pinned else 0) | (LOWRANK_ABSOLUTE if absolute else 0)
         check(lib().fa_submit_lowrank(self.handle, part, slot, f.ctypes.data, f.size, int(r), float(weight), flags))
+
+    def set_rot1(self, on=True, part=None):
+        """fa_set_rot1: the part takes rot1 receipts, on the stage and the reference of set_mx8 (part None: the default
+        of parts defined later); on=False switches them off."""
+        check(lib().fa_set_rot1(self.handle, -1 if part is None else part, 1 if on else 0))
+
+    def submit_rot1(self, part, slot, bits, scale, seed, weight=1.0, absolute=False, pinned=False):
+        """fa_submit_rot1: the client's update against the part's last output as (bits uint32[128 nb], scale
+        float32[nb], seed), expanded into the slot on the GPU.  pinned: views of PinnedBuffers the caller keeps
+        unchanged until finalize returns.  absolute: the values themselves, no reference."""
+        bits, scale = np.ascontiguousarray(bits), np.ascontiguousarray(scale)
+        if bits.dtype != np.uint32 or scale.dtype != np.float32:
+            raise ValueError("need bits uint32 and scale float32")
+        if part in self.parts:
+            nb = rot1_blocks(self.parts[part][0])
+            if bits.size != nb * 128 or scale.size != nb:
+                raise ValueError("bucket %d expects %d words and %d scales, got %d and %d"
+                                 % (part, nb * 128, nb, bits.size, scale.size))
+        flags = (HOST_PINNED if pinned else 0) | (ROT1_ABSOLUTE if absolute else 0)
+        check(lib().fa_submit_rot1(self.handle, part, slot, bits.ctypes.data, scale.ctypes.data, int(seed), float(weight), flags))
 
     def set_mx8_reference(self, part_id, g):
         """fa_mx8_set_reference: the part's device output := g (n elements of the out dtype; bf16 as uint16 bits), the

@@ -306,10 +306,10 @@ struct FlagCfg {  // fa.h "MX8 replies"
     bool flag = false;
     bool on() const { return flag; }
 };
-// fa.h "MX8 receipts", "Top-k receipts", "Low-rank receipts": the compressed formats a part takes (k_max 0: no top-k;
-// no matrices: no low-rank, which a context default never has).
+// fa.h "MX8 receipts", "Top-k receipts", "Low-rank receipts", "Rot1 receipts": the compressed formats a part takes
+// (k_max 0: no top-k; no matrices: no low-rank, which a context default never has).
 struct ReceiptCfg {
-    bool flag = false;
+    bool flag = false, rot1 = false;
     size_t k_max = 0;
     std::vector<fa_lowrank_mat> mats;
     int r_max = 0;
@@ -318,7 +318,7 @@ struct ReceiptCfg {
         return r_max == o.r_max && mats.size() == o.mats.size() &&
                (mats.empty() || !std::memcmp(mats.data(), o.mats.data(), mats.size() * sizeof(fa_lowrank_mat)));
     }
-    bool on() const { return flag || k_max > 0 || lowrank(); }
+    bool on() const { return flag || rot1 || k_max > 0 || lowrank(); }
 };
 struct SecaggCfg {  // fa.h "Secagg stage"
     float scale = 0.0f;
@@ -403,12 +403,13 @@ struct NoiseStage {
 // many values), allocated at the first fa_submit_topk.  plan: per GPU the low-rank plans of its pieces back to back,
 // piece j at plan_at[g][j] with plan_len[g][j] bytes, built and uploaded by fa_set_lowrank; factors: per GPU the
 // low-rank shadows of its held slots, fstride bytes apart (a whole receipt of rank r_max), allocated at the first
-// fa_submit_lowrank.
+// fa_submit_lowrank.  rot: per GPU the rot1 shadows of its held slots, rstride[g] bytes apart (the 128 words of each
+// block its range touches, then from rsoff[g] on their scales), allocated at the first fa_submit_rot1.
 struct Mx8Stage {
     ReceiptCfg cfg;
     bool ref = false;
-    DevArrays buf, sparse, plan, factors;
-    std::vector<size_t> stride, eoff, sstride, scap;
+    DevArrays buf, sparse, plan, factors, rot;
+    std::vector<size_t> stride, eoff, sstride, scap, rstride, rsoff;
     std::vector<std::vector<size_t>> plan_at, plan_len;
     size_t fstride = 0;
     bool on() const { return cfg.on(); }

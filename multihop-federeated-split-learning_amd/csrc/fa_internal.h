@@ -240,6 +240,19 @@ void lowrank_decode_host(const fa_lowrank_mat* mats, size_t M, uint64_t n, const
                          uint64_t cnt, float* d);
 hipError_t launch_lowrank_expand(const void* plan, size_t plan_bytes, const float* f, int r, uint64_t idx0, int64_t cnt,
                                  const void* ref, fa_dtype rdt, void* dst, fa_dtype ddt, hipStream_t s);
+// Rot1 receipts (fa.h "Rot1 receipts"), fa_rot1.hip.  Expansion: dst[i] (dtype ddt, one rounding) := fl(widen(ref[i]) +
+// d_i), or d_i with ref null, over bucket elements [idx0, idx0 + cnt), any idx0; bits (128 words per block) and scale
+// (one per block) start at block idx0 >> 12; every store is checked against the range.  Encoding over n elements of
+// dtype dt from block blk0 on (rules 1-6): bits, scale := the codes of fl(widen(y) - widen(sent)), out (nullable; y or
+// sent exactly, or apart) := g'.  Any pointers of element alignment.
+constexpr int kRot1Block = 4096, kRot1Words = kRot1Block / 32;
+hipError_t launch_rot1_expand(const uint32_t* bits, const float* scale, uint64_t seed, uint64_t idx0, int64_t cnt,
+                              const void* ref, fa_dtype rdt, void* dst, fa_dtype ddt, hipStream_t s);
+hipError_t launch_rot1_encode(const void* y, const void* sent, fa_dtype dt, int64_t n, uint64_t blk0, uint64_t seed,
+                              uint32_t* bits, float* scale, void* out, hipStream_t s);
+// The codec on the host (fa_rot1_encode, fa_rot1_decode): plain loops over the rule.
+void rot1_encode_host(const float* delta, size_t n, uint64_t seed, uint32_t* bits, float* scale);
+void rot1_decode_host(const uint32_t* bits, const float* scale, uint64_t seed, uint64_t idx0, size_t cnt, float* d);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
                        const Tuning& tu, hipStream_t s);

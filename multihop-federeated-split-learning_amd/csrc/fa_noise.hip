@@ -34,6 +34,7 @@
 
 #include "fa_device.h"
 #include "fa_internal.h"
+#include "fa_philox.h"
 
 #pragma clang fp contract(off)
 
@@ -54,26 +55,7 @@ constexpr float kC3 = 0x1.555556p-2f, kC5 = 0x1.99999ap-3f, kC7 = 0x1.24924ap-3f
 constexpr float kS3 = -0x1.555556p-3f, kS5 = 0x1.111112p-7f, kS7 = -0x1.a01a02p-13f, kS9 = 0x1.71de3ap-19f;  // sine
 constexpr float kK2 = -0x1p-1f, kK4 = 0x1.555556p-5f, kK6 = -0x1.6c16c2p-10f, kK8 = 0x1.a01a02p-16f;         // cosine
 
-// Rule 1: Philox4x32-10 of counter (c0..c3) under key (k0, k1).  The 64-bit products are left to the compiler
-// (v_mad_u64_u32 on gfx950: one instruction per product).
-__host__ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                       uint32_t k1, uint32_t* r) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        c0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        c1 = (uint32_t)p1;
-        c2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    r[0] = c0;
-    r[1] = c1;
-    r[2] = c2;
-    r[3] = c3;
-}
+// Rule 1: philox4x32_10 (fa_philox.h).
 
 // Rule 2: R = sqrt(-2 ln u), u = (r + 1) 2^-32 with its top 24 bits kept.
 __host__ __device__ __forceinline__ float noise_radius(uint32_t r) {

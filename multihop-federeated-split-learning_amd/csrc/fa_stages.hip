@@ -528,6 +528,7 @@ void free_mx8(fa_ctx* ctx, Part& p) {
     p.mx8.sparse.free(ctx->gpu);
     p.mx8.plan.free(ctx->gpu);
     p.mx8.factors.free(ctx->gpu);
+    p.mx8.rot.free(ctx->gpu);
     p.mx8 = Mx8Stage{};
 }
 void free_reply(fa_ctx* ctx, Part& p) {
@@ -1193,7 +1194,7 @@ int set_part_noise(fa_ctx* ctx, Part& p, const NoiseCfg& c) {
     return FA_OK;
 }
 
-// fa_set_mx8 / fa_set_topk / fa_set_lowrank / fa_set_mx8_reply on a part (not FA_LITERAL, not rs).  Off: what the stage
+// fa_set_mx8 / fa_set_topk / fa_set_lowrank / fa_set_rot1 / fa_set_mx8_reply on a part (not FA_LITERAL, not rs).  Off: what the stage
 // allocated goes, after the devices' pending work.  On, for a part without it: what this round kept host-side or chained
 // so far goes back to the plain path; the buffers come with the first fa_submit_mx8 / fa_submit_topk /
 // fa_submit_lowrank, or the first reducing call.
@@ -1249,10 +1250,11 @@ int set_part_receipts(fa_ctx* ctx, Part& p, const ReceiptCfg& c) {
         p.mx8.cfg = c;
     } else {
         const bool drop_q = was.flag && !c.flag && p.mx8.buf, drop_s = was.k_max != c.k_max && p.mx8.sparse;
-        const bool drop_f = new_lr && (p.mx8.plan || p.mx8.factors);
-        if (drop_q || drop_s || drop_f)
+        const bool drop_f = new_lr && (p.mx8.plan || p.mx8.factors), drop_r = was.rot1 && !c.rot1 && p.mx8.rot;
+        if (drop_q || drop_s || drop_f || drop_r)
             if (int rc = wait_devices(ctx)) return rc;
         if (drop_q) p.mx8.buf.free(ctx->gpu);
+        if (drop_r) p.mx8.rot.free(ctx->gpu);
         if (drop_s) p.mx8.sparse.free(ctx->gpu);
         if (drop_f) {
             p.mx8.plan.free(ctx->gpu);
@@ -1635,7 +1637,78 @@ int submit_lowrank_impl(fa_ctx* ctx, int part_id, int slot, const float* f, size
     return mark_submitted(ctx, *p, slot, weight);
 }
 
-// The receipt formats a fa_set_mx8 / fa_set_topk / fa_set_lowrank starts from: the part's own, or the context default's.
+// ------------------------------------------------------------------ rot1 receipts (fa.h "Rot1 receipts")
+
+// The blocks of 4096 elements GPU g's range [off, off + cnt) touches: off >> 12 .. (off + cnt - 1) >> 12.
+inline size_t rot1_blocks(size_t off, size_t cnt) { return cnt ? ((off + cnt - 1) >> 12) - (off >> 12) + 1 : 0; }
+
+// The rot1 shadows of a part, allocated once: per GPU held x rstride bytes, a shadow the words of the blocks the GPU's
+// range touches followed by their scales.  On failure the part keeps the stage.
+int ensure_rot1_buf(fa_ctx* ctx, Part& p) {
+    Mx8Stage& s = p.mx8;
+    if (s.rot) return FA_OK;
+    s.rsoff.clear();
+    s.rstride.clear();
+    for (size_t g = 0; g < (size_t)ctx->G; ++g) {
+        const size_t nb = rot1_blocks(p.off[g], p.cnt[g]);
+        s.rsoff.push_back(nb * fa::kRot1Words * 4);
+        s.rstride.push_back((nb * (fa::kRot1Words + 1) * 4 + 255) / 256 * 256);
+    }
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.rstride[g]); };
+    const int g = s.rot.alloc(ctx->gpu, bytes);
+    if (g < 0) return FA_OK;
+    return fail(FA_ERR_NOMEM, "rot1: shadow alloc of %zu B failed on GPU %zu", bytes((size_t)g), (size_t)g);
+}
+
+int submit_rot1_impl(fa_ctx* ctx, int part_id, int slot, const uint32_t* bits, const float* scale, uint64_t seed,
+                     float weight, int flags) {
+    Trace tr("fa_submit_rot1 part %d slot %d", part_id, slot);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (flags & ~(FA_HOST_PINNED | FA_ROT1_ABSOLUTE)) return fail(FA_ERR_ARG, "rot1: unknown flags 0x%x", flags);
+    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    if (!p->mx8.cfg.rot1) return fail(FA_ERR_STATE, "rot1: part %d does not take rot1 receipts (fa_set_rot1)", part_id);
+    if (p->n > 0 && (!bits || !scale)) return fail(FA_ERR_ARG, "rot1: %s is null", !bits ? "bits" : "scale");
+    const bool pinned = (flags & FA_HOST_PINNED) != 0, absolute = (flags & FA_ROT1_ABSOLUTE) != 0;
+    if (!absolute && !p->mx8.ref)
+        return fail(FA_ERR_STATE, "rot1: part %d has no reference (no round reduced with the stage on, no "
+                                  "fa_mx8_set_reference): send a full receipt, or FA_ROT1_ABSOLUTE", part_id);
+    if ((rc = ensure_rot1_buf(ctx, *p))) return rc;
+    if ((rc = host_flush(ctx, *p))) return rc;  // none is kept while the stage is on; the plain path from here on
+    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        const size_t off = p->off[(size_t)g], cnt = p->cnt[(size_t)g];
+        if (cnt == 0) return FA_OK;
+        // after the part's last reducing call: it read the slot and wrote the reference
+        if (hipStream_t ds = p->done_stream[(size_t)g]) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(r.copy, p->done[(size_t)g], 0));
+        }
+        const size_t b0 = off >> 12, nb = rot1_blocks(off, cnt);
+        char* db = p->mx8.rot.at((size_t)g) + (size_t)(slot - p->c0[(size_t)g]) * p->mx8.rstride[(size_t)g];
+        char* dsc = db + p->mx8.rsoff[(size_t)g];
+        ++r.copy_gen;  // the next reducing call waits for the copy stream: the copies and the expansion
+        int rc2 = mx8_h2d(r, db, reinterpret_cast<const char*>(bits + b0 * fa::kRot1Words), nb * fa::kRot1Words * 4, pinned);
+        if (!rc2) rc2 = mx8_h2d(r, dsc, reinterpret_cast<const char*>(scale + b0), nb * 4, pinned);
+        if (rc2) return rc2;
+        for (int j = 0; j < p->npiece[(size_t)g]; ++j) {
+            const size_t lo = piece_lo(*p, g, j), pc = piece_cnt(*p, g, j);
+            if (pc == 0) continue;
+            const size_t pb = ((off + lo) >> 12) - b0;  // the piece's first block among the GPU's
+            const void* ref = absolute ? nullptr : static_cast<const char*>(p->dout[(size_t)g]) + lo * dsize(p->out);
+            FA_HIP(fa::launch_rot1_expand(reinterpret_cast<const uint32_t*>(db) + pb * fa::kRot1Words,
+                                          reinterpret_cast<const float*>(dsc) + pb, seed, (uint64_t)(off + lo), (int64_t)pc,
+                                          ref, p->out, piece_ptr(*p, g, slot, j), p->in, r.copy));
+        }
+        return FA_OK;
+    });
+    if (rc) return rc;
+    return mark_submitted(ctx, *p, slot, weight);
+}
+
+// The receipt formats a fa_set_mx8 / fa_set_topk / fa_set_lowrank / fa_set_rot1 starts from: the part's own, or the context default's.
 ReceiptCfg receipts_of(fa_ctx* ctx, int part_id) {
     if (!ctx) return ReceiptCfg{};
     const auto it = ctx->parts.find(part_id);
@@ -2311,6 +2384,20 @@ int fa_submit_lowrank(fa_ctx* ctx, int part_id, int client_slot, const float* f,
     return submit_lowrank_impl(ctx, part_id, client_slot, f, len, r, weight, flags);
 }
 
+int fa_set_rot1(fa_ctx* ctx, int part_id, int on) {
+    g_err.clear();
+    StageCfgs c = requested(ctx);
+    c.mx8 = receipts_of(ctx, part_id);
+    c.mx8.rot1 = on != 0;
+    return set_stage(ctx, part_id, kMx8, c);
+}
+
+int fa_submit_rot1(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* bits, const float* scale, uint64_t seed,
+                   float weight, int flags) {
+    g_err.clear();
+    return submit_rot1_impl(ctx, part_id, client_slot, bits, scale, seed, weight, flags);
+}
+
 int fa_submit_mx8(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags) {
     g_err.clear();
     return submit_mx8_impl(ctx, part_id, client_slot, q, e, weight, flags);
@@ -2322,7 +2409,7 @@ int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
     if (int rc = check_part(ctx, part_id, &p)) return rc;
     if (!p->mx8.on() && !p->reply.on())
         return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
-                                  "(fa_set_mx8_reply), nor takes top-k (fa_set_topk) or low-rank receipts (fa_set_lowrank)", part_id);
+                                  "(fa_set_mx8_reply), nor takes top-k (fa_set_topk), low-rank (fa_set_lowrank) or rot1 receipts (fa_set_rot1)", part_id);
     if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
     if (int rc = wait_devices(ctx)) return rc;  // the part's pending work, on whatever stream
     if (p->reply.on())
