@@ -525,6 +525,54 @@
  *              are pure host arithmetic.  No cryptographic review of the construction is claimed here.  Added without
  *              a new FA_ABI_VERSION: fa_secagg_unmask_device with n == 0 touches no device and answers FA_OK -- that
  *              is how a caller probes for it.
+ *   Sign-vote stage (fa_set_sign, fa_submit_sign, fa_copy_sign_planes, fa_sign_vote_device, fa_sign_vote_host,
+ *              fa_sign_pack, fa_sign_words, fa_sign_form): signSGD with majority vote (Bernstein et al., "signSGD with
+ *              Majority Vote is Communication Efficient and Fault Tolerant", ICLR 2019).  An owner sends one bit per
+ *              element, the server counts per element how many owners said "negative", the reply is the sign of the
+ *              majority.  The receipts are never expanded: the round reads D / 8 bytes per element of them.
+ *              1. Format.  A sign receipt of a bucket of n elements is fa_sign_words(n) = ceil(n / 32) uint32 words;
+ *                 the bit of element i is bit i & 31 of word i >> 5, i the element's index in the whole bucket, never
+ *                 the index within a shard or a piece.  Bits at or beyond n in the last word are ignored: any value
+ *                 there gives the same result.
+ *              2. Owner's side (fa_sign_pack, pure host arithmetic).  The bit is set iff delta_i < 0, an IEEE compare:
+ *                 clear for -0 and NaN (rot1's encode rule 3).  The padding bits are written as 0.
+ *              3. Counts.  c_i is the number of the round's D receipts whose bit i is set, an exact integer, 1 <= D <=
+ *                 FA_SIGN_MAX_CLIENTS.  Weights are ignored, as for FA_TRIMMED and the secagg stage.
+ *              4. Parameters.  eta: fp32, finite, > 0.  rule: FA_SIGN_MAJORITY or FA_SIGN_MEAN.  margin m, 1 <= m <= D,
+ *                 used by the majority rule only (checked where D is known: fa_set_sign, fa_sign_vote_device).
+ *              5. Majority.  With s_i = D - 2 c_i: v_i = +1 if s_i >= m, -1 if -s_i >= m, else 0; t_i = +eta, -eta or
+ *                 +0.  m = 1 is the paper's vote, a tie on even D giving 0; a larger m is a quorum.
+ *              6. Mean.  step = fl32(eta / (float)D), computed once on the host; t_i = fl32((float)s_i * step): one
+ *                 exact conversion and one IEEE multiply.
+ *              7. Aggregate.  a_i = fl32(widen(g_i) + t_i): one IEEE add, g widened exactly, -0 + +0 is +0; without a
+ *                 reference (absolute mode) a_i = t_i.  NaN and inf in g propagate.  a stands exactly where the chain's
+ *                 result stands: it feeds the noise stage and the server optimizer if the part has them, otherwise it
+ *                 is rounded once to the out dtype; MX8 replies, range shards, range pieces and fa_reduce_parts work as
+ *                 for any part.
+ *              8. Reference.  g is the part's device output as the last reducing call with the stage left it, exactly
+ *                 the reference of MX8 receipts (fa_mx8_set_reference sets it).  A round on a part without a reference
+ *                 runs in absolute mode.
+ *              9. Vote planes (the compressed reply).  The round optionally leaves two bit planes of fa_sign_words(n)
+ *                 words each: neg (the bit is set where v_i = -1) and pos (where v_i = +1), padding bits 0.  An owner
+ *                 that holds g and the planes rebuilds the reply bit for bit by rule 7: 2 bits per element where fp32
+ *                 takes 32.  The planes exist only under the majority rule on a part with no noise stage and no server
+ *                 optimizer (with either the reply is no function of the planes): asking for them otherwise, or
+ *                 giving a part with planes one of those stages, is FA_ERR_STATE.
+ *              10. Layout independence.  The counts are exact, range shards and pieces are cut at multiples of 64
+ *                 elements, so a word never straddles a cut: every output is the same bits for any GPU count, pieces
+ *                 or pointer phase.
+ *              11. Admission.  Only on an FA_FEDAVG part.  The stage belongs to the measure-then-select family: not
+ *                 with the clip, Krum, DnC, geomed or secagg stage (Bulyan needs an FA_TRIMMED part), and not with any of
+ *                 the four receipt formats (those setters refuse a sign part in turn).  Not on an FA_SHARD_CLIENT_RS
+ *                 context, not as a context default.  Like the other stage parts the part is never kept host-side,
+ *                 FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager, and a reducing call needs every client submitted, with
+ *                 fa_submit_sign: a dense fa_submit to such a part is FA_ERR_STATE.  Setting the stage on a part drops
+ *                 what the round had received so far.
+ *              Memory: per GPU and client slot a shadow of ceil(cnt / 32) * 4 bytes, rounded up to 256, and with planes
+ *              twice that once more.  The part's dense slots are neither read nor written by a vote round; they stay
+ *              allocated (not allocating them is left for later).
+ *              Added without a new FA_ABI_VERSION: fa_sign_vote_device with n == 0 touches no device and answers FA_OK
+ *              -- that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -1296,6 +1344,53 @@ int fa_secagg_quantize(const float* v, size_t n, float q, int32_t* out, uint64_t
 /* Which vector form a launch over n elements and T terms takes: 0 = a tile per wave, 1 = the term split (the four
  * waves of a workgroup share a tile's terms).  Pure host arithmetic; the bits do not depend on it. */
 int fa_secagg_form(size_t n, int T);
+
+/* Sign-vote stage (the header comment, "Sign-vote stage"): one-bit receipts counted bit-sliced on the GPU. */
+#define FA_SIGN_MAX_CLIENTS 128
+#define FA_SIGN_MAJORITY 0
+#define FA_SIGN_MEAN 1
+/* ceil(n / 32): the words of a sign receipt, and of a vote plane, of n elements. */
+size_t fa_sign_words(size_t n);
+/* Rule 2, pure host arithmetic: bits (fa_sign_words(n) words) = the sign receipt of the n deltas. */
+int fa_sign_pack(const float* delta, size_t n, uint32_t* bits);
+/* Rules 3-9 on the host, usable without a device: bits[k], k < D, are whole receipts; element i of ref (fp32, n
+ * elements, NULL = absolute mode), out (the fp32 a_i, before any rounding to a 16-bit type), neg and pos (fa_sign_words(n)
+ * words each, both NULL or both set, majority only) is bucket element idx0 + i, idx0 a multiple of 32.  FA_ERR_ARG as
+ * fa_sign_vote_device. */
+int fa_sign_vote_host(const uint32_t* const* bits, int D, size_t n, uint64_t idx0, float eta, int rule, int margin,
+                      const float* ref, float* out, uint32_t* neg, uint32_t* pos);
+/* Rules 3-9 on raw device pointers: d_out[i] (n of out_dtype, one rounding) from the D receipts d_bits (each the whole
+ * receipt of its bucket: the call reads its words idx0 >> 5 .. ) and d_ref (n of ref_dtype, NULL = absolute mode), element
+ * i being bucket element idx0 + i; d_neg and d_pos (fa_sign_words(n) words each, both NULL or both set, majority only) get
+ * the planes.  ctx may be NULL (then `gpu` is the HIP device).  Every argument is checked before any device call: 1 <= D
+ * <= FA_SIGN_MAX_CLIENTS, the dtypes and their pair (bf16 <-> f16: FA_ERR_ARG), eta finite and > 0, the rule, 1 <= margin
+ * <= D, idx0 a multiple of 32 with idx0 + n < 2^64, one plane pointer without the other, planes under the mean rule, and
+ * for n > 0 null pointers, alignment (FA_ERR_ALIGN: receipts and planes 4 bytes, d_ref and d_out their element) and that
+ * d_out does not overlap d_ref; with n == 0 and valid arguments it returns FA_OK without touching a device.  Async on
+ * hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream).  Any phase of the pointers is correct; the
+ * vector form needs the receipts (at word idx0 >> 5) and the planes in one 16-byte phase and d_ref, d_out 16-byte
+ * aligned (fa_sign_form). */
+int fa_sign_vote_device(fa_ctx* ctx, int gpu, const uint32_t* const* d_bits, int D, size_t n, uint64_t idx0, float eta,
+                        int rule, int margin, const void* d_ref, fa_dtype ref_dtype, void* d_out, fa_dtype out_dtype,
+                        uint32_t* d_neg, uint32_t* d_pos, void* hip_stream);
+/* Which form fa_sign_vote_device takes for these operands: 0 = the element form throughout, 1 = the vector form with
+ * element edges.  Pure host arithmetic on the pointer values; the bits do not depend on it. */
+int fa_sign_form(size_t n, const uint32_t* const* d_bits, int D, uint64_t idx0, const void* d_ref, fa_dtype ref_dtype,
+                 const void* d_out, fa_dtype out_dtype, const void* d_neg, const void* d_pos);
+/* Gives a part the stage (part_id >= 0; again: the numbers change, a round under way stays); eta <= 0 removes it and
+ * frees what it allocated.  planes != 0: the reducing calls leave the vote planes (rule 9).  FA_ERR_ARG, naming the
+ * cause: eta NaN or +inf, a rule other than the two, margin outside 1 .. D, D > FA_SIGN_MAX_CLIENTS, part_id < 0 (no
+ * context default), a part whose mode is not FA_FEDAVG, a part with a clip, Krum, DnC, geomed, secagg or receipt stage
+ * (those setters refuse a sign part in turn), an FA_SHARD_CLIENT_RS context.  FA_ERR_STATE: planes under the mean rule
+ * or on a part with a noise stage or a server optimizer. */
+int fa_set_sign(fa_ctx* ctx, int part_id, float eta, int rule, int margin, int planes);
+/* The sign receipt of client `client_slot`: bits (fa_sign_words(n) words).  flags: FA_HOST_PINNED as for fa_submit_rot1.
+ * Per GPU enqueues the H2D of the words of its range into the slot's shadow (allocated at the part's first submit); the
+ * slot then counts as submitted.  FA_ERR_STATE on a part without fa_set_sign. */
+int fa_submit_sign(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* bits, int flags);
+/* The planes of the part's last reducing call into host arrays of fa_sign_words(n) words each, waiting for it.
+ * FA_ERR_STATE on a part without planes or not yet reduced with them. */
+int fa_copy_sign_planes(fa_ctx* ctx, int part_id, uint32_t* neg, uint32_t* pos);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

@@ -164,6 +164,14 @@ def lib():
         "fa_secagg_mask_host": (I, [P, P, U64, S, P]),
         "fa_secagg_quantize": (I, [P, S, F, P, ctypes.POINTER(U64)]),
         "fa_secagg_form": (I, [S, I]),
+        "fa_sign_words": (S, [S]),
+        "fa_sign_pack": (I, [P, S, P]),
+        "fa_sign_vote_host": (I, [P, I, S, U64, F, I, I, P, P, P, P]),
+        "fa_sign_vote_device": (I, [P, I, P, I, S, U64, F, I, I, P, I, P, I, P, P, P]),
+        "fa_sign_form": (I, [S, P, I, U64, P, I, P, I, P, P]),
+        "fa_set_sign": (I, [P, I, F, I, I, I]),
+        "fa_submit_sign": (I, [P, I, I, P, I]),
+        "fa_copy_sign_planes": (I, [P, I, P, P]),
         "fa_diag_secagg_unmask": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, I, P]),  # diagnostic (outside fa.h)
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
@@ -796,6 +804,60 @@ def secagg_form(n, T):
     return lib().fa_secagg_form(n, int(T))
 
 
+SIGN_MAX_CLIENTS = 128  # FA_SIGN_MAX_CLIENTS
+SIGN_MAJORITY, SIGN_MEAN = 0, 1  # FA_SIGN_MAJORITY, FA_SIGN_MEAN
+SIGN_ELEMENT, SIGN_VECTOR = 0, 1  # sign_form
+
+
+def sign_words(n):
+    """fa_sign_words: ceil(n / 32), the uint32 words of a sign receipt and of a vote plane of n elements."""
+    return lib().fa_sign_words(n)
+
+
+def sign_pack(delta):
+    """fa_sign_pack (host arithmetic, fa.h "Sign-vote stage" rule 2): the sign receipt (np.uint32 words) of the fp32
+    deltas of a whole bucket: the bit is set iff delta < 0."""
+    delta = np.ascontiguousarray(np.asarray(delta, np.float32).reshape(-1))
+    bits = np.empty(sign_words(delta.size), np.uint32)
+    check(lib().fa_sign_pack(delta.ctypes.data, delta.size, bits.ctypes.data))
+    return bits
+
+
+def _sign_ptrs(bits):
+    return (ctypes.c_void_p * max(1, len(bits)))(*[_addr(b) for b in bits])
+
+
+def sign_vote_host(bits, n, eta, rule=SIGN_MAJORITY, margin=1, ref=None, idx0=0, planes=False):
+    """fa_sign_vote_host (host arithmetic, rules 3-9): the fp32 aggregate of bucket elements idx0 .. idx0 + n - 1 from the
+    whole receipts `bits` (np.uint32 arrays) and ref (fp32[n], None: absolute mode); with planes (a, neg, pos)."""
+    bits = [np.ascontiguousarray(np.asarray(b, np.uint32).reshape(-1)) for b in bits]
+    if ref is not None:
+        ref = np.ascontiguousarray(np.asarray(ref, np.float32).reshape(-1))
+    out = np.empty(n, np.float32)
+    neg, pos = (np.empty(sign_words(n), np.uint32), np.empty(sign_words(n), np.uint32)) if planes else (None, None)
+    check(lib().fa_sign_vote_host(_sign_ptrs(bits), len(bits), n, int(idx0), float(eta), int(rule), int(margin), _addr(ref),
+                                  out.ctypes.data, _addr(neg), _addr(pos)))
+    return (out, neg, pos) if planes else out
+
+
+def sign_vote_device(bits, n, out, out_dtype=F32, eta=1.0, rule=SIGN_MAJORITY, margin=1, ref=None, ref_dtype=F32, idx0=0,
+                     neg=None, pos=None, stream=None, gpu=0, ctx=None):
+    """fa_sign_vote_device: out[i] = ref[i] + t_i (ref None: t_i) over n device-resident elements, bucket elements idx0 ..,
+    from the D device-resident whole receipts `bits`; neg, pos: the vote planes (sign_words(n) uint32 words each).
+    Enqueued, not synchronized.  With n == 0 no device is touched: the feature probe."""
+    check(lib().fa_sign_vote_device(ctx.handle if ctx is not None else None, gpu, _sign_ptrs(bits), len(bits), n, int(idx0),
+                                    float(eta), int(rule), int(margin), _addr(ref), ref_dtype, _addr(out), out_dtype,
+                                    _addr(neg), _addr(pos), _stream(stream)))
+
+
+def sign_form(n, bits, out, out_dtype=F32, ref=None, ref_dtype=F32, idx0=0, neg=None, pos=None):
+    """fa_sign_form (host arithmetic on the addresses): SIGN_VECTOR if sign_vote_device takes the vector form for these
+    operands, SIGN_ELEMENT if the element form throughout."""
+    rc = lib().fa_sign_form(n, _sign_ptrs(bits), len(bits), int(idx0), _addr(ref), ref_dtype, _addr(out), out_dtype,
+                            _addr(neg), _addr(pos))
+    return rc if rc >= 0 else check(rc)
+
+
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
     """fa_sync_device: every device bucket in `clients` := sum_k w_k clients[k] (in place, enqueued)."""
     D = len(clients)
@@ -1178,6 +1240,28 @@ class Aggregator:
         signs (+1 / -1)[T]; T = 0 (three empty sequences) is set explicitly."""
         T, keys, nonces, signs = _secagg_terms(keys, nonces, signs)
         check(lib().fa_secagg_set_terms(self.handle, part_id, T, keys.ctypes.data, nonces.ctypes.data, signs.ctypes.data))
+
+    def set_sign(self, part, eta, rule=SIGN_MAJORITY, margin=1, planes=False):
+        """fa_set_sign: the part's rounds are sign votes over one-bit receipts (submit_sign), a_i = g_i + t_i with g the
+        part's last output; eta <= 0 removes the stage.  planes: the reducing calls leave the vote planes."""
+        check(lib().fa_set_sign(self.handle, part, float(eta), int(rule), int(margin), 1 if planes else 0))
+
+    def submit_sign(self, part, slot, bits, pinned=False):
+        """fa_submit_sign: the client's sign receipt (uint32[sign_words(n)]).  pinned: a view of a PinnedBuffer the
+        caller keeps unchanged until the round is reduced."""
+        bits = np.ascontiguousarray(bits)
+        if bits.dtype != np.uint32:
+            raise ValueError("need bits uint32")
+        if part in self.parts and bits.size != sign_words(self.parts[part][0]):
+            raise ValueError("bucket %d expects %d words, got %d" % (part, sign_words(self.parts[part][0]), bits.size))
+        check(lib().fa_submit_sign(self.handle, part, slot, bits.ctypes.data, HOST_PINNED if pinned else 0))
+
+    def copy_sign_planes(self, part):
+        """fa_copy_sign_planes: (neg, pos), the vote planes of the part's last reducing call (uint32[sign_words(n)])."""
+        words = sign_words(self.parts[part][0]) if part in self.parts else 0
+        neg, pos = np.empty(words, np.uint32), np.empty(words, np.uint32)
+        check(lib().fa_copy_sign_planes(self.handle, part, neg.ctypes.data, pos.ctypes.data))
+        return neg, pos
 
     def submit(self, part_id, slot, host, weight=1.0, pinned=False):
         host = np.ascontiguousarray(host)

@@ -301,6 +301,7 @@ int wait_copies(fa_ctx* ctx, int g, hipStream_t s) {
 // output ends here, so this is also where an MX8 part's output becomes the next round's reference.
 void set_range_runs(Part& p, int G) {
     p.mx8.ref = p.mx8.on();
+    p.sign.ref = p.sign.on();
     for (int g = 0; g < G; ++g) {
         p.runs[(size_t)g] = {Run{0, p.off[(size_t)g], p.cnt[(size_t)g]}};
         p.run_src[(size_t)g] = p.dout[(size_t)g];
@@ -790,6 +791,7 @@ int submit_impl(fa_ctx* ctx, int part_id, int slot, const Gather& src, float wei
     int rc = check_part(ctx, part_id, &p);
     if (rc) return rc;
     if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    if (p->sign.on()) return fail(FA_ERR_STATE, "part %d has a sign-vote stage: it takes sign receipts (fa_submit_sign)", part_id);
     if ((rc = src.check("host source"))) return rc;
     const size_t si = dsize(p->in), total = src.total();
     if (total != p->n * si)
@@ -854,6 +856,7 @@ int piece_impl(fa_ctx* ctx, int part_id, int slot, size_t at, const void* src, s
     int rc = check_part(ctx, part_id, &p);
     if (rc) return rc;
     if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    if (p->sign.on()) return fail(FA_ERR_STATE, "part %d has a sign-vote stage: it takes sign receipts (fa_submit_sign)", part_id);
     const size_t si = dsize(p->in);
     if (at > p->n * si || len > p->n * si - at)
         return fail(FA_ERR_ARG, "piece [%zu, %zu) outside part %d's %zu bytes", at, at + len, part_id, p->n * si);
@@ -1600,6 +1603,7 @@ int fa_submit_commit(fa_ctx* ctx, int part_id, int client_slot, float weight) {
     if (rc) return rc;
     if (client_slot < 0 || client_slot >= p->D)
         return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", client_slot, p->D);
+    if (p->sign.on()) return fail(FA_ERR_STATE, "part %d has a sign-vote stage: it takes sign receipts (fa_submit_sign)", part_id);
     if (p->host_src[(size_t)client_slot].size()) {  // an earlier receipt kept in place would shadow the pieces
         p->host_src[(size_t)client_slot].clear();
         --p->n_host;

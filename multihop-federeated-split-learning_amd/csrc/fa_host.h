@@ -274,7 +274,8 @@ struct DevArrays {
 //   bulyan           ready = false                        ready = false      ready = false, if it was on
 //   receipts reply   host_flush, restart_round_plain      nothing            the round stays
 //   secagg           restart_round_plain, no terms        the round stays    the round stays, the terms go
-enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kStages };
+//   sign             reset_round: the receipts go         the round stays    the round stays, the shadows go
+enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kSign, kStages };
 
 struct OptCfg : fa_server_opt {  // fa.h "Server optimizer"
     OptCfg(const fa_server_opt& o = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f}) : fa_server_opt(o) {}
@@ -328,6 +329,12 @@ struct DncCfg {  // fa.h "DnC stage": the owners to remove and P
     int drop = 0, iters = 0;
     bool on() const { return iters != 0; }
 };
+struct SignCfg {  // fa.h "Sign-vote stage": eta, the rule, the margin, whether the rounds leave the planes
+    float eta = 0.0f;
+    int rule = FA_SIGN_MAJORITY, margin = 1;
+    bool planes = false;
+    bool on() const { return eta > 0.0f; }
+};
 struct StageCfgs {
     OptCfg opt;
     ClipCfg clip;
@@ -339,6 +346,7 @@ struct StageCfgs {
     FlagCfg reply;
     SecaggCfg secagg;
     DncCfg dnc;
+    SignCfg sign;
 };
 
 // Per GPU the fp32 state over its cnt elements (v only for the adaptive rules).
@@ -447,12 +455,23 @@ struct DncStage {
     int n = 0;
     bool on() const { return cfg.on(); }
 };
+// ref: the device output holds a reference, as Mx8Stage::ref.  buf: per GPU the sign shadows of its held slots, stride[g]
+// bytes apart (the words of its range from word off >> 5 on), allocated at the first fa_submit_sign.  planes: per GPU
+// the neg plane of its range, then stride[g] bytes on the pos plane, allocated at the first reducing call that leaves
+// them (has_planes: one did since the stage was set).
+struct SignStage {
+    SignCfg cfg;
+    bool ref = false, has_planes = false;
+    DevArrays buf, planes;
+    std::vector<size_t> stride;
+    bool on() const { return cfg.on(); }
+};
 // The stages that are on in a StageCfgs or a Part, one bit per StageId.
 template <class S>
 inline unsigned stages_on(const S& s) {
     return s.opt.on() << kOpt | s.clip.on() << kClip | s.krum.on() << kKrum | s.geomed.on() << kGeomed |
            s.bulyan.on() << kBulyan | s.noise.on() << kNoise | s.mx8.on() << kMx8 | s.reply.on() << kReply | s.secagg.on() << kSecagg |
-           s.dnc.on() << kDnc;
+           s.dnc.on() << kDnc | s.sign.on() << kSign;
 }
 
 struct Part {
@@ -510,6 +529,7 @@ struct Part {
     ReplyStage reply;
     SecaggStage secagg;
     DncStage dnc;
+    SignStage sign;
     DevArrays oavg;
 };
 

@@ -191,6 +191,29 @@ hipError_t launch_secagg(const ClientTable& t, int nc, const uint32_t* tab, int 
 // The mask words on the host (fa_secagg_mask_host): out[0, n) := the words of elements idx0 .. idx0 + n - 1.  The
 // kernel's own rounds.
 void secagg_mask_host(const uint32_t* key, const uint32_t* nonce, uint64_t idx0, size_t n, uint32_t* out);
+// The sign-vote stage (fa.h "Sign-vote stage"), fa_sign.hip.  out[i] (dtype odt, one rounding) := fl32(widen(ref[i]) + t_i),
+// or t_i with ref null, over n elements whose bits are bit i & 31 of word i >> 5 of bits[0..D) (each pointer at the word of
+// the launch's first element, a multiple of 32 of the bucket index); neg, pos (both or neither, majority only): the vote
+// planes, (n + 31) / 32 words each.  (rdt, odt) as dtype_pair_ok(in, out); out may be ref exactly (a lane reads its
+// elements before it writes them).  sp: sign_split of the same operands (host-only): the words before the receipts' 16-byte
+// boundary, the quads of 128 elements the vector form takes, and whether it may (one 16-byte phase of all receipts and of
+// the planes; ref, out 16-byte aligned).
+struct SignSplit {
+    int64_t headw, nq, nwords;
+    bool vec;
+    int64_t tailw0() const { return headw + 4 * nq; }
+    int64_t edge_words() const { return headw + (nwords - tailw0()); }  // words left to the element form
+};
+SignSplit sign_split(const uint32_t* const* bits, int D, size_t n, const void* ref, fa_dtype rdt, const void* out,
+                     fa_dtype odt, const void* neg, const void* pos);
+hipError_t launch_sign_vote(const uint32_t* const* bits, int D, int64_t n, float eta, int rule, int margin, const void* ref,
+                            fa_dtype rdt, void* out, fa_dtype odt, uint32_t* neg, uint32_t* pos, const SignSplit& sp,
+                            const Tuning& tu, hipStream_t s);
+// The rule on the host (fa_sign_pack, fa_sign_vote_host): plain loops; bits[k] are whole receipts, element i is bucket
+// element idx0 + i, ref / out / neg / pos are the range's own.
+void sign_pack_host(const float* delta, size_t n, uint32_t* bits);
+void sign_vote_host(const uint32_t* const* bits, int D, size_t n, uint64_t idx0, float eta, int rule, int margin,
+                    const float* ref, float* out, uint32_t* neg, uint32_t* pos);
 // MX8 receipts (fa.h "MX8 receipts"), fa_mx8.hip.  dst[i] (dtype ddt, one rounding) := fl(widen(ref[i]) + d_i), or d_i
 // without a reference (ref null), over n elements, d_i = fl((float)q[i] * 2^(E - 133)) with E = e[((idx0 + i) >> 5) -
 // (idx0 >> 5)]: e[0] is the scale of the block that bucket element idx0 lies in.  (ddt, rdt) as dtype_pair_ok(in, out).

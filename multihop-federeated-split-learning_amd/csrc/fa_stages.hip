@@ -539,9 +539,14 @@ void free_secagg(fa_ctx* ctx, Part& p) {
     p.secagg.dev.free(ctx->gpu);
     p.secagg = SecaggStage{};
 }
+void free_sign(fa_ctx* ctx, Part& p) {
+    for (DevArrays* a : {&p.sign.buf, &p.sign.planes}) a->free(ctx->gpu);
+    p.sign = SignStage{};
+}
 void free_stages(fa_ctx* ctx, Part& p) {
     p.noise = NoiseStage{};
     free_secagg(ctx, p);
+    free_sign(ctx, p);
     free_mx8(ctx, p);
     free_reply(ctx, p);
     free_opt(ctx, p);
@@ -984,6 +989,106 @@ int secagg_piece(fa_ctx* ctx, Part& p, int g, int j, std::vector<const void*>& p
                      sa.cfg.scale, dst, odt, -1, st);
 }
 
+// ------------------------------------------------------------------ sign-vote stage
+
+int mx8_h2d(GpuRes& r, char* dev, const char* src, size_t bytes, bool pinned);  // below, with the receipts
+
+// The refusals shared by fa_set_sign, fa_sign_vote_device and fa_sign_vote_host.
+int check_sign_params(float eta, int rule, int margin, bool planes) {
+    if (!finite_f(eta) || !(eta > 0.0f)) return fail(FA_ERR_ARG, "sign: eta %g must be finite and > 0", (double)eta);
+    if (rule != FA_SIGN_MAJORITY && rule != FA_SIGN_MEAN) return fail(FA_ERR_ARG, "sign: rule %d is neither FA_SIGN_MAJORITY nor FA_SIGN_MEAN", rule);
+    if (margin < 1 || margin > FA_SIGN_MAX_CLIENTS) return fail(FA_ERR_ARG, "sign: margin %d outside 1 .. D", margin);
+    if (planes && rule == FA_SIGN_MEAN) return fail(FA_ERR_STATE, "sign: the vote planes exist under the majority rule only");
+    return FA_OK;
+}
+int check_sign_clients(int D, int margin) {
+    if (D < 1 || D > FA_SIGN_MAX_CLIENTS) return fail(FA_ERR_ARG, "sign: D = %d clients outside 1 .. %d", D, FA_SIGN_MAX_CLIENTS);
+    if (margin > D) return fail(FA_ERR_ARG, "sign: margin %d outside 1 .. D = %d", margin, D);
+    return FA_OK;
+}
+
+// The words of a range of cnt elements that starts at a multiple of 32, and the bytes of a shadow or a plane of it.
+inline size_t sign_words(size_t cnt) { return (cnt + 31) / 32; }
+inline size_t sign_stride(size_t cnt) { return (sign_words(cnt) * 4 + 255) / 256 * 256; }
+
+// The sign shadows of a part, allocated once: per GPU held x stride bytes.  On failure the part keeps the stage.
+int ensure_sign_buf(fa_ctx* ctx, Part& p) {
+    SignStage& s = p.sign;
+    if (s.buf) return FA_OK;
+    s.stride.clear();
+    for (size_t g = 0; g < (size_t)ctx->G; ++g) s.stride.push_back(sign_stride(p.cnt[g]));
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.stride[g]); };
+    const int g = s.buf.alloc(ctx->gpu, bytes);
+    if (g < 0) return FA_OK;
+    return fail(FA_ERR_NOMEM, "sign: shadow alloc of %zu B failed on GPU %zu", bytes((size_t)g), (size_t)g);
+}
+
+int submit_sign_impl(fa_ctx* ctx, int part_id, int slot, const uint32_t* bits, int flags) {
+    Trace tr("fa_submit_sign part %d slot %d", part_id, slot);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (flags & ~FA_HOST_PINNED) return fail(FA_ERR_ARG, "sign: unknown flags 0x%x", flags);
+    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    if (!p->sign.on()) return fail(FA_ERR_STATE, "sign: part %d has no sign-vote stage (fa_set_sign)", part_id);
+    if (p->n > 0 && !bits) return fail(FA_ERR_ARG, "sign: bits is null");
+    if ((rc = ensure_sign_buf(ctx, *p))) return rc;
+    const bool pinned = (flags & FA_HOST_PINNED) != 0;
+    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        const size_t off = p->off[(size_t)g], cnt = p->cnt[(size_t)g];
+        if (cnt == 0) return FA_OK;
+        // after the part's last reducing call: it read the shadow
+        if (hipStream_t ds = p->done_stream[(size_t)g]) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(r.copy, p->done[(size_t)g], 0));
+        }
+        char* db = p->sign.buf.at((size_t)g) + (size_t)(slot - p->c0[(size_t)g]) * p->sign.stride[(size_t)g];
+        ++r.copy_gen;  // the next reducing call waits for the copy stream
+        return mx8_h2d(r, db, reinterpret_cast<const char*>(bits + (off >> 5)), sign_words(cnt) * 4, pinned);
+    });
+    if (rc) return rc;
+    return mark_submitted(ctx, *p, slot, 1.0f);
+}
+
+// The vote on the current device over n elements: bits[k] at the word of the first one, a multiple of 32 of the bucket.
+int sign_on(const fa::Tuning& tu, const uint32_t* const* bits, int D, size_t n, const SignCfg& c, const void* ref,
+            fa_dtype rdt, void* dst, fa_dtype odt, uint32_t* neg, uint32_t* pos, hipStream_t s) {
+    const fa::SignSplit sp = fa::sign_split(bits, D, n, ref, rdt, dst, odt, neg, pos);
+    FA_HIP(fa::launch_sign_vote(bits, D, (int64_t)n, c.eta, c.rule, c.margin, ref, rdt, dst, odt, neg, pos, sp, tu, s));
+    return FA_OK;
+}
+
+// Before the round's launches: the receipts are there, and the planes' arrays if the round leaves them.
+int sign_round_begin(fa_ctx* ctx, Part& p) {
+    SignStage& s = p.sign;
+    if (!s.buf) return fail(FA_ERR_STATE, "sign: part %d has no sign receipts (fa_submit_sign)", p.id);
+    for (size_t g = 0; g < (size_t)ctx->G; ++g)
+        if (p.off[g] % 64 || (p.npiece[g] > 1 && p.piece_len[g] % 64))
+            return fail(FA_ERR_STATE, "sign: part %d is not cut at multiples of 64 elements", p.id);
+    if (!s.cfg.planes || s.planes) return FA_OK;
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, 2 * s.stride[g]); };
+    const int g = s.planes.alloc(ctx->gpu, bytes);
+    if (g < 0) return FA_OK;
+    return fail(FA_ERR_NOMEM, "sign: plane alloc of %zu B failed on GPU %zu", bytes((size_t)g), (size_t)g);
+}
+
+// Rules 3-9 for piece j of GPU g (the current device), into dst (dtype odt): every client's shadow, the reference in
+// the part's output (dst itself where the aggregate is reduced in place).
+int sign_piece(fa_ctx* ctx, Part& p, int g, int j, void* dst, fa_dtype odt, hipStream_t st) {
+    const SignStage& s = p.sign;
+    const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
+    if (cnt == 0) return FA_OK;
+    std::vector<const uint32_t*> bits((size_t)p.D);
+    for (int k = 0; k < p.D; ++k)
+        bits[(size_t)k] = s.buf.at<uint32_t>((size_t)g) + (size_t)k * (s.stride[(size_t)g] / 4) + (lo >> 5);
+    const void* ref = s.ref ? static_cast<const char*>(p.dout[(size_t)g]) + lo * dsize(p.out) : nullptr;
+    uint32_t* neg = s.cfg.planes ? s.planes.at<uint32_t>((size_t)g) + (lo >> 5) : nullptr;
+    return sign_on(ctx->tuning.tu, bits.data(), p.D, cnt, s.cfg, ref, p.out, dst, odt, neg,
+                   neg ? neg + s.stride[(size_t)g] / 4 : nullptr, st);
+}
+
 // ------------------------------------------------------------------ one reducing call, as the stages see it
 
 int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, StageRound* rd) {
@@ -1010,6 +1115,7 @@ int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, Stage
     if (p.geomed.on()) return geomed_plan(ctx, p, w, s, &rd->plan);
     if (p.bulyan.on()) return bulyan_plan(ctx, p, s, &rd->plan);
     if (p.secagg.on()) return secagg_round_begin(ctx, p, s);
+    if (p.sign.on()) return sign_round_begin(ctx, p);
     return FA_OK;
 }
 
@@ -1033,6 +1139,8 @@ int stage_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, const StageR
         rc = bulyan_piece(ctx, p, g, j, rd.plan, adst, adt, st);
     else if (p.secagg.on())
         rc = secagg_piece(ctx, p, g, j, ptrs, adst, adt, st);
+    else if (p.sign.on())
+        rc = sign_piece(ctx, p, g, j, adst, adt, st);
     else
         rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                        mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
@@ -1064,6 +1172,7 @@ void stage_round_end(Part& p) {
     if (p.clip.on()) p.clip.has_ref = true;  // what this round sent out
     if (p.noise.on()) ++p.noise.round;       // one reducing call = one round of the generator
     if (p.secagg.on()) p.secagg.have = false;  // terms are per round: a stale list is never applied
+    if (p.sign.on()) p.sign.has_planes = p.sign.cfg.planes;
 }
 
 // ------------------------------------------------------------------ setting a stage on a part
@@ -1290,8 +1399,34 @@ int set_part_secagg(fa_ctx* ctx, Part& p, const SecaggCfg& c) {
     return FA_OK;
 }
 
+// fa_set_sign on a part (the numbers checked; an FA_FEDAVG part, not rs).  Off: the shadows and the planes go, after the
+// devices' pending work.  A part that has the stage: the numbers change; planes that are no longer asked for go.  Else
+// what the round received so far is dropped: dense receipts are no sign receipts.
+int set_part_sign(fa_ctx* ctx, Part& p, const SignCfg& c) {
+    if (c.on() && c.planes && (p.opt.on() || p.noise.on()))
+        return fail(FA_ERR_STATE, "sign: part %d has a %s stage: its reply is no function of the vote planes", p.id,
+                    p.opt.on() ? "server-optimizer" : "noise");
+    if (!c.on() || (p.sign.on() && p.sign.cfg.planes && !c.planes)) {
+        if (p.sign.on())
+            if (int rc = wait_devices(ctx)) return rc;
+        if (!c.on()) {
+            free_sign(ctx, p);
+            return FA_OK;
+        }
+        p.sign.planes.free(ctx->gpu);
+        p.sign.has_planes = false;
+    }
+    if (!p.sign.on()) {
+        if (int rc = host_flush(ctx, p)) return rc;
+        reset_round(p);
+    }
+    p.sign.cfg = c;
+    return FA_OK;
+}
+
 int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
     switch (id) {
+        case kSign: return set_part_sign(ctx, p, c.sign);
         case kOpt: return set_part_opt(ctx, p, c.opt);
         case kClip: return set_part_clip(ctx, p, c.clip);
         case kKrum: return set_part_select(p, p.krum, c.krum);
@@ -1329,12 +1464,14 @@ const StageRule kRules[kStages] = {
     {"bulyan", "Bulyan", kTrim, false, 0, "the rule needs every client on one GPU; use FA_SHARD_RANGE",
      " (the stage replaces the window of an FA_TRIMMED part)"},
     {"noise", "noise", kAvg | kTrim, false, 0, "its aggregate is not bit-specified; use FA_SHARD_RANGE", ""},
-    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
+    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg | 1u << kSign, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
     {"mx8 reply", "reply", kAvg | kTrim, false, 0, "use FA_SHARD_RANGE", ""},
     {"secagg", "secagg", kAvg, true, 1u << kMx8, "its sum is taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage unmasks the sum of an FA_FEDAVG part)"},
     {"dnc", "DnC", kAvg, true, 0, "a Gram entry needs both clients on one GPU; use FA_SHARD_RANGE",
      " (the stage selects the owners of an FA_FEDAVG average)"},
+    {"sign", "sign-vote", kAvg, true, 1u << kMx8, "its counts are taken over every client of an element; use FA_SHARD_RANGE",
+     " (the stage votes on the updates of an FA_FEDAVG part)"},
 };
 
 // The request "turn stage id on (or off), on the context default (part_id < 0, *out = null) or on this part (*out)"
@@ -1362,6 +1499,8 @@ int admit(fa_ctx* ctx, StageId id, bool on, int part_id, Part** out) {
     for (int o = 0; p && o < kStages; ++o)  // masked words are no MX8 deltas, and MX8 slots hold no masked words
         if (have & r.never & (1u << o))
             return fail(FA_ERR_ARG, "%s: part %d has a %s stage (the two stages do not compose)", r.name, part_id, kRules[o].title);
+    if ((id == kOpt || id == kNoise) && p && p->sign.on() && p->sign.cfg.planes)
+        return fail(FA_ERR_STATE, "%s: part %d leaves vote planes (fa_set_sign): its reply would be no function of them", r.name, part_id);
     if (id == kSecagg && p && p->in != FA_F32)
         return fail(FA_ERR_ARG, "secagg: part %d has %s slots (masked uint32 words lie in FA_F32 slots)", part_id, fa::dtype_name(p->in));
     if (id == kSecagg && p && (uint64_t)p->n > kSecaggMaxIndex)
@@ -1374,6 +1513,7 @@ int check_for_clients(StageId id, int D, StageCfgs& c) {
     if (id == kKrum) return check_krum(D, c.krum.f, c.krum.m, &c.krum.m);
     if (id == kGeomed) return check_geomed(D, c.geomed.iters, c.geomed.nu);
     if (id == kDnc) return check_dnc(D, c.dnc.drop, c.dnc.iters);
+    if (id == kSign) return check_sign_clients(D, c.sign.margin);
     return id == kBulyan ? check_bulyan(D, c.bulyan.f) : FA_OK;
 }
 
@@ -2297,6 +2437,138 @@ int fa_secagg_quantize(const float* v, size_t n, float q, int32_t* out, uint64_t
 
 int fa_secagg_form(size_t n, int T) { return fa::secagg_form((int64_t)n, T); }
 
+size_t fa_sign_words(size_t n) { return n / 32 + (n % 32 ? 1 : 0); }
+
+int fa_sign_pack(const float* delta, size_t n, uint32_t* bits) {
+    g_err.clear();
+    if (n == 0) return FA_OK;
+    if (!delta || !bits) return fail(FA_ERR_ARG, "sign: %s is null", !delta ? "delta" : "bits");
+    fa::sign_pack_host(delta, n, bits);
+    return FA_OK;
+}
+
+// What fa_sign_vote_host and fa_sign_vote_device refuse before they look at a pointer's target.
+static int check_sign_vote(int D, size_t n, uint64_t idx0, float eta, int rule, int margin, const void* neg, const void* pos) {
+    if (int rc = check_sign_clients(D, 1)) return rc;
+    if ((neg == nullptr) != (pos == nullptr)) return fail(FA_ERR_ARG, "sign: %s plane without the other", neg ? "the neg" : "the pos");
+    if (int rc = check_sign_params(eta, rule, margin, false)) return rc;
+    if (neg && rule == FA_SIGN_MEAN) return fail(FA_ERR_ARG, "sign: the vote planes exist under the majority rule only");
+    if (int rc = check_sign_clients(D, margin)) return rc;
+    if (idx0 % 32) return fail(FA_ERR_ARG, "sign: idx0 %llu is no multiple of 32", (unsigned long long)idx0);
+    if (idx0 + (uint64_t)n < idx0) return fail(FA_ERR_ARG, "sign: idx0 + n beyond 2^64");
+    return FA_OK;
+}
+
+int fa_sign_vote_host(const uint32_t* const* bits, int D, size_t n, uint64_t idx0, float eta, int rule, int margin,
+                      const float* ref, float* out, uint32_t* neg, uint32_t* pos) {
+    g_err.clear();
+    if (int rc = check_sign_vote(D, n, idx0, eta, rule, margin, neg, pos)) return rc;
+    if (n == 0) return FA_OK;
+    if (int rc = check_clients(reinterpret_cast<const void* const*>(bits), D, 4, "receipt")) return rc;
+    if (!out) return fail(FA_ERR_ARG, "sign: out is null");
+    fa::sign_vote_host(bits, D, n, idx0, eta, rule, margin, ref, out, neg, pos);
+    return FA_OK;
+}
+
+// The receipts at the word of idx0 (into at), after the checks of the pointers fa_sign_vote_device and fa_sign_form share.
+static int sign_operands(const uint32_t* const* d_bits, int D, uint64_t idx0, const void* d_ref, fa_dtype rdt, const void* d_out,
+                         fa_dtype odt, const void* d_neg, const void* d_pos, std::vector<const uint32_t*>* at) {
+    if (int rc = check_clients(reinterpret_cast<const void* const*>(d_bits), D, 4, "receipt")) return rc;
+    if (!d_out) return fail(FA_ERR_ARG, "output pointer is null");
+    if (d_ref && !aligned(d_ref, dsize(rdt))) return fail(FA_ERR_ALIGN, "sign: reference not %zu-byte aligned", dsize(rdt));
+    if (!aligned(d_out, dsize(odt))) return fail(FA_ERR_ALIGN, "output not %zu-byte aligned", dsize(odt));
+    if (d_neg && (!aligned(d_neg, 4) || !aligned(d_pos, 4))) return fail(FA_ERR_ALIGN, "sign: planes not 4-byte aligned");
+    at->resize((size_t)D);
+    for (int k = 0; k < D; ++k) (*at)[(size_t)k] = d_bits[k] + (idx0 >> 5);
+    return FA_OK;
+}
+
+int fa_sign_vote_device(fa_ctx* ctx, int gpu, const uint32_t* const* d_bits, int D, size_t n, uint64_t idx0, float eta,
+                        int rule, int margin, const void* d_ref, fa_dtype ref_dtype, void* d_out, fa_dtype out_dtype,
+                        uint32_t* d_neg, uint32_t* d_pos, void* hip_stream) {
+    g_err.clear();
+    // every check before any device call: with n == 0 this is the feature probe of a box without a GPU
+    if (!dvalid(out_dtype) || !dvalid(ref_dtype)) return fail(FA_ERR_ARG, "bad dtype");
+    FA_PAIR(ref_dtype, out_dtype);
+    if (int rc = check_sign_vote(D, n, idx0, eta, rule, margin, d_neg, d_pos)) return rc;
+    if (ctx && (gpu < 0 || gpu >= ctx->G)) return fail(FA_ERR_ARG, "gpu %d out of range", gpu);
+    if (n == 0) return FA_OK;
+    std::vector<const uint32_t*> at;
+    if (int rc = sign_operands(d_bits, D, idx0, d_ref, ref_dtype, d_out, out_dtype, d_neg, d_pos, &at)) return rc;
+    if (d_ref) {
+        const uintptr_t o = (uintptr_t)d_out, r = (uintptr_t)d_ref;
+        if (o < r + n * dsize(ref_dtype) && r < o + n * dsize(out_dtype)) return fail(FA_ERR_ARG, "sign: d_out overlaps d_ref");
+    }
+    const DeviceCall c = device_call(ctx, gpu, hip_stream);
+    DeviceGuard dg(c.dev);
+    SignCfg cfg;
+    cfg.eta = eta;
+    cfg.rule = rule;
+    cfg.margin = margin;
+    return sign_on(c.tu, at.data(), D, n, cfg, d_ref, ref_dtype, d_out, out_dtype, d_neg, d_pos, c.s);
+}
+
+int fa_sign_form(size_t n, const uint32_t* const* d_bits, int D, uint64_t idx0, const void* d_ref, fa_dtype ref_dtype,
+                 const void* d_out, fa_dtype out_dtype, const void* d_neg, const void* d_pos) {
+    g_err.clear();
+    if (!dvalid(out_dtype) || !dvalid(ref_dtype)) return fail(FA_ERR_ARG, "bad dtype");
+    if (int rc = check_sign_clients(D, 1)) return rc;
+    if (idx0 % 32) return fail(FA_ERR_ARG, "sign: idx0 %llu is no multiple of 32", (unsigned long long)idx0);
+    std::vector<const uint32_t*> at;
+    if (int rc = sign_operands(d_bits, D, idx0, d_ref, ref_dtype, d_out, out_dtype, d_neg, d_pos, &at)) return rc;
+    return fa::sign_split(at.data(), D, n, d_ref, ref_dtype, d_out, out_dtype, d_neg, d_pos).vec ? 1 : 0;
+}
+
+int fa_set_sign(fa_ctx* ctx, int part_id, float eta, int rule, int margin, int planes) {
+    g_err.clear();
+    StageCfgs c = requested(ctx);
+    c.sign = SignCfg{};
+    if (eta > 0.0f || eta != eta) {  // <= 0 turns the stage off
+        if (int rc = check_sign_params(eta, rule, margin, planes != 0)) return rc;
+        if (ctx && part_id < 0)
+            return fail(FA_ERR_ARG, "sign: set on a part, not as a context default (a round's receipts belong to one part)");
+        c.sign.eta = eta;
+        c.sign.rule = rule;
+        c.sign.margin = margin;
+        c.sign.planes = planes != 0;
+    }
+    return set_stage(ctx, part_id, kSign, c);
+}
+
+int fa_submit_sign(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* bits, int flags) {
+    g_err.clear();
+    return submit_sign_impl(ctx, part_id, client_slot, bits, flags);
+}
+
+int fa_copy_sign_planes(fa_ctx* ctx, int part_id, uint32_t* neg, uint32_t* pos) {
+    g_err.clear();
+    Part* p;
+    if (int rc = check_part(ctx, part_id, &p)) return rc;
+    if (!p->sign.on() || !p->sign.has_planes || !p->sign.planes)
+        return fail(FA_ERR_STATE, "sign: part %d has no vote planes (%s)", part_id,
+                    !p->sign.on() ? "no sign-vote stage" : "fa_set_sign without planes, or no reducing call since");
+    if (p->n && (!neg || !pos)) return fail(FA_ERR_ARG, "sign: %s is null", !neg ? "neg" : "pos");
+    for (int g = 0; g < ctx->G; ++g) {  // ordered after the reducing call as copy_output is
+        GpuRes& r = ctx->gpu[(size_t)g];
+        const size_t cnt = p->cnt[(size_t)g], w0 = p->off[(size_t)g] >> 5, bytes = sign_words(cnt) * 4;
+        if (!cnt) continue;
+        DeviceGuard dg(r.dev);
+        hipStream_t ds = p->done_stream[(size_t)g];
+        if (ds && ds != r.compute) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(r.compute, p->done[(size_t)g], 0));
+        }
+        const char* src = p->sign.planes.at((size_t)g);
+        FA_HIP(hipMemcpyAsync(neg + w0, src, bytes, hipMemcpyDeviceToHost, r.compute));
+        FA_HIP(hipMemcpyAsync(pos + w0, src + p->sign.stride[(size_t)g], bytes, hipMemcpyDeviceToHost, r.compute));
+    }
+    for (int g = 0; g < ctx->G; ++g) {
+        DeviceGuard dg(ctx->gpu[(size_t)g].dev);
+        FA_HIP(hipStreamSynchronize(ctx->gpu[(size_t)g].compute));
+    }
+    return FA_OK;
+}
+
 size_t fa_mx8_scale_bytes(size_t n) { return n / FA_MX8_BLOCK + (n % FA_MX8_BLOCK ? 1 : 0); }
 
 int fa_mx8_encode(const float* delta, size_t n, int8_t* q, uint8_t* e) {
@@ -2407,9 +2679,10 @@ int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
     g_err.clear();
     Part* p;
     if (int rc = check_part(ctx, part_id, &p)) return rc;
-    if (!p->mx8.on() && !p->reply.on())
+    if (!p->mx8.on() && !p->reply.on() && !p->sign.on())
         return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
-                                  "(fa_set_mx8_reply), nor takes top-k (fa_set_topk), low-rank (fa_set_lowrank) or rot1 receipts (fa_set_rot1)", part_id);
+                                  "(fa_set_mx8_reply), nor takes top-k (fa_set_topk), low-rank (fa_set_lowrank) or rot1 receipts (fa_set_rot1), "
+                                  "nor has a sign-vote stage (fa_set_sign)", part_id);
     if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
     if (int rc = wait_devices(ctx)) return rc;  // the part's pending work, on whatever stream
     if (p->reply.on())
