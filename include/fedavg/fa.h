@@ -573,6 +573,47 @@
  *              allocated (not allocating them is left for later).
  *              Added without a new FA_ABI_VERSION: fa_sign_vote_device with n == 0 touches no device and answers FA_OK
  *              -- that is how a caller probes for it.
+ *   Sparse-sum stage (fa_set_sparse_sum, fa_submit_sparse, fa_sparse_sum_device, fa_sparse_sum_host,
+ *              fa_sparse_sum_workspace, fa_sparse_sum_form): a round of top-k receipts reduced without expanding them.
+ *              sum_c w_c (g + d_c) touches only elements that some owner named, so the round reads the (idx, val) pairs,
+ *              8 sum_c k_c bytes, and one dense pass over g, where the expanded route moves 12 D + 4 bytes per element.
+ *              Format: the top-k receipt, unchanged (fa_topk_encode and fa_topk_encode_device stay the owner's side): idx
+ *              is k strictly ascending uint32, each < n, a position in the whole bucket; val is k fp32.  1 <= D <=
+ *              FA_SPARSE_MAX_CLIENTS; 0 <= k_c <= n per client and k_c <= 2^32 - 1 (the kernel's tables count in 32-bit
+ *              words: the one receipt that names all 2^32 elements of a bucket of 2^32 is a dense one); n <= 2^32 where
+ *              any receipt has entries.
+ *              1. Sum.  Per element i: acc = +0; for the clients c in ascending client order that have an entry (i, d):
+ *                 acc = fmaf(w_c, d, acc), one fused operation, as in the FA_FEDAVG chain.  Clients without an entry at i
+ *                 are skipped, not added as +0.  The one consequence: a partial sum of -0 stays -0, where a chain over
+ *                 expanded slots would turn it into +0 at the next client; a partial sum can only be -0 if an exact
+ *                 product underflows to zero (a product that is exactly -0 gives -0 + +0 = +0).
+ *              2. Aggregate.  a_i = fl32(widen(g_i) + acc_i): one IEEE add, never contracted with rule 1; g widened
+ *                 exactly (bf16; fp16 with its subnormals).  The same add is done for elements nobody named, so -0 + +0 =
+ *                 +0.  Without a reference (absolute mode) a_i = acc_i.  NaN and inf in val, w or g follow IEEE rules
+ *                 (0 * inf is NaN); NaN payloads are unspecified.
+ *              3. Weights.  The weights are the owners' shares of the *update*; the reference enters with weight one.  In
+ *                 real arithmetic this is the expanded route's result, sum_c w_c (g + d_c), exactly when sum w_c = 1; it
+ *                 is not the same bits (the expanded route rounds g + d_c per owner, this one the sum of the updates).
+ *                 Any finite or non-finite fp32 weight is taken as given.
+ *              4. Place in the round.  a stands exactly where the chain's result stands: it feeds the noise stage and the
+ *                 server optimizer if the part has them, otherwise it is rounded once to the out dtype; MX8 replies, range
+ *                 shards, range pieces and fa_reduce_parts work as for any part.  The reference g is the part's device
+ *                 output as the last reducing call with the stage left it, exactly the reference of MX8 receipts
+ *                 (fa_mx8_set_reference sets it).  A round on a part without a reference runs in absolute mode.
+ *              5. Layout independence.  Every element's arithmetic is a fixed sequence that depends on no tile, grid, shard
+ *                 or piece: every output is the same bits for any GPU count, pieces, pointer phase or kernel form.
+ *              6. Admission.  Only on an FA_FEDAVG part.  The stage belongs to the measure-then-select family: not with
+ *                 the clip, Krum, DnC, geomed, secagg or sign stage (Bulyan needs an FA_TRIMMED part), and not with any of
+ *                 the four receipt formats (those setters refuse a sparse-sum part in turn).  Not on an
+ *                 FA_SHARD_CLIENT_RS context, not as a context default.  Like the other stage parts the part is never kept
+ *                 host-side, FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager, and a reducing call needs every client
+ *                 submitted, with fa_submit_sparse: a dense fa_submit to such a part is FA_ERR_STATE.  Setting the stage
+ *                 on a part drops what the round had received so far.
+ *              Memory: per GPU and client slot a shadow of min(k_max, cnt) * 8 bytes, rounded up to 256, and per GPU one
+ *              workspace of fa_sparse_sum_workspace(cnt, D) bytes.  The part's dense slots are neither read nor written
+ *              by such a round; they stay allocated (not allocating them is left for later).
+ *              Added without a new FA_ABI_VERSION: fa_sparse_sum_device with n == 0 touches no device and answers FA_OK
+ *              -- that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -1391,6 +1432,53 @@ int fa_submit_sign(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* bi
 /* The planes of the part's last reducing call into host arrays of fa_sign_words(n) words each, waiting for it.
  * FA_ERR_STATE on a part without planes or not yet reduced with them. */
 int fa_copy_sign_planes(fa_ctx* ctx, int part_id, uint32_t* neg, uint32_t* pos);
+
+/* Sparse-sum stage (the header comment, "Sparse-sum stage"): top-k receipts reduced on the GPU without expanding them. */
+#define FA_SPARSE_MAX_CLIENTS 128
+/* fa_sparse_sum_form: a bit each. */
+#define FA_SPARSE_VECTOR 1   /* the dense side moves 16 bytes per access wherever a lane lies inside the launch */
+#define FA_SPARSE_BIG_TILE 2 /* a wave owns 8192 elements, not 2048: densities below 1 / 2048 */
+/* Rules 1-2 on the host, usable without a device: out[i] (fp32, n elements) is the aggregate of bucket element idx0 + i
+ * from the receipts (idx[c], val[c]) of k[c] entries under w[c], c < D, and ref (fp32, n elements, NULL = absolute mode).
+ * Entries outside [idx0, idx0 + n) are skipped.  FA_ERR_ARG as fa_sparse_sum_device. */
+int fa_sparse_sum_host(const uint32_t* const* idx, const float* const* val, const size_t* k, const float* w, int D, size_t n,
+                       uint64_t idx0, const float* ref, float* out);
+/* The bytes of d_work for one fa_sparse_sum_device over n elements and D clients. */
+size_t fa_sparse_sum_workspace(size_t n, int D);
+/* Rules 1-2 on raw device pointers over bucket elements idx0 .. idx0 + n - 1: d_out[i] (n of out_dtype, one rounding)
+ * from d_ref (n of ref_dtype, NULL = absolute mode) and the receipts: d_idx[c] and d_val[c] are client c's k[c] entries,
+ * the whole bucket's or a range's (entries outside the range are skipped); the arrays d_idx, d_val, k and w themselves
+ * are host memory and are read before the call returns.  d_work: fa_sparse_sum_workspace(n, D) bytes, 16-byte aligned,
+ * not initialised, the call's own until it has run.  ctx may be NULL (then `gpu` is the HIP device).  Every argument is
+ * checked before any device call: 1 <= D <= FA_SPARSE_MAX_CLIENTS, the dtypes and their pair (bf16 <-> f16: FA_ERR_ARG),
+ * idx0 + n < 2^64 (and <= 2^32 where a receipt has entries), k[c] <= 2^32 - 1, and for n > 0 null pointers, alignment
+ * (FA_ERR_ALIGN: idx and val 4 bytes, d_ref and d_out their element, d_work 16) and that d_out does not overlap d_ref;
+ * with n == 0 and valid arguments it returns FA_OK without touching a device.  Ascending order is the caller's
+ * obligation, as in fa_topk_expand_device: with unsorted or repeated indices the values are unspecified, nothing is
+ * written outside d_out[0, n) and nothing is read outside idx[0, k) and val[0, k).  Async on hip_stream (NULL = the ctx's
+ * compute stream of `gpu`, or the null stream).  Any phase of the pointers is correct (fa_sparse_sum_form). */
+int fa_sparse_sum_device(fa_ctx* ctx, int gpu, const uint32_t* const* d_idx, const float* const* d_val, const size_t* k,
+                         const float* w, int D, size_t n, uint64_t idx0, const void* d_ref, fa_dtype ref_dtype, void* d_out,
+                         fa_dtype out_dtype, void* d_work, void* hip_stream);
+/* Which form fa_sparse_sum_device takes for these operands: FA_SPARSE_VECTOR if d_ref and d_out agree on a common head
+ * before their 16-byte boundaries (else the dense side goes element by element), FA_SPARSE_BIG_TILE by the density
+ * sum k / (D n).  Pure host arithmetic on the counts and the pointer values; the bits do not depend on it. */
+int fa_sparse_sum_form(size_t n, const size_t* k, int D, const void* d_ref, fa_dtype ref_dtype, const void* d_out,
+                       fa_dtype out_dtype);
+/* Gives a part the stage (part_id >= 0): its rounds take top-k receipts of at most k_max entries (fa_submit_sparse) and
+ * reduce them by rules 1-2 against the part's last output; again: k_max changes, the shadows are allocated anew, the round
+ * under way is dropped if they were in use, and the reference stays (rule 4).  k_max == 0 removes the stage and frees what it allocated.  FA_ERR_ARG, naming
+ * the cause: D > FA_SPARSE_MAX_CLIENTS, part_id < 0 (no context default), a part whose mode is not FA_FEDAVG, a part with
+ * a clip, Krum, DnC, geomed, secagg, sign or receipt stage (those setters refuse a sparse-sum part in turn), an
+ * FA_SHARD_CLIENT_RS context.  No density limit is enforced: in DESIGN.md 8p the stage beats the expanded route at every
+ * density measured, k = n / 1000 to n / 10; nothing above n / 10 was measured. */
+int fa_set_sparse_sum(fa_ctx* ctx, int part_id, size_t k_max);
+/* The top-k receipt of client `client_slot`: k <= k_max entries, idx strictly ascending and < n (checked on the host:
+ * FA_ERR_ARG naming the entry, the round stays as it was), under `weight` (rule 3).  flags: FA_HOST_PINNED as for
+ * fa_submit_topk.  Per GPU enqueues the H2D of the entries of its range into the slot's shadow (allocated at the part's
+ * first submit); the slot then counts as submitted.  FA_ERR_STATE on a part without fa_set_sparse_sum. */
+int fa_submit_sparse(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* idx, const float* val, size_t k, float weight,
+                     int flags);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

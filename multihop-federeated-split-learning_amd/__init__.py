@@ -172,6 +172,13 @@ def lib():
         "fa_set_sign": (I, [P, I, F, I, I, I]),
         "fa_submit_sign": (I, [P, I, I, P, I]),
         "fa_copy_sign_planes": (I, [P, I, P, P]),
+        "fa_sparse_sum_host": (I, [P, P, P, P, I, S, U64, P, P]),
+        "fa_sparse_sum_workspace": (S, [S, I]),
+        "fa_sparse_sum_device": (I, [P, I, P, P, P, P, I, S, U64, P, I, P, I, P, P]),
+        "fa_diag_sparse_sum": (I, [P, I, P, P, P, P, I, S, U64, P, I, P, I, P, I, P]),  # diagnostic (outside fa.h)
+        "fa_sparse_sum_form": (I, [S, P, I, P, I, P, I]),
+        "fa_set_sparse_sum": (I, [P, I, S]),
+        "fa_submit_sparse": (I, [P, I, I, P, P, S, F, I]),
         "fa_diag_secagg_unmask": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, I, P]),  # diagnostic (outside fa.h)
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
@@ -858,6 +865,70 @@ def sign_form(n, bits, out, out_dtype=F32, ref=None, ref_dtype=F32, idx0=0, neg=
     return rc if rc >= 0 else check(rc)
 
 
+SPARSE_MAX_CLIENTS = 128  # FA_SPARSE_MAX_CLIENTS
+SPARSE_VECTOR, SPARSE_BIG_TILE = 1, 2  # sparse_sum_form: a bit each
+SPARSE_TILES = (2048, 8192)  # the elements a wave owns: the small tile, the big one (densities below 1 / 2048)
+SPARSE_GROUP = 4  # the clients whose first entries a wave keeps in flight
+
+
+def _sparse_args(idx, val, k, weights):
+    """The pointer arrays, the counts and the weights of D receipts (idx[c], val[c]) of k[c] entries.  Returns ctypes
+    arrays, which the caller keeps until the call returns."""
+    D = len(idx)
+    if len(val) != D or len(k) != D:
+        raise ValueError("need one val and one count per idx")
+    w = np.ascontiguousarray(np.ones(D) if weights is None else weights, np.float32).reshape(-1)
+    if w.size != D:
+        raise ValueError("need one weight per client")
+    pi = (ctypes.c_void_p * max(1, D))(*[_addr(x) for x in idx])
+    pv = (ctypes.c_void_p * max(1, D))(*[_addr(x) for x in val])
+    return pi, pv, (ctypes.c_size_t * max(1, D))(*[int(x) for x in k]), w, D
+
+
+def sparse_sum_host(idx, val, n, weights=None, ref=None, idx0=0):
+    """fa_sparse_sum_host (host arithmetic, fa.h "Sparse-sum stage" rules 1-2): the fp32 aggregate of bucket elements idx0 ..
+    idx0 + n - 1 from the receipts (idx[c] np.uint32 ascending, val[c] np.float32) under `weights` (None: ones) and ref
+    (fp32[n], None: absolute mode)."""
+    idx = [np.ascontiguousarray(np.asarray(i, np.uint32).reshape(-1)) for i in idx]
+    val = [np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1)) for v in val]
+    if [i.size for i in idx] != [v.size for v in val]:
+        raise ValueError("idx and val differ in length")
+    pi, pv, k, w, D = _sparse_args(idx, val, [v.size for v in val], weights)
+    if ref is not None:
+        ref = np.ascontiguousarray(np.asarray(ref, np.float32).reshape(-1))
+    out = np.empty(n, np.float32)
+    check(lib().fa_sparse_sum_host(pi, pv, k, w.ctypes.data, D, n, int(idx0), _addr(ref), out.ctypes.data))
+    return out
+
+
+def sparse_sum_workspace(n, D):
+    """fa_sparse_sum_workspace: the bytes of sparse_sum_device's scratch for n elements and D clients."""
+    return lib().fa_sparse_sum_workspace(n, int(D))
+
+
+def sparse_sum_device(idx, val, k, n, out, work, out_dtype=F32, weights=None, ref=None, ref_dtype=F32, idx0=0, tile=None,
+                      stream=None, gpu=0, ctx=None):
+    """fa_sparse_sum_device: out[i] = ref[i] + sum_c w_c d_c,i (ref None: the sum) over n device-resident elements, bucket
+    elements idx0 .., from the D device-resident receipts (idx[c], val[c]) of k[c] entries; work: sparse_sum_workspace(n, D) bytes of device
+    scratch.  tile: None, or 0 / 1 to force the small / the big tile (the diagnostic entry; the same bits).  Enqueued, not
+    synchronized.  With n == 0 no device is touched: the feature probe."""
+    pi, pv, k, w, D = _sparse_args(idx, val, k, weights)
+    args = [ctx.handle if ctx is not None else None, gpu, pi, pv, k, w.ctypes.data, D, n, int(idx0), _addr(ref), ref_dtype,
+            _addr(out), out_dtype, _addr(work)]
+    if tile is None:
+        check(lib().fa_sparse_sum_device(*args, _stream(stream)))
+    else:
+        check(lib().fa_diag_sparse_sum(*args, int(tile), _stream(stream)))
+
+
+def sparse_sum_form(n, k, out, out_dtype=F32, ref=None, ref_dtype=F32):
+    """fa_sparse_sum_form (host arithmetic on the counts k and the addresses): SPARSE_VECTOR if the dense side of
+    sparse_sum_device takes 16-byte accesses for these operands, SPARSE_BIG_TILE if a wave owns the big tile."""
+    kk = (ctypes.c_size_t * max(1, len(k)))(*[int(x) for x in k])
+    rc = lib().fa_sparse_sum_form(n, kk, len(k), _addr(ref), ref_dtype, _addr(out), out_dtype)
+    return rc if rc >= 0 else check(rc)
+
+
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
     """fa_sync_device: every device bucket in `clients` := sum_k w_k clients[k] (in place, enqueued)."""
     D = len(clients)
@@ -1307,6 +1378,20 @@ class Aggregator:
             raise ValueError("need idx uint32 and val float32 of one length")
         flags = (HOST_PINNED if pinned else 0) | (TOPK_ABSOLUTE if absolute else 0)
         check(lib().fa_submit_topk(self.handle, part, slot, idx.ctypes.data, val.ctypes.data, idx.size, float(weight), flags))
+
+    def set_sparse_sum(self, part, k_max):
+        """fa_set_sparse_sum: the part's rounds take top-k receipts of at most k_max entries (submit_sparse) and reduce them
+        without expanding them, a_i = g_i + sum_c w_c d_c,i with g the part's last output; 0 removes the stage."""
+        check(lib().fa_set_sparse_sum(self.handle, part, int(k_max)))
+
+    def submit_sparse(self, part, slot, idx, val, weight=1.0, pinned=False):
+        """fa_submit_sparse: the client's update as (idx uint32[k] ascending, val float32[k]), kept as it is until the
+        reducing call.  pinned: views of PinnedBuffers the caller keeps unchanged until the round is reduced."""
+        idx, val = np.ascontiguousarray(idx), np.ascontiguousarray(val)
+        if idx.dtype != np.uint32 or val.dtype != np.float32 or idx.size != val.size:
+            raise ValueError("need idx uint32 and val float32 of one length")
+        check(lib().fa_submit_sparse(self.handle, part, slot, idx.ctypes.data, val.ctypes.data, idx.size, float(weight),
+                                     HOST_PINNED if pinned else 0))
 
     def set_lowrank(self, part, mats, r_max):
         """fa_set_lowrank: the part takes low-rank receipts of rank at most r_max over the table (lowrank_mats, or rows

@@ -274,8 +274,8 @@ struct DevArrays {
 //   bulyan           ready = false                        ready = false      ready = false, if it was on
 //   receipts reply   host_flush, restart_round_plain      nothing            the round stays
 //   secagg           restart_round_plain, no terms        the round stays    the round stays, the terms go
-//   sign             reset_round: the receipts go         the round stays    the round stays, the shadows go
-enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kSign, kStages };
+//   sign sparse      reset_round: the receipts go         the round stays    the round stays, the shadows go
+enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kSign, kSparse, kStages };
 
 struct OptCfg : fa_server_opt {  // fa.h "Server optimizer"
     OptCfg(const fa_server_opt& o = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f}) : fa_server_opt(o) {}
@@ -335,6 +335,10 @@ struct SignCfg {  // fa.h "Sign-vote stage": eta, the rule, the margin, whether 
     bool planes = false;
     bool on() const { return eta > 0.0f; }
 };
+struct SparseCfg {  // fa.h "Sparse-sum stage": the entries a receipt may hold
+    size_t k_max = 0;
+    bool on() const { return k_max != 0; }
+};
 struct StageCfgs {
     OptCfg opt;
     ClipCfg clip;
@@ -347,6 +351,7 @@ struct StageCfgs {
     SecaggCfg secagg;
     DncCfg dnc;
     SignCfg sign;
+    SparseCfg sparse;
 };
 
 // Per GPU the fp32 state over its cnt elements (v only for the adaptive rules).
@@ -466,12 +471,24 @@ struct SignStage {
     std::vector<size_t> stride;
     bool on() const { return cfg.on(); }
 };
+// ref: the device output holds a reference, as Mx8Stage::ref.  buf: per GPU the shadows of its held slots, stride[g] bytes
+// apart, a shadow cap[g] = min(k_max, cnt) indices followed by as many values, allocated at the first fa_submit_sparse;
+// work: per GPU the kernel's workspace over its largest piece.  cut[g][slot * (npiece + 1) + j]: the first entry of the
+// slot's shadow at or after piece j of GPU g (the last word: its entries), as the last fa_submit_sparse left it.
+struct SparseStage {
+    SparseCfg cfg;
+    bool ref = false;
+    DevArrays buf, work;
+    std::vector<size_t> cap, stride;
+    std::vector<std::vector<uint64_t>> cut;
+    bool on() const { return cfg.on(); }
+};
 // The stages that are on in a StageCfgs or a Part, one bit per StageId.
 template <class S>
 inline unsigned stages_on(const S& s) {
     return s.opt.on() << kOpt | s.clip.on() << kClip | s.krum.on() << kKrum | s.geomed.on() << kGeomed |
            s.bulyan.on() << kBulyan | s.noise.on() << kNoise | s.mx8.on() << kMx8 | s.reply.on() << kReply | s.secagg.on() << kSecagg |
-           s.dnc.on() << kDnc | s.sign.on() << kSign;
+           s.dnc.on() << kDnc | s.sign.on() << kSign | s.sparse.on() << kSparse;
 }
 
 struct Part {
@@ -530,6 +547,7 @@ struct Part {
     SecaggStage secagg;
     DncStage dnc;
     SignStage sign;
+    SparseStage sparse;
     DevArrays oavg;
 };
 

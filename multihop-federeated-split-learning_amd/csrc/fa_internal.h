@@ -214,6 +214,24 @@ hipError_t launch_sign_vote(const uint32_t* const* bits, int D, int64_t n, float
 void sign_pack_host(const float* delta, size_t n, uint32_t* bits);
 void sign_vote_host(const uint32_t* const* bits, int D, size_t n, uint64_t idx0, float eta, int rule, int margin,
                     const float* ref, float* out, uint32_t* neg, uint32_t* pos);
+// The sparse-sum stage (fa.h "Sparse-sum stage"), fa_sparse.hip.  out[i] (dtype odt, one rounding) := fl32(widen(ref[i]) +
+// acc_i), or acc_i with ref null, over n elements, bucket elements idx0 .., acc_i the fmaf chain over the entries (idx[c][j],
+// val[c][j]), j < k[c] <= 2^32 - 1, of clients c = 0 .. D - 1 in that order under w[c].  (rdt, odt) as dtype_pair_ok(in,
+// out); out may be ref exactly (a lane reads its elements before it writes them).  work: sparse_workspace(n, D) bytes,
+// 4-byte aligned, not initialised.  form: kSparseSmall or kSparseBig, the tile a wave owns; anything else =
+// sparse_tile_form(k, D, n), by density.  sparse_vec: whether the dense side may use 16-byte accesses (host-only).
+enum { kSparseSmall = 0, kSparseBig = 1 };
+constexpr int kSparseTileSmall = 2048, kSparseTileBig = 8192;
+constexpr int kSparseGroup = 4;  // the clients whose first entries a wave keeps in flight
+int sparse_tile_form(const uint64_t* k, int D, size_t n);
+bool sparse_vec(size_t n, const void* ref, fa_dtype rdt, const void* out, fa_dtype odt);
+size_t sparse_workspace(size_t n, int D);
+hipError_t launch_sparse_sum(const uint32_t* const* idx, const float* const* val, const uint64_t* k, const float* w, int D,
+                             uint64_t idx0, int64_t n, const void* ref, fa_dtype rdt, void* out, fa_dtype odt, void* work,
+                             int form, const Tuning& tu, hipStream_t s);
+// Rules 1-2 on the host (fa_sparse_sum_host): plain loops, client by client.
+void sparse_sum_host(const uint32_t* const* idx, const float* const* val, const uint64_t* k, const float* w, int D, size_t n,
+                     uint64_t idx0, const float* ref, float* out);
 // MX8 receipts (fa.h "MX8 receipts"), fa_mx8.hip.  dst[i] (dtype ddt, one rounding) := fl(widen(ref[i]) + d_i), or d_i
 // without a reference (ref null), over n elements, d_i = fl((float)q[i] * 2^(E - 133)) with E = e[((idx0 + i) >> 5) -
 // (idx0 >> 5)]: e[0] is the scale of the block that bucket element idx0 lies in.  (ddt, rdt) as dtype_pair_ok(in, out).

@@ -543,10 +543,15 @@ void free_sign(fa_ctx* ctx, Part& p) {
     for (DevArrays* a : {&p.sign.buf, &p.sign.planes}) a->free(ctx->gpu);
     p.sign = SignStage{};
 }
+void free_sparse(fa_ctx* ctx, Part& p) {
+    for (DevArrays* a : {&p.sparse.buf, &p.sparse.work}) a->free(ctx->gpu);
+    p.sparse = SparseStage{};
+}
 void free_stages(fa_ctx* ctx, Part& p) {
     p.noise = NoiseStage{};
     free_secagg(ctx, p);
     free_sign(ctx, p);
+    free_sparse(ctx, p);
     free_mx8(ctx, p);
     free_reply(ctx, p);
     free_opt(ctx, p);
@@ -1089,6 +1094,118 @@ int sign_piece(fa_ctx* ctx, Part& p, int g, int j, void* dst, fa_dtype odt, hipS
                    neg ? neg + s.stride[(size_t)g] / 4 : nullptr, st);
 }
 
+// ------------------------------------------------------------------ sparse-sum stage
+
+int check_sparse_clients(int D) {
+    if (D < 1 || D > FA_SPARSE_MAX_CLIENTS) return fail(FA_ERR_ARG, "sparse: D = %d clients outside 1 .. %d", D, FA_SPARSE_MAX_CLIENTS);
+    return FA_OK;
+}
+
+// The shadows and the workspaces of a part, allocated once per k_max: per GPU held x stride bytes, a shadow cap[g] =
+// min(k_max, cnt) indices followed by as many values, and one workspace over the GPU's largest piece (its pieces run one
+// after the other on one stream).  On failure the part keeps the stage.
+int ensure_sparse_buf(fa_ctx* ctx, Part& p) {
+    SparseStage& s = p.sparse;
+    if (s.buf) return FA_OK;
+    s.cap.clear();
+    s.stride.clear();
+    s.cut.assign((size_t)ctx->G, {});
+    for (size_t g = 0; g < (size_t)ctx->G; ++g) {
+        s.cap.push_back(std::min(s.cfg.k_max, p.cnt[g]));
+        s.stride.push_back((s.cap[g] * 8 + 255) / 256 * 256);
+        s.cut[g].assign((size_t)p.D * (size_t)(p.npiece[g] + 1), 0);
+    }
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.stride[g]); };
+    const auto wbytes = [&](size_t g) {
+        size_t most = 0;
+        for (int j = 0; j < p.npiece[g]; ++j) most = std::max(most, piece_cnt(p, (int)g, j));
+        return std::max<size_t>(256, fa::sparse_workspace(most, p.D));
+    };
+    int g = s.buf.alloc(ctx->gpu, bytes);
+    if (g >= 0) return fail(FA_ERR_NOMEM, "sparse: shadow alloc of %zu B failed on GPU %zu", bytes((size_t)g), (size_t)g);
+    g = s.work.alloc(ctx->gpu, wbytes);
+    if (g < 0) return FA_OK;
+    s.buf.free(ctx->gpu);
+    return fail(FA_ERR_NOMEM, "sparse: workspace alloc of %zu B failed on GPU %zu", wbytes((size_t)g), (size_t)g);
+}
+
+int submit_sparse_impl(fa_ctx* ctx, int part_id, int slot, const uint32_t* idx, const float* val, size_t k, float weight,
+                       int flags) {
+    Trace tr("fa_submit_sparse part %d slot %d", part_id, slot);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (flags & ~FA_HOST_PINNED) return fail(FA_ERR_ARG, "sparse: unknown flags 0x%x", flags);
+    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    if (!p->sparse.on()) return fail(FA_ERR_STATE, "sparse: part %d has no sparse-sum stage (fa_set_sparse_sum)", part_id);
+    if (k > p->sparse.cfg.k_max)
+        return fail(FA_ERR_ARG, "sparse: %zu entries, part %d takes at most %zu (fa_set_sparse_sum)", k, part_id, p->sparse.cfg.k_max);
+    if (k && (!idx || !val)) return fail(FA_ERR_ARG, "sparse: %s is null", !idx ? "idx" : "val");
+    if (k && (uint64_t)p->n > (1ull << 32)) return fail(FA_ERR_ARG, "sparse: part %d holds more than 2^32 elements", part_id);
+    if ((uint64_t)k > 0xffffffffull) return fail(FA_ERR_ARG, "sparse: %zu entries, a receipt holds at most 2^32 - 1", k);
+    for (size_t j = 0; j < k; ++j) {
+        if ((uint64_t)idx[j] >= (uint64_t)p->n) return fail(FA_ERR_ARG, "sparse: idx[%zu] = %u, the bucket holds %zu elements", j, idx[j], p->n);
+        if (j && idx[j] <= idx[j - 1])
+            return fail(FA_ERR_ARG, "sparse: idx[%zu] = %u after idx[%zu] = %u: not strictly ascending", j, idx[j], j - 1, idx[j - 1]);
+    }
+    if ((rc = ensure_sparse_buf(ctx, *p))) return rc;
+    const bool pinned = (flags & FA_HOST_PINNED) != 0;
+    const auto first_at = [&](size_t e) { return (size_t)(std::lower_bound(idx, idx + k, (uint64_t)e, [](uint32_t a, uint64_t b) { return (uint64_t)a < b; }) - idx); };
+    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        SparseStage& s = p->sparse;
+        const size_t off = p->off[(size_t)g], cnt = p->cnt[(size_t)g], np = (size_t)p->npiece[(size_t)g];
+        if (cnt == 0) return FA_OK;
+        // after the part's last reducing call: it read the shadow
+        if (hipStream_t ds = p->done_stream[(size_t)g]) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(r.copy, p->done[(size_t)g], 0));
+        }
+        const size_t a = first_at(off), b = first_at(off + cnt);  // the GPU's entries: b - a <= min(k_max, cnt)
+        char* di = s.buf.at((size_t)g) + (size_t)(slot - p->c0[(size_t)g]) * s.stride[(size_t)g];
+        ++r.copy_gen;  // the next reducing call waits for the copy stream
+        int rc2 = mx8_h2d(r, di, reinterpret_cast<const char*>(idx + a), (b - a) * 4, pinned);
+        if (!rc2) rc2 = mx8_h2d(r, di + s.cap[(size_t)g] * 4, reinterpret_cast<const char*>(val + a), (b - a) * 4, pinned);
+        if (rc2) return rc2;
+        uint64_t* cut = &s.cut[(size_t)g][(size_t)slot * (np + 1)];
+        for (size_t j = 0; j < np; ++j) cut[j] = first_at(off + piece_lo(*p, g, (int)j)) - a;
+        cut[np] = b - a;
+        return FA_OK;
+    });
+    if (rc) return rc;
+    return mark_submitted(ctx, *p, slot, weight);
+}
+
+// Before the round's launches: the receipts are there (a part's pieces are fixed when it is defined, so the cuts of the
+// submits hold).
+int sparse_round_begin(const Part& p) {
+    if (!p.sparse.buf) return fail(FA_ERR_STATE, "sparse: part %d has no top-k receipts (fa_submit_sparse)", p.id);
+    return FA_OK;
+}
+
+// Rules 1-2 for piece j of GPU g (the current device), into dst (dtype odt): every client's entries of the piece under
+// w, the reference in the part's output (dst itself where the aggregate is reduced in place).
+int sparse_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, void* dst, fa_dtype odt, hipStream_t st) {
+    const SparseStage& s = p.sparse;
+    const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j), np = (size_t)p.npiece[(size_t)g];
+    if (cnt == 0) return FA_OK;
+    std::vector<const uint32_t*> idx((size_t)p.D);
+    std::vector<const float*> val((size_t)p.D);
+    std::vector<uint64_t> k((size_t)p.D);
+    for (int c = 0; c < p.D; ++c) {
+        const char* base = s.buf.at((size_t)g) + (size_t)(c - p.c0[(size_t)g]) * s.stride[(size_t)g];
+        const uint64_t a = s.cut[(size_t)g][(size_t)c * (np + 1) + (size_t)j], b = s.cut[(size_t)g][(size_t)c * (np + 1) + (size_t)j + 1];
+        idx[(size_t)c] = reinterpret_cast<const uint32_t*>(base) + a;
+        val[(size_t)c] = reinterpret_cast<const float*>(base + s.cap[(size_t)g] * 4) + a;
+        k[(size_t)c] = b - a;
+    }
+    const void* ref = s.ref ? static_cast<const char*>(p.dout[(size_t)g]) + lo * dsize(p.out) : nullptr;
+    FA_HIP(fa::launch_sparse_sum(idx.data(), val.data(), k.data(), w, p.D, (uint64_t)(p.off[(size_t)g] + lo), (int64_t)cnt, ref,
+                                 p.out, dst, odt, s.work.at((size_t)g), -1, ctx->tuning.tu, st));
+    return FA_OK;
+}
+
 // ------------------------------------------------------------------ one reducing call, as the stages see it
 
 int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, StageRound* rd) {
@@ -1116,6 +1233,7 @@ int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, Stage
     if (p.bulyan.on()) return bulyan_plan(ctx, p, s, &rd->plan);
     if (p.secagg.on()) return secagg_round_begin(ctx, p, s);
     if (p.sign.on()) return sign_round_begin(ctx, p);
+    if (p.sparse.on()) return sparse_round_begin(p);
     return FA_OK;
 }
 
@@ -1141,6 +1259,8 @@ int stage_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, const StageR
         rc = secagg_piece(ctx, p, g, j, ptrs, adst, adt, st);
     else if (p.sign.on())
         rc = sign_piece(ctx, p, g, j, adst, adt, st);
+    else if (p.sparse.on())
+        rc = sparse_piece(ctx, p, g, j, w, adst, adt, st);
     else
         rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                        mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
@@ -1424,8 +1544,31 @@ int set_part_sign(fa_ctx* ctx, Part& p, const SignCfg& c) {
     return FA_OK;
 }
 
+// fa_set_sparse_sum on a part (an FA_FEDAVG part of at most FA_SPARSE_MAX_CLIENTS clients, not rs).  Off: the shadows and
+// the workspaces go, after the devices' pending work.  Another k_max: they go as well and come anew with the next receipt,
+// and with them what the round received; the reference stays (the part's output, rule 4).  The first time: what the round received so far is dropped: dense receipts are
+// no top-k receipts.
+int set_part_sparse(fa_ctx* ctx, Part& p, const SparseCfg& c) {
+    if (p.sparse.on() && c.k_max == p.sparse.cfg.k_max) return FA_OK;
+    if (p.sparse.on()) {
+        if (int rc = wait_devices(ctx)) return rc;
+        const bool held = (bool)p.sparse.buf, ref = p.sparse.ref;
+        free_sparse(ctx, p);
+        if (!c.on()) return FA_OK;
+        p.sparse.ref = ref;  // the stage stays on: the part's output is still its reference (rule 4)
+        if (held) reset_round(p);
+    } else {
+        if (!c.on()) return FA_OK;
+        if (int rc = host_flush(ctx, p)) return rc;
+        reset_round(p);
+    }
+    p.sparse.cfg = c;
+    return FA_OK;
+}
+
 int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
     switch (id) {
+        case kSparse: return set_part_sparse(ctx, p, c.sparse);
         case kSign: return set_part_sign(ctx, p, c.sign);
         case kOpt: return set_part_opt(ctx, p, c.opt);
         case kClip: return set_part_clip(ctx, p, c.clip);
@@ -1464,7 +1607,7 @@ const StageRule kRules[kStages] = {
     {"bulyan", "Bulyan", kTrim, false, 0, "the rule needs every client on one GPU; use FA_SHARD_RANGE",
      " (the stage replaces the window of an FA_TRIMMED part)"},
     {"noise", "noise", kAvg | kTrim, false, 0, "its aggregate is not bit-specified; use FA_SHARD_RANGE", ""},
-    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg | 1u << kSign, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
+    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg | 1u << kSign | 1u << kSparse, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
     {"mx8 reply", "reply", kAvg | kTrim, false, 0, "use FA_SHARD_RANGE", ""},
     {"secagg", "secagg", kAvg, true, 1u << kMx8, "its sum is taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage unmasks the sum of an FA_FEDAVG part)"},
@@ -1472,6 +1615,8 @@ const StageRule kRules[kStages] = {
      " (the stage selects the owners of an FA_FEDAVG average)"},
     {"sign", "sign-vote", kAvg, true, 1u << kMx8, "its counts are taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage votes on the updates of an FA_FEDAVG part)"},
+    {"sparse", "sparse-sum", kAvg, true, 1u << kMx8, "its sums are taken over every client of an element; use FA_SHARD_RANGE",
+     " (the stage sums the updates of an FA_FEDAVG part)"},
 };
 
 // The request "turn stage id on (or off), on the context default (part_id < 0, *out = null) or on this part (*out)"
@@ -1514,6 +1659,7 @@ int check_for_clients(StageId id, int D, StageCfgs& c) {
     if (id == kGeomed) return check_geomed(D, c.geomed.iters, c.geomed.nu);
     if (id == kDnc) return check_dnc(D, c.dnc.drop, c.dnc.iters);
     if (id == kSign) return check_sign_clients(D, c.sign.margin);
+    if (id == kSparse) return check_sparse_clients(D);
     return id == kBulyan ? check_bulyan(D, c.bulyan.f) : FA_OK;
 }
 
@@ -2569,6 +2715,24 @@ int fa_copy_sign_planes(fa_ctx* ctx, int part_id, uint32_t* neg, uint32_t* pos) 
     return FA_OK;
 }
 
+int fa_set_sparse_sum(fa_ctx* ctx, int part_id, size_t k_max) {
+    g_err.clear();
+    StageCfgs c = requested(ctx);
+    c.sparse = SparseCfg{};
+    if (k_max) {  // 0 turns the stage off
+        if (ctx && part_id < 0)
+            return fail(FA_ERR_ARG, "sparse: set on a part, not as a context default (a round's receipts belong to one part)");
+        c.sparse.k_max = k_max;
+    }
+    return set_stage(ctx, part_id, kSparse, c);
+}
+
+int fa_submit_sparse(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* idx, const float* val, size_t k, float weight,
+                     int flags) {
+    g_err.clear();
+    return submit_sparse_impl(ctx, part_id, client_slot, idx, val, k, weight, flags);
+}
+
 size_t fa_mx8_scale_bytes(size_t n) { return n / FA_MX8_BLOCK + (n % FA_MX8_BLOCK ? 1 : 0); }
 
 int fa_mx8_encode(const float* delta, size_t n, int8_t* q, uint8_t* e) {
@@ -2679,10 +2843,10 @@ int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
     g_err.clear();
     Part* p;
     if (int rc = check_part(ctx, part_id, &p)) return rc;
-    if (!p->mx8.on() && !p->reply.on() && !p->sign.on())
+    if (!p->mx8.on() && !p->reply.on() && !p->sign.on() && !p->sparse.on())
         return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
                                   "(fa_set_mx8_reply), nor takes top-k (fa_set_topk), low-rank (fa_set_lowrank) or rot1 receipts (fa_set_rot1), "
-                                  "nor has a sign-vote stage (fa_set_sign)", part_id);
+                                  "nor has a sign-vote (fa_set_sign) or sparse-sum stage (fa_set_sparse_sum)", part_id);
     if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
     if (int rc = wait_devices(ctx)) return rc;  // the part's pending work, on whatever stream
     if (p->reply.on())
