@@ -614,6 +614,46 @@
  *              by such a round; they stay allocated (not allocating them is left for later).
  *              Added without a new FA_ABI_VERSION: fa_sparse_sum_device with n == 0 touches no device and answers FA_OK
  *              -- that is how a caller probes for it.
+ *   MX8-sum stage (fa_set_mx8_sum, fa_submit_mx8_sum, fa_mx8_sum_device, fa_mx8_sum_host, fa_mx8_sum_form): a round of
+ *              MX8 receipts reduced without expanding them.  With the weights as shares of the update, sum_c w_c (g + d_c)
+ *              is g + sum_c w_c d_c, so the round reads the D code streams as they are, one byte per owner and element and
+ *              one scale byte per owner and 32 elements, reads g once and writes the output once: 1.03 D + 8 bytes per
+ *              element with fp32 g and output, where fa_submit_mx8 and the chain move about 13 D + 4.
+ *              Format: the MX8 receipt, unchanged (fa_mx8_encode and fa_mx8_encode_device stay the owner's side): q is n
+ *              int8, e is ceil(n / 32) bytes, the block of element i is i >> 5 of the whole bucket.  1 <= D <=
+ *              FA_MX8_SUM_MAX_CLIENTS.
+ *              1. Decode.  d_c,i is decode rules 1-2 of MX8 receipts, unchanged: a quiet NaN for E = 255, else
+ *                 fl32((float)q * 2^(E - 133)), one IEEE multiply, subnormal scales kept; -128 at E = 254 gives -inf.
+ *              2. Sum.  Per element i: acc = +0; for every client c in ascending order acc = fmaf(w_c, d_c,i, acc), one
+ *                 fused operation, as in the FA_FEDAVG chain.  Every client has a value at every element: nobody is
+ *                 skipped.  The scale is not folded into the weight (w_c * 2^(E - 133) can round where q * 2^(E - 133)
+ *                 cannot): the multiply of rule 1 is done, then the fma.
+ *              3. Aggregate.  a_i = fl32(widen(g_i) + acc_i): one IEEE add, never contracted with rule 2; g widened
+ *                 exactly (bf16; fp16 with its subnormals).  Without a reference (absolute mode) a_i = acc_i.  NaN and inf
+ *                 in d, w or g follow IEEE rules (0 * NaN is NaN); NaN payloads are unspecified.
+ *              4. Weights, place in the round, reference, layout independence, admission: what rules 3-6 of the sparse-sum
+ *                 stage say, with fa_set_mx8_sum and fa_submit_mx8_sum in place of fa_set_sparse_sum and fa_submit_sparse.
+ *                 The weights are the owners' shares of the *update* and g enters with weight one; any fp32 weight is taken
+ *                 as given.  a stands exactly where the chain's result stands: it feeds the noise stage and the server
+ *                 optimizer if the part has them, otherwise it is rounded once to the out dtype; MX8 replies, range shards,
+ *                 range pieces and fa_reduce_parts work as for any part.  The reference g is the part's device output as
+ *                 the last reducing call with the stage left it (fa_mx8_set_reference sets it); a round on a part without
+ *                 a reference runs in absolute mode.  Every element's arithmetic is a fixed sequence that depends on no
+ *                 tile, grid, shard or piece: the same bits for any GPU count, pieces, pointer phase or kernel form.  Only
+ *                 on an FA_FEDAVG part; a member of the measure-then-select family: not with the clip, Krum, DnC, geomed,
+ *                 secagg, sign or sparse-sum stage, and not with any of the four receipt formats (those setters refuse an
+ *                 MX8-sum part in turn).  Not on an FA_SHARD_CLIENT_RS context, not as a context default.  The part is never
+ *                 kept host-side, FA_ACCUMULATE_ON_ARRIVAL leaves it non-eager, and a reducing call needs every client
+ *                 submitted, with fa_submit_mx8_sum: a dense fa_submit to such a part is FA_ERR_STATE.  Setting the stage on
+ *                 a part drops what the round had received so far.
+ *              5. One identity.  In absolute mode with an f32 output the result is bit for bit what the same receipts give
+ *                 through fa_set_mx8 with FA_MX8_ABSOLUTE into f32 slots and the chain: the same fma chain over the same d.
+ *                 In relative mode the bits differ: the expanded route rounds g + d_c per owner.
+ *              Memory: per GPU and client slot one shadow in the MX8 shadow layout (cnt bytes of q rounded up to 16, then
+ *              the scale bytes of the blocks the range touches, rounded up to 256), allocated at the part's first submit.
+ *              The part's dense slots are neither read nor written by such a round; they stay allocated.
+ *              Added without a new FA_ABI_VERSION: fa_mx8_sum_device with n == 0 touches no device and answers FA_OK --
+ *              that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -1479,6 +1519,45 @@ int fa_set_sparse_sum(fa_ctx* ctx, int part_id, size_t k_max);
  * first submit); the slot then counts as submitted.  FA_ERR_STATE on a part without fa_set_sparse_sum. */
 int fa_submit_sparse(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* idx, const float* val, size_t k, float weight,
                      int flags);
+
+/* MX8-sum stage (the header comment, "MX8-sum stage"): MX8 receipts reduced on the GPU without expanding them. */
+#define FA_MX8_SUM_MAX_CLIENTS 128
+/* fa_mx8_sum_form. */
+#define FA_MX8_SUM_VECTOR 1 /* 16 elements per lane: 16-byte accesses to q, the reference and the output */
+/* Rules 1-3 on the host, usable without a device: out[i] (fp32, n elements) is the aggregate of bucket element idx0 + i
+ * from the receipts (q[c], e[c]) under w[c], c < D, and ref (fp32, n elements, NULL = absolute mode).  q[c][i] is the code
+ * of bucket element idx0 + i, e[c][0] the scale of the block that element idx0 lies in.  FA_ERR_ARG as fa_mx8_sum_device. */
+int fa_mx8_sum_host(const int8_t* const* q, const uint8_t* const* e, const float* w, int D, size_t n, uint64_t idx0,
+                    const float* ref, float* out);
+/* Rules 1-3 on raw device pointers over bucket elements idx0 .. idx0 + n - 1: d_out[i] (n of out_dtype, one rounding) from
+ * d_ref (n of ref_dtype, NULL = absolute mode) and the receipts: d_q[c] are client c's n codes, d_e[c] the scale bytes of
+ * blocks idx0 >> 5 .. (idx0 + n - 1) >> 5; the arrays d_q, d_e and w themselves are host memory and are read before the
+ * call returns.  ctx may be NULL (then `gpu` is the HIP device).  Every argument is checked before any device call: 1 <= D
+ * <= FA_MX8_SUM_MAX_CLIENTS, the dtypes and their pair (bf16 <-> f16: FA_ERR_ARG), idx0 + n < 2^64, and for n > 0 null
+ * pointers, the element alignment of d_ref and d_out (FA_ERR_ALIGN) and that d_out does not overlap d_ref; with n == 0
+ * and valid arguments it returns FA_OK without touching a device.  Nothing is read outside q[0, n) and those scale bytes,
+ * nothing is written outside d_out[0, n).  Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the null
+ * stream).  Any phase of the pointers and any idx0 is correct (fa_mx8_sum_form). */
+int fa_mx8_sum_device(fa_ctx* ctx, int gpu, const int8_t* const* d_q, const uint8_t* const* d_e, const float* w, int D, size_t n,
+                      uint64_t idx0, const void* d_ref, fa_dtype ref_dtype, void* d_out, fa_dtype out_dtype, void* hip_stream);
+/* Which form fa_mx8_sum_device takes for these operands: FA_MX8_SUM_VECTOR if d_ref and d_out agree on a common head before
+ * their 16-byte boundaries, every d_q[c] is 16-byte aligned after that head and the bucket index of the first element
+ * after it is a multiple of 16; else 0, the element form.  (A launch that ends before the head has no vector in either
+ * case.)  Pure host arithmetic on the pointer values; the bits do not depend on it. */
+int fa_mx8_sum_form(size_t n, const int8_t* const* d_q, int D, uint64_t idx0, const void* d_ref, fa_dtype ref_dtype,
+                    const void* d_out, fa_dtype out_dtype);
+/* Gives a part the stage (part_id >= 0, on != 0): its rounds take MX8 receipts with fa_submit_mx8_sum and reduce them by
+ * rules 1-3 against the part's last output; the round under way is dropped.  Again on a part that has it: nothing.  on == 0
+ * removes the stage and frees what it allocated.  FA_ERR_ARG, naming the cause: D > FA_MX8_SUM_MAX_CLIENTS, part_id < 0 (no
+ * context default), a part whose mode is not FA_FEDAVG, a part with a clip, Krum, DnC, geomed, secagg, sign, sparse-sum or
+ * receipt stage (those setters refuse an MX8-sum part in turn), an FA_SHARD_CLIENT_RS context.  In DESIGN.md 8q the stage takes
+ * 0.105 - 0.176 of the expanded route's device time at every D measured (64, 32, 8; n = 64 Mi fp32); it lost nowhere. */
+int fa_set_mx8_sum(fa_ctx* ctx, int part_id, int on);
+/* The MX8 receipt of client `client_slot`, q (n int8) and e (ceil(n / 32) bytes) of the whole bucket, under `weight` (rule
+ * 4).  flags: FA_HOST_PINNED as for fa_submit_mx8.  Per GPU enqueues the H2D of its range's q bytes and scale bytes into
+ * the slot's shadow (allocated at the part's first submit); the slot then counts as submitted.  FA_ERR_STATE on a part
+ * without fa_set_mx8_sum. */
+int fa_submit_mx8_sum(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags);
 
 /* Compute-node aggregation of an intermediate model part.
  * A compute node keeps one State per client (systemAPI::init_state_vector,

@@ -179,6 +179,11 @@ def lib():
         "fa_sparse_sum_form": (I, [S, P, I, P, I, P, I]),
         "fa_set_sparse_sum": (I, [P, I, S]),
         "fa_submit_sparse": (I, [P, I, I, P, P, S, F, I]),
+        "fa_mx8_sum_host": (I, [P, P, P, I, S, U64, P, P]),
+        "fa_mx8_sum_device": (I, [P, I, P, P, P, I, S, U64, P, I, P, I, P]),
+        "fa_mx8_sum_form": (I, [S, P, I, U64, P, I, P, I]),
+        "fa_set_mx8_sum": (I, [P, I, I]),
+        "fa_submit_mx8_sum": (I, [P, I, I, P, P, F, I]),
         "fa_diag_secagg_unmask": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, I, P]),  # diagnostic (outside fa.h)
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
@@ -929,6 +934,60 @@ def sparse_sum_form(n, k, out, out_dtype=F32, ref=None, ref_dtype=F32):
     return rc if rc >= 0 else check(rc)
 
 
+MX8_SUM_MAX_CLIENTS = 128  # FA_MX8_SUM_MAX_CLIENTS
+MX8_SUM_VECTOR = 1  # mx8_sum_form
+MX8_SUM_TILE = 4096  # the elements of a workgroup's tile: 128 blocks, 16 elements per lane
+MX8_SUM_GROUP = 4  # the clients whose q words a lane keeps in flight
+
+
+def _mx8_sum_args(q, e, weights):
+    """The pointer arrays and the weights of D receipts (q[c], e[c]).  Returns ctypes arrays, which the caller keeps until
+    the call returns."""
+    D = len(q)
+    if len(e) != D:
+        raise ValueError("need one e per q")
+    w = np.ascontiguousarray(np.ones(D) if weights is None else weights, np.float32).reshape(-1)
+    if w.size != D:
+        raise ValueError("need one weight per client")
+    pq = (ctypes.c_void_p * max(1, D))(*[_addr(x) for x in q])
+    pe = (ctypes.c_void_p * max(1, D))(*[_addr(x) for x in e])
+    return pq, pe, w, D
+
+
+def mx8_sum_host(q, e, n, weights=None, ref=None, idx0=0):
+    """fa_mx8_sum_host (host arithmetic, fa.h "MX8-sum stage" rules 1-3): the fp32 aggregate of bucket elements idx0 .. idx0 +
+    n - 1 from the receipts (q[c] int8[n], e[c] uint8, e[c][0] the scale of element idx0's block) under `weights` (None:
+    ones) and ref (fp32[n], None: absolute mode)."""
+    q = [np.ascontiguousarray(np.asarray(x, np.int8).reshape(-1)) for x in q]
+    e = [np.ascontiguousarray(np.asarray(x, np.uint8).reshape(-1)) for x in e]
+    blocks = ((int(idx0) + n - 1) >> 5) - (int(idx0) >> 5) + 1 if n else 0
+    if any(x.size != n for x in q) or any(x.size < blocks for x in e):
+        raise ValueError("need %d codes and %d scales per client" % (n, blocks))
+    pq, pe, w, D = _mx8_sum_args(q, e, weights)
+    if ref is not None:
+        ref = np.ascontiguousarray(np.asarray(ref, np.float32).reshape(-1))
+    out = np.empty(n, np.float32)
+    check(lib().fa_mx8_sum_host(pq, pe, w.ctypes.data, D, n, int(idx0), _addr(ref), out.ctypes.data))
+    return out
+
+
+def mx8_sum_device(q, e, n, out, out_dtype=F32, weights=None, ref=None, ref_dtype=F32, idx0=0, stream=None, gpu=0, ctx=None):
+    """fa_mx8_sum_device: out[i] = ref[i] + sum_c w_c d_c,i (ref None: the sum) over n device-resident elements, bucket
+    elements idx0 .., from the D device-resident receipts (q[c], e[c]), q / e / idx0 as for mx8_decode, at any byte (q, e)
+    or element (ref, out) phase.  Enqueued, not synchronized.  With n == 0 no device is touched: the feature probe."""
+    pq, pe, w, D = _mx8_sum_args(q, e, weights)
+    check(lib().fa_mx8_sum_device(ctx.handle if ctx is not None else None, gpu, pq, pe, w.ctypes.data, D, n, int(idx0),
+                                  _addr(ref), ref_dtype, _addr(out), out_dtype, _stream(stream)))
+
+
+def mx8_sum_form(n, q, out, out_dtype=F32, ref=None, ref_dtype=F32, idx0=0):
+    """fa_mx8_sum_form (host arithmetic on the addresses and idx0): MX8_SUM_VECTOR if mx8_sum_device takes a lane's 16
+    elements in 16-byte accesses for these operands, 0 if it goes element by element."""
+    pq = (ctypes.c_void_p * max(1, len(q)))(*[_addr(x) for x in q])
+    rc = lib().fa_mx8_sum_form(n, pq, len(q), int(idx0), _addr(ref), ref_dtype, _addr(out), out_dtype)
+    return rc if rc >= 0 else check(rc)
+
+
 def sync_device(clients, weights, n, dtype, stream=None, gpu=0, ctx=None):
     """fa_sync_device: every device bucket in `clients` := sum_k w_k clients[k] (in place, enqueued)."""
     D = len(clients)
@@ -1392,6 +1451,25 @@ class Aggregator:
             raise ValueError("need idx uint32 and val float32 of one length")
         check(lib().fa_submit_sparse(self.handle, part, slot, idx.ctypes.data, val.ctypes.data, idx.size, float(weight),
                                      HOST_PINNED if pinned else 0))
+
+    def set_mx8_sum(self, on=True, part_id=-1):
+        """fa_set_mx8_sum: the part's rounds take MX8 receipts (submit_mx8_sum) and reduce them without expanding them,
+        a_i = g_i + sum_c w_c d_c,i with g the part's last output; on=False removes the stage."""
+        check(lib().fa_set_mx8_sum(self.handle, part_id, 1 if on else 0))
+
+    def submit_mx8_sum(self, part_id, slot, q, e, weight=1.0, pinned=False):
+        """fa_submit_mx8_sum: the client's update as (q int8[n], e uint8[ceil(n / 32)]), kept as it is until the reducing
+        call.  pinned: views of PinnedBuffers the caller keeps unchanged until the round is reduced."""
+        q, e = np.ascontiguousarray(q), np.ascontiguousarray(e)
+        if q.dtype != np.int8 or e.dtype != np.uint8:
+            raise ValueError("need q int8 and e uint8")
+        if part_id in self.parts:
+            n = self.parts[part_id][0]
+            if q.size != n or e.size != mx8_scale_bytes(n):
+                raise ValueError("bucket %d expects %d codes and %d scales, got %d and %d"
+                                 % (part_id, n, mx8_scale_bytes(n), q.size, e.size))
+        check(lib().fa_submit_mx8_sum(self.handle, part_id, slot, q.ctypes.data, e.ctypes.data, float(weight),
+                                      HOST_PINNED if pinned else 0))
 
     def set_lowrank(self, part, mats, r_max):
         """fa_set_lowrank: the part takes low-rank receipts of rank at most r_max over the table (lowrank_mats, or rows

@@ -275,7 +275,8 @@ struct DevArrays {
 //   receipts reply   host_flush, restart_round_plain      nothing            the round stays
 //   secagg           restart_round_plain, no terms        the round stays    the round stays, the terms go
 //   sign sparse      reset_round: the receipts go         the round stays    the round stays, the shadows go
-enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kSign, kSparse, kStages };
+//   mx8 sum          reset_round: the receipts go         the round stays    the round stays, the shadows go
+enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kSign, kSparse, kMx8Sum, kStages };
 
 struct OptCfg : fa_server_opt {  // fa.h "Server optimizer"
     OptCfg(const fa_server_opt& o = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f}) : fa_server_opt(o) {}
@@ -339,6 +340,10 @@ struct SparseCfg {  // fa.h "Sparse-sum stage": the entries a receipt may hold
     size_t k_max = 0;
     bool on() const { return k_max != 0; }
 };
+struct Mx8SumCfg {  // fa.h "MX8-sum stage"
+    bool flag = false;
+    bool on() const { return flag; }
+};
 struct StageCfgs {
     OptCfg opt;
     ClipCfg clip;
@@ -352,6 +357,7 @@ struct StageCfgs {
     DncCfg dnc;
     SignCfg sign;
     SparseCfg sparse;
+    Mx8SumCfg mx8sum;
 };
 
 // Per GPU the fp32 state over its cnt elements (v only for the adaptive rules).
@@ -483,12 +489,22 @@ struct SparseStage {
     std::vector<std::vector<uint64_t>> cut;
     bool on() const { return cfg.on(); }
 };
+// ref: the device output holds a reference, as Mx8Stage::ref.  buf: per GPU the shadows of its held slots in the layout of
+// Mx8Stage::buf, stride[g] bytes apart (q: cnt bytes, then from eoff[g] on the scale bytes of the blocks its range touches),
+// allocated at the first fa_submit_mx8_sum.
+struct Mx8SumStage {
+    Mx8SumCfg cfg;
+    bool ref = false;
+    DevArrays buf;
+    std::vector<size_t> stride, eoff;
+    bool on() const { return cfg.on(); }
+};
 // The stages that are on in a StageCfgs or a Part, one bit per StageId.
 template <class S>
 inline unsigned stages_on(const S& s) {
     return s.opt.on() << kOpt | s.clip.on() << kClip | s.krum.on() << kKrum | s.geomed.on() << kGeomed |
            s.bulyan.on() << kBulyan | s.noise.on() << kNoise | s.mx8.on() << kMx8 | s.reply.on() << kReply | s.secagg.on() << kSecagg |
-           s.dnc.on() << kDnc | s.sign.on() << kSign | s.sparse.on() << kSparse;
+           s.dnc.on() << kDnc | s.sign.on() << kSign | s.sparse.on() << kSparse | s.mx8sum.on() << kMx8Sum;
 }
 
 struct Part {
@@ -548,6 +564,7 @@ struct Part {
     DncStage dnc;
     SignStage sign;
     SparseStage sparse;
+    Mx8SumStage mx8sum;
     DevArrays oavg;
 };
 

@@ -239,6 +239,20 @@ void sparse_sum_host(const uint32_t* const* idx, const float* const* val, const 
 Split mx8_split(const void* q, size_t n, const void* ref, fa_dtype rdt, const void* dst, fa_dtype ddt);
 hipError_t launch_mx8_expand(const int8_t* q, const uint8_t* e, uint64_t idx0, int64_t n, const void* ref, fa_dtype rdt,
                              void* dst, fa_dtype ddt, hipStream_t s);
+// The MX8-sum stage (fa.h "MX8-sum stage"), fa_mx8sum.hip.  out[i] (dtype odt, one rounding) := fl32(widen(ref[i]) + acc_i),
+// or acc_i with ref null, over n elements, bucket elements idx0 .., acc_i the fmaf chain over d_c,i = fl((float)q[c][i] *
+// 2^(E - 133)), E = e[c][((idx0 + i) >> 5) - (idx0 >> 5)], of clients c = 0 .. D - 1 in that order under w[c].  (rdt, odt) as
+// dtype_pair_ok(in, out); out may be ref exactly (a lane reads its elements before it writes them).  Any pointers of
+// element alignment: mx8sum_split (host-only) says which form a launch takes (vec: the vector form over [head, tail0)).
+constexpr int kMx8SumTile = 4096;  // the elements of a workgroup's tile: 128 blocks
+constexpr int kMx8SumGroup = 4;    // the clients whose q words a lane keeps in flight
+Split mx8sum_split(size_t n, const int8_t* const* q, int D, uint64_t idx0, const void* ref, fa_dtype rdt, const void* out,
+                   fa_dtype odt);
+hipError_t launch_mx8_sum(const int8_t* const* q, const uint8_t* const* e, const float* w, int D, uint64_t idx0, int64_t n,
+                          const void* ref, fa_dtype rdt, void* out, fa_dtype odt, const Tuning& tu, hipStream_t s);
+// Rules 1-3 on the host (fa_mx8_sum_host): plain loops, client by client.
+void mx8_sum_host(const int8_t* const* q, const uint8_t* const* e, const float* w, int D, size_t n, uint64_t idx0,
+                  const float* ref, float* out);
 // The codec on the host (fa_mx8_decode: the kernel's own multiply and scale; fa_mx8_encode: the owner's side).
 void mx8_decode_host(const int8_t* q, const uint8_t* e, size_t n, uint64_t idx0, float* d);
 void mx8_encode_host(const float* delta, size_t n, int8_t* q, uint8_t* e);

@@ -547,11 +547,16 @@ void free_sparse(fa_ctx* ctx, Part& p) {
     for (DevArrays* a : {&p.sparse.buf, &p.sparse.work}) a->free(ctx->gpu);
     p.sparse = SparseStage{};
 }
+void free_mx8sum(fa_ctx* ctx, Part& p) {
+    p.mx8sum.buf.free(ctx->gpu);
+    p.mx8sum = Mx8SumStage{};
+}
 void free_stages(fa_ctx* ctx, Part& p) {
     p.noise = NoiseStage{};
     free_secagg(ctx, p);
     free_sign(ctx, p);
     free_sparse(ctx, p);
+    free_mx8sum(ctx, p);
     free_mx8(ctx, p);
     free_reply(ctx, p);
     free_opt(ctx, p);
@@ -1206,6 +1211,88 @@ int sparse_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, void* dst, 
     return FA_OK;
 }
 
+// ------------------------------------------------------------------ MX8-sum stage
+
+int check_mx8sum_clients(int D) {
+    if (D < 1 || D > FA_MX8_SUM_MAX_CLIENTS)
+        return fail(FA_ERR_ARG, "mx8 sum: D = %d clients outside 1 .. %d", D, FA_MX8_SUM_MAX_CLIENTS);
+    return FA_OK;
+}
+
+inline size_t mx8_scales(size_t off, size_t cnt);  // below, with the receipts
+void mx8_shadow_layout(const Part& p, int G, std::vector<size_t>* stride, std::vector<size_t>* eoff);
+
+// The shadows of a part, allocated once: per GPU held x stride bytes in the MX8 shadow layout.  q lies at the shadow's
+// start and a piece starts on a multiple of 64 elements, so every launch takes the vector form.  On failure the part keeps
+// the stage.
+int ensure_mx8sum_buf(fa_ctx* ctx, Part& p) {
+    Mx8SumStage& s = p.mx8sum;
+    if (s.buf) return FA_OK;
+    mx8_shadow_layout(p, ctx->G, &s.stride, &s.eoff);
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.stride[g]); };
+    const int g = s.buf.alloc(ctx->gpu, bytes);
+    if (g < 0) return FA_OK;
+    return fail(FA_ERR_NOMEM, "mx8 sum: shadow alloc of %zu B failed on GPU %zu", bytes((size_t)g), (size_t)g);
+}
+
+int submit_mx8_sum_impl(fa_ctx* ctx, int part_id, int slot, const int8_t* q, const uint8_t* e, float weight, int flags) {
+    Trace tr("fa_submit_mx8_sum part %d slot %d", part_id, slot);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (flags & ~FA_HOST_PINNED) return fail(FA_ERR_ARG, "mx8 sum: unknown flags 0x%x", flags);
+    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    if (!p->mx8sum.on()) return fail(FA_ERR_STATE, "mx8 sum: part %d has no MX8-sum stage (fa_set_mx8_sum)", part_id);
+    if (p->n > 0 && (!q || !e)) return fail(FA_ERR_ARG, "mx8 sum: %s is null", !q ? "q" : "e");
+    if ((rc = ensure_mx8sum_buf(ctx, *p))) return rc;
+    const bool pinned = (flags & FA_HOST_PINNED) != 0;
+    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        const size_t off = p->off[(size_t)g], cnt = p->cnt[(size_t)g];
+        if (cnt == 0) return FA_OK;
+        // after the part's last reducing call: it read the shadow
+        if (hipStream_t ds = p->done_stream[(size_t)g]) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(r.copy, p->done[(size_t)g], 0));
+        }
+        char* dq = p->mx8sum.buf.at((size_t)g) + (size_t)(slot - p->c0[(size_t)g]) * p->mx8sum.stride[(size_t)g];
+        ++r.copy_gen;  // the next reducing call waits for the copy stream
+        int rc2 = mx8_h2d(r, dq, reinterpret_cast<const char*>(q) + off, cnt, pinned);
+        if (!rc2)
+            rc2 = mx8_h2d(r, dq + p->mx8sum.eoff[(size_t)g], reinterpret_cast<const char*>(e) + (off >> 5), mx8_scales(off, cnt),
+                          pinned);
+        return rc2;
+    });
+    if (rc) return rc;
+    return mark_submitted(ctx, *p, slot, weight);
+}
+
+// Before the round's launches: the receipts are there.
+int mx8sum_round_begin(const Part& p) {
+    if (!p.mx8sum.buf) return fail(FA_ERR_STATE, "mx8 sum: part %d has no MX8 receipts (fa_submit_mx8_sum)", p.id);
+    return FA_OK;
+}
+
+// Rules 1-3 for piece j of GPU g (the current device), into dst (dtype odt): every client's codes and scales of the piece
+// under w, the reference in the part's output (dst itself where the aggregate is reduced in place).
+int mx8sum_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, void* dst, fa_dtype odt, hipStream_t st) {
+    const Mx8SumStage& s = p.mx8sum;
+    const size_t off = p.off[(size_t)g], lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
+    if (cnt == 0) return FA_OK;
+    std::vector<const int8_t*> q((size_t)p.D);
+    std::vector<const uint8_t*> e((size_t)p.D);
+    for (int c = 0; c < p.D; ++c) {
+        const char* base = s.buf.at((size_t)g) + (size_t)(c - p.c0[(size_t)g]) * s.stride[(size_t)g];
+        q[(size_t)c] = reinterpret_cast<const int8_t*>(base) + lo;
+        e[(size_t)c] = reinterpret_cast<const uint8_t*>(base) + s.eoff[(size_t)g] + (((off + lo) >> 5) - (off >> 5));
+    }
+    const void* ref = s.ref ? static_cast<const char*>(p.dout[(size_t)g]) + lo * dsize(p.out) : nullptr;
+    FA_HIP(fa::launch_mx8_sum(q.data(), e.data(), w, p.D, (uint64_t)(off + lo), (int64_t)cnt, ref, p.out, dst, odt,
+                              ctx->tuning.tu, st));
+    return FA_OK;
+}
+
 // ------------------------------------------------------------------ one reducing call, as the stages see it
 
 int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, StageRound* rd) {
@@ -1234,6 +1321,7 @@ int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, Stage
     if (p.secagg.on()) return secagg_round_begin(ctx, p, s);
     if (p.sign.on()) return sign_round_begin(ctx, p);
     if (p.sparse.on()) return sparse_round_begin(p);
+    if (p.mx8sum.on()) return mx8sum_round_begin(p);
     return FA_OK;
 }
 
@@ -1261,6 +1349,8 @@ int stage_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, const StageR
         rc = sign_piece(ctx, p, g, j, adst, adt, st);
     else if (p.sparse.on())
         rc = sparse_piece(ctx, p, g, j, w, adst, adt, st);
+    else if (p.mx8sum.on())
+        rc = mx8sum_piece(ctx, p, g, j, w, adst, adt, st);
     else
         rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                        mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
@@ -1566,8 +1656,25 @@ int set_part_sparse(fa_ctx* ctx, Part& p, const SparseCfg& c) {
     return FA_OK;
 }
 
+// fa_set_mx8_sum on a part (an FA_FEDAVG part of at most FA_MX8_SUM_MAX_CLIENTS clients, not rs).  Off: the shadows go,
+// after the devices' pending work.  On a part that has the stage: nothing.  The first time: what the round received so
+// far is dropped: dense receipts are no MX8 receipts.
+int set_part_mx8sum(fa_ctx* ctx, Part& p, const Mx8SumCfg& c) {
+    if (p.mx8sum.on() == c.on()) return FA_OK;
+    if (!c.on()) {
+        if (int rc = wait_devices(ctx)) return rc;
+        free_mx8sum(ctx, p);
+        return FA_OK;
+    }
+    if (int rc = host_flush(ctx, p)) return rc;
+    reset_round(p);
+    p.mx8sum.cfg = c;
+    return FA_OK;
+}
+
 int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
     switch (id) {
+        case kMx8Sum: return set_part_mx8sum(ctx, p, c.mx8sum);
         case kSparse: return set_part_sparse(ctx, p, c.sparse);
         case kSign: return set_part_sign(ctx, p, c.sign);
         case kOpt: return set_part_opt(ctx, p, c.opt);
@@ -1607,7 +1714,7 @@ const StageRule kRules[kStages] = {
     {"bulyan", "Bulyan", kTrim, false, 0, "the rule needs every client on one GPU; use FA_SHARD_RANGE",
      " (the stage replaces the window of an FA_TRIMMED part)"},
     {"noise", "noise", kAvg | kTrim, false, 0, "its aggregate is not bit-specified; use FA_SHARD_RANGE", ""},
-    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg | 1u << kSign | 1u << kSparse, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
+    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg | 1u << kSign | 1u << kSparse | 1u << kMx8Sum, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
     {"mx8 reply", "reply", kAvg | kTrim, false, 0, "use FA_SHARD_RANGE", ""},
     {"secagg", "secagg", kAvg, true, 1u << kMx8, "its sum is taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage unmasks the sum of an FA_FEDAVG part)"},
@@ -1616,6 +1723,8 @@ const StageRule kRules[kStages] = {
     {"sign", "sign-vote", kAvg, true, 1u << kMx8, "its counts are taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage votes on the updates of an FA_FEDAVG part)"},
     {"sparse", "sparse-sum", kAvg, true, 1u << kMx8, "its sums are taken over every client of an element; use FA_SHARD_RANGE",
+     " (the stage sums the updates of an FA_FEDAVG part)"},
+    {"mx8 sum", "MX8-sum", kAvg, true, 1u << kMx8, "its sums are taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage sums the updates of an FA_FEDAVG part)"},
 };
 
@@ -1660,6 +1769,7 @@ int check_for_clients(StageId id, int D, StageCfgs& c) {
     if (id == kDnc) return check_dnc(D, c.dnc.drop, c.dnc.iters);
     if (id == kSign) return check_sign_clients(D, c.sign.margin);
     if (id == kSparse) return check_sparse_clients(D);
+    if (id == kMx8Sum) return check_mx8sum_clients(D);
     return id == kBulyan ? check_bulyan(D, c.bulyan.f) : FA_OK;
 }
 
@@ -1707,18 +1817,24 @@ int stage_part(fa_ctx* ctx, int part_id, StageId id, Part** out, bool report = f
 // The scale bytes GPU g's range [off, off + cnt) touches: blocks off >> 5 .. (off + cnt - 1) >> 5.
 inline size_t mx8_scales(size_t off, size_t cnt) { return cnt ? ((off + cnt - 1) >> 5) - (off >> 5) + 1 : 0; }
 
+// The MX8 shadow layout, per GPU (the MX8 receipts' and the MX8-sum stage's): q, cnt bytes rounded up to 16, then the
+// scale bytes of the blocks the range touches; the stride between slots rounded up to 256.
+void mx8_shadow_layout(const Part& p, int G, std::vector<size_t>* stride, std::vector<size_t>* eoff) {
+    stride->clear();
+    eoff->clear();
+    for (size_t g = 0; g < (size_t)G; ++g) {
+        eoff->push_back((p.cnt[g] + 15) / 16 * 16);
+        stride->push_back(((*eoff)[g] + mx8_scales(p.off[g], p.cnt[g]) + 255) / 256 * 256);
+    }
+}
+
 // The shadows of an MX8 part, allocated once: per GPU held x stride bytes.  q lies at the shadow's start, which
 // keeps the 16-byte phase of the slots and the output (all 16-byte aligned: the vector form applies).  On failure the
 // part stays an MX8 part.
 int ensure_mx8_buf(fa_ctx* ctx, Part& p) {
     Mx8Stage& s = p.mx8;
     if (s.buf) return FA_OK;
-    s.stride.clear();
-    s.eoff.clear();
-    for (size_t g = 0; g < (size_t)ctx->G; ++g) {
-        s.eoff.push_back((p.cnt[g] + 15) / 16 * 16);
-        s.stride.push_back((s.eoff[g] + mx8_scales(p.off[g], p.cnt[g]) + 255) / 256 * 256);
-    }
+    mx8_shadow_layout(p, ctx->G, &s.stride, &s.eoff);
     const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.stride[g]); };
     const int g = s.buf.alloc(ctx->gpu, bytes);
     if (g < 0) return FA_OK;
@@ -2733,6 +2849,23 @@ int fa_submit_sparse(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* 
     return submit_sparse_impl(ctx, part_id, client_slot, idx, val, k, weight, flags);
 }
 
+int fa_set_mx8_sum(fa_ctx* ctx, int part_id, int on) {
+    g_err.clear();
+    StageCfgs c = requested(ctx);
+    c.mx8sum = Mx8SumCfg{};
+    if (on) {
+        if (ctx && part_id < 0)
+            return fail(FA_ERR_ARG, "mx8 sum: set on a part, not as a context default (a round's receipts belong to one part)");
+        c.mx8sum.flag = true;
+    }
+    return set_stage(ctx, part_id, kMx8Sum, c);
+}
+
+int fa_submit_mx8_sum(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q, const uint8_t* e, float weight, int flags) {
+    g_err.clear();
+    return submit_mx8_sum_impl(ctx, part_id, client_slot, q, e, weight, flags);
+}
+
 size_t fa_mx8_scale_bytes(size_t n) { return n / FA_MX8_BLOCK + (n % FA_MX8_BLOCK ? 1 : 0); }
 
 int fa_mx8_encode(const float* delta, size_t n, int8_t* q, uint8_t* e) {
@@ -2843,10 +2976,10 @@ int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
     g_err.clear();
     Part* p;
     if (int rc = check_part(ctx, part_id, &p)) return rc;
-    if (!p->mx8.on() && !p->reply.on() && !p->sign.on() && !p->sparse.on())
+    if (!p->mx8.on() && !p->reply.on() && !p->sign.on() && !p->sparse.on() && !p->mx8sum.on())
         return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
                                   "(fa_set_mx8_reply), nor takes top-k (fa_set_topk), low-rank (fa_set_lowrank) or rot1 receipts (fa_set_rot1), "
-                                  "nor has a sign-vote (fa_set_sign) or sparse-sum stage (fa_set_sparse_sum)", part_id);
+                                  "nor has a sign-vote (fa_set_sign), sparse-sum (fa_set_sparse_sum) or MX8-sum stage (fa_set_mx8_sum)", part_id);
     if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
     if (int rc = wait_devices(ctx)) return rc;  // the part's pending work, on whatever stream
     if (p->reply.on())
