@@ -654,6 +654,44 @@
  *              The part's dense slots are neither read nor written by such a round; they stay allocated.
  *              Added without a new FA_ABI_VERSION: fa_mx8_sum_device with n == 0 touches no device and answers FA_OK --
  *              that is how a caller probes for it.
+ *   Low-rank-sum stage (fa_set_lowrank_sum, fa_submit_lowrank_sum, fa_lowrank_sum_device, fa_lowrank_sum_host): a round
+ *              of low-rank receipts reduced without expanding them.  The weighted sum of the owners' products is itself
+ *              one matrix product, sum_c w_c P_c Q_c^T = [w_1 P_1 | ... | w_D P_D] [Q_1 | ... | Q_D]^T -- the "stacking"
+ *              form of exact federated LoRA aggregation -- so the round reads g once and writes the aggregate once: 8 bytes
+ *              per element with fp32 g and output, where fa_submit_lowrank and the chain move about 12 D + 4.  It runs the
+ *              fp64 multiply-adds the D expansions run together, and rounds once where they round D + 1 times.
+ *              Format: the low-rank receipt, unchanged: the part's table of fa_lowrank_mat, one rank per owner, 1 <= r_c <=
+ *              r_max <= FA_LOWRANK_MAX_RANK, and f_c of fa_lowrank_len(.., r_c) floats.  Owners may differ in rank.  1 <= D
+ *              <= FA_LOWRANK_SUM_MAX_CLIENTS.
+ *              1. Weighted factor.  p'_c[a,t] = fl32(w_c * P_c[a,t]), one IEEE fp32 multiply, subnormals kept.  The weight
+ *                 goes onto P, never onto Q, and it is not applied in fp64: w P Q would then be no exact fp64 product.
+ *              2. Stacked sum, covered elements.  S = sum_c sum_{t < r_c} (double)p'_c[a,t] * (double)Q_c[b,t].  Every
+ *                 product is exact in fp64.  The order and grouping of the fp64 adds is NOT specified, the four-term sum
+ *                 inside a matrix instruction included; whatever the order, |S - exact| <= K 2^-53 sum |p' q| with K =
+ *                 sum_c r_c.  acc = fl32(S), one rounding to nearest-even.  The host twin adds in ascending (c, t).  Kernel
+ *                 and twin agree bit for bit wherever the partial sums are exact; elsewhere they differ by at most one fp32
+ *                 ulp, and only when S lies that close to a rounding boundary (low-rank receipts, rule 2).
+ *              3. Rest elements.  acc = +0; for every client c in ascending order acc = fmaf(w_c, d_c,i, acc), one fused
+ *                 operation: the chain of the other sum stages, bit-specified.
+ *              4. Aggregate.  a_i = fl32(widen(g_i) + acc_i): one IEEE add, never contracted; g widened exactly.  Without a
+ *                 reference (absolute mode) a_i = acc_i.  NaN and inf follow IEEE rules: a non-finite P_c[a,.] reaches row
+ *                 a only, a non-finite Q_c[b,.] column b only, and w_c = 0 with an inf in P_c gives NaN.
+ *              5. Weights, place in the round, reference, layout independence, admission: what rules 3-6 of the sparse-sum
+ *                 stage say, with fa_set_lowrank_sum and fa_submit_lowrank_sum in place of fa_set_sparse_sum and
+ *                 fa_submit_sparse (layout independence within rule 2: a covered element's fp64 adds may be grouped by
+ *                 tile).  Only on an FA_FEDAVG part; a member of the measure-then-select family: not with the clip, Krum,
+ *                 DnC, geomed, secagg, sign, sparse-sum or MX8-sum stage, and not with any of the four receipt formats
+ *                 (those setters refuse a low-rank-sum part in turn).  Not on an FA_SHARD_CLIENT_RS context, not as a
+ *                 context default.  A dense fa_submit to such a part is FA_ERR_STATE.  Setting the stage on a part drops
+ *                 what the round had received so far.
+ *                 Unlike MX8-sum rule 5 there is NO bit identity with the expanded route, not even in absolute mode: that
+ *                 route rounds each owner's product to fp32 and then chains them, this one rounds the sum once.  It is at
+ *                 least as accurate.
+ *              Memory: per GPU and client slot a shadow of fa_lowrank_len(.., r_max) floats, rounded up to 256 bytes,
+ *              allocated at the part's first fa_submit_lowrank_sum, and per GPU the plans of its pieces.  The part's dense
+ *              slots are neither read nor written by such a round; they stay allocated.
+ *              Added without a new FA_ABI_VERSION: fa_lowrank_sum_device with cnt == 0 touches no device and answers
+ *              FA_OK -- that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -1341,6 +1379,47 @@ int fa_set_lowrank(fa_ctx* ctx, int part_id, const fa_lowrank_mat* mats, size_t 
 #define FA_LOWRANK_ABSOLUTE 0x2
 int fa_submit_lowrank(fa_ctx* ctx, int part_id, int client_slot, const float* f, size_t len, int r, float weight,
                       int flags);
+
+/* Low-rank-sum stage (the header comment, "Low-rank-sum stage"): a round of low-rank receipts reduced as one stacked
+ * product on the fp64 matrix unit, without expanding them. */
+#define FA_LOWRANK_SUM_MAX_CLIENTS 128
+/* Rules 1-4 on the host, usable without a device: out[i] (fp32, cnt elements) is the aggregate of bucket element idx0 + i
+ * from the whole receipts f[c] of rank r[c] under w[c], c < D, and ref (fp32, cnt elements, NULL = absolute mode); the
+ * fp64 sums added in ascending (c, t).  FA_ERR_ARG for a bad table, D, rank or range and for null pointers. */
+int fa_lowrank_sum_host(const fa_lowrank_mat* mats, size_t M, size_t n, const float* const* f, const int* r, const float* w,
+                        int D, uint64_t idx0, size_t cnt, const float* ref, float* out);
+/* Rules 1-4 on raw device pointers, on device `gpu`: d_out[i] (cnt of out_dtype, one rounding) over bucket elements idx0 ..
+ * idx0 + cnt - 1 from d_ref (cnt of ref_dtype, NULL = absolute mode), the whole receipts d_f[c] (device memory, rank r[c])
+ * under w[c], and the plan built for exactly this range (d_plan, plan_bytes: fa_lowrank_plan_build; it does not depend on
+ * a rank, and a plan of another range leaves d_out untouched).  The arrays d_f, r and w themselves are host memory and are
+ * read before the call returns.  One launch: a workgroup per plan record; every store is checked against the tile, the
+ * matrix and the range, so nothing is written outside d_out[0, cnt).  ctx may be NULL (then `gpu` is the HIP device).
+ * Every argument is checked before any device call: the dtypes and their pair, 1 <= D <= FA_LOWRANK_SUM_MAX_CLIENTS, idx0 +
+ * cnt < 2^64, and for cnt > 0 every rank, the plan size, null pointers, alignment (FA_ERR_ALIGN: d_plan 8 bytes, every
+ * d_f[c] 4, d_ref and d_out their element) and that d_out does not overlap d_ref (FA_ERR_ARG); with cnt == 0 and valid
+ * arguments it returns FA_OK without touching a device.  Any element phase of d_ref and d_out is correct; 16-byte loads
+ * and stores are used where the two phases agree.  Async on hip_stream (NULL = the ctx's compute stream of `gpu`, or the
+ * null stream). */
+int fa_lowrank_sum_device(fa_ctx* ctx, int gpu, const void* d_plan, size_t plan_bytes, const float* const* d_f, const int* r,
+                          const float* w, int D, uint64_t idx0, size_t cnt, const void* d_ref, fa_dtype ref_dtype, void* d_out,
+                          fa_dtype out_dtype, void* hip_stream);
+/* Gives a part the stage (part_id >= 0, M > 0) over the table mats[0, M) (copied) for receipts of rank at most r_max: its
+ * rounds take low-rank receipts with fa_submit_lowrank_sum and reduce them by rules 1-4 against the part's last output;
+ * the round under way is dropped, and the plans of every GPU's range and piece are built and uploaded.  Again with the
+ * same table and r_max: nothing; with another: the shadows and what the round received go, the reference stays.  M == 0
+ * removes the stage and frees what it allocated.  FA_ERR_ARG, naming the cause: a bad table, r_max outside 1 ..
+ * FA_LOWRANK_MAX_RANK, D > FA_LOWRANK_SUM_MAX_CLIENTS, part_id < 0 (no context default), a part whose mode is not
+ * FA_FEDAVG, a part with a clip, Krum, DnC, geomed, secagg, sign, sparse-sum, MX8-sum or receipt stage (those setters
+ * refuse a low-rank-sum part in turn), an FA_SHARD_CLIENT_RS context.  In DESIGN.md 8r the stage takes 0.23 - 0.79 of the
+ * expanded route's device time at r = 4 and 16 (D = 8, 32, 64; 64 matrices of 1024 x 1024 fp32) and 1.03 - 1.08 at r = 64:
+ * there it loses a few percent of time and keeps the single rounding. */
+int fa_set_lowrank_sum(fa_ctx* ctx, int part_id, const fa_lowrank_mat* mats, size_t M, int r_max);
+/* The low-rank receipt of client `client_slot`: rank r <= r_max and f, len values, where len must be fa_lowrank_len(.., r)
+ * (FA_ERR_ARG otherwise, as for r; the round stays as it was), under `weight` (rule 5).  flags: FA_HOST_PINNED as for
+ * fa_submit_mx8.  Enqueues the H2D of f to every GPU that holds part of the part, into the slot's shadow (allocated at the
+ * part's first submit); the slot then counts as submitted.  FA_ERR_STATE on a part without fa_set_lowrank_sum. */
+int fa_submit_lowrank_sum(fa_ctx* ctx, int part_id, int client_slot, const float* f, size_t len, int r, float weight,
+                          int flags);
 
 /* Rot1 receipts (the header comment, "Rot1 receipts"): Hadamard sign codes, expanded on the GPU by fp16 MFMA. */
 #define FA_ROT1_BLOCK 4096

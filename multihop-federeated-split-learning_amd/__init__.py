@@ -184,6 +184,10 @@ def lib():
         "fa_mx8_sum_form": (I, [S, P, I, U64, P, I, P, I]),
         "fa_set_mx8_sum": (I, [P, I, I]),
         "fa_submit_mx8_sum": (I, [P, I, I, P, P, F, I]),
+        "fa_lowrank_sum_host": (I, [P, S, S, P, P, P, I, U64, S, P, P]),
+        "fa_lowrank_sum_device": (I, [P, I, P, S, P, P, P, I, U64, S, P, I, P, I, P]),
+        "fa_set_lowrank_sum": (I, [P, I, P, S, I]),
+        "fa_submit_lowrank_sum": (I, [P, I, I, P, S, I, F, I]),
         "fa_diag_secagg_unmask": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, I, P]),  # diagnostic (outside fa.h)
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
@@ -738,6 +742,52 @@ def lowrank_expand_device(plan, f, r, cnt, dst, dst_dtype=F32, ref=None, ref_dty
     check(lib().fa_lowrank_expand_device(ctx.handle if ctx is not None else None, gpu, _addr(plan), int(plan_bytes),
                                          _addr(f), int(r), int(idx0), cnt, _addr(ref), ref_dtype, _addr(dst), dst_dtype,
                                          _stream(stream)))
+
+
+LOWRANK_SUM_MAX_CLIENTS = 128  # FA_LOWRANK_SUM_MAX_CLIENTS
+
+
+def _lowrank_sum_args(f, r, weights):
+    """The pointer array, the ranks and the weights of D receipts f[c] of rank r[c].  Returns arrays the caller keeps until
+    the call returns."""
+    D = len(f)
+    r = np.ascontiguousarray(r, np.int32).reshape(-1)
+    w = np.ascontiguousarray(np.ones(D) if weights is None else weights, np.float32).reshape(-1)
+    if r.size != D or w.size != D:
+        raise ValueError("need one rank and one weight per client")
+    return (ctypes.c_void_p * max(1, D))(*[_addr(x) for x in f]), r, w, D
+
+
+def lowrank_sum_host(f, r, mats, n, weights=None, ref=None, idx0=0, cnt=None):
+    """fa_lowrank_sum_host (host arithmetic, fa.h "Low-rank-sum stage" rules 1-4): the fp32 aggregate of bucket elements
+    idx0 .. idx0 + cnt - 1 (cnt None: to the end) from the receipts f[c] of rank r[c] under `weights` (None: ones) and
+    ref (fp32[cnt], None: absolute mode)."""
+    t = _lowrank_table(mats)
+    f = [np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1)) for x in f]
+    for x, rc in zip(f, r):
+        if x.size != lowrank_len(t, n, rc):
+            raise ValueError("%d values, a receipt of rank %d has %d" % (x.size, rc, lowrank_len(t, n, rc)))
+    pf, r, w, D = _lowrank_sum_args(f, r, weights)
+    cnt = n - idx0 if cnt is None else cnt
+    if ref is not None:
+        ref = np.ascontiguousarray(np.asarray(ref, np.float32).reshape(-1))
+    out = np.empty(cnt, np.float32)
+    check(lib().fa_lowrank_sum_host(t.ctypes.data, t.size, n, pf, r.ctypes.data, w.ctypes.data, D, int(idx0), cnt, _addr(ref),
+                                    out.ctypes.data))
+    return out
+
+
+def lowrank_sum_device(plan, f, r, cnt, out, out_dtype=F32, weights=None, ref=None, ref_dtype=F32, idx0=0, plan_bytes=None,
+                       stream=None, gpu=0, ctx=None):
+    """fa_lowrank_sum_device: out[i] = ref[i] + acc_i (ref None: acc_i) over cnt device-resident elements, bucket elements
+    idx0 .., from the D device-resident receipts f[c] of rank r[c] under `weights` and the device-resident plan of exactly
+    that range (lowrank_plan).  Enqueued, not synchronized.  With cnt == 0 no device is touched: the feature probe."""
+    if plan_bytes is None:
+        plan_bytes = plan.numel() * plan.element_size() if hasattr(plan, "numel") else getattr(plan, "nbytes", 0)
+    pf, r, w, D = _lowrank_sum_args(f, r, weights)
+    check(lib().fa_lowrank_sum_device(ctx.handle if ctx is not None else None, gpu, _addr(plan), int(plan_bytes), pf,
+                                      r.ctypes.data, w.ctypes.data, D, int(idx0), cnt, _addr(ref), ref_dtype, _addr(out),
+                                      out_dtype, _stream(stream)))
 
 
 def lowrank_encode(delta, mats, r):
@@ -1486,6 +1536,22 @@ class Aggregator:
             raise ValueError("need f float32")
         flags = (HOST_PINNED if pinned else 0) | (LOWRANK_ABSOLUTE if absolute else 0)
         check(lib().fa_submit_lowrank(self.handle, part, slot, f.ctypes.data, f.size, int(r), float(weight), flags))
+
+    def set_lowrank_sum(self, part, mats, r_max):
+        """fa_set_lowrank_sum: the part's rounds take low-rank receipts of rank at most r_max over the table
+        (submit_lowrank_sum) and reduce them as one stacked product, without expanding them; an empty table removes
+        the stage."""
+        t = _lowrank_table(mats)
+        check(lib().fa_set_lowrank_sum(self.handle, part, t.ctypes.data, t.size, int(r_max)))
+
+    def submit_lowrank_sum(self, part, slot, f, r, weight=1.0, pinned=False):
+        """fa_submit_lowrank_sum: the client's update as the fp32 receipt f of rank r, kept as it is until the reducing
+        call.  pinned: a view of a PinnedBuffer the caller keeps unchanged until the round is reduced."""
+        f = np.ascontiguousarray(f)
+        if f.dtype != np.float32:
+            raise ValueError("need f float32")
+        check(lib().fa_submit_lowrank_sum(self.handle, part, slot, f.ctypes.data, f.size, int(r), float(weight),
+                                          HOST_PINNED if pinned else 0))
 
     def set_rot1(self, on=True, part=None):
         """fa_set_rot1: the part takes rot1 receipts, on the stage and the reference of set_mx8 (part None: the default

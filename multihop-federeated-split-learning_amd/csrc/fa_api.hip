@@ -304,6 +304,7 @@ void set_range_runs(Part& p, int G) {
     p.sign.ref = p.sign.on();
     p.sparse.ref = p.sparse.on();
     p.mx8sum.ref = p.mx8sum.on();
+    p.lrsum.ref = p.lrsum.on();
     for (int g = 0; g < G; ++g) {
         p.runs[(size_t)g] = {Run{0, p.off[(size_t)g], p.cnt[(size_t)g]}};
         p.run_src[(size_t)g] = p.dout[(size_t)g];
@@ -796,6 +797,7 @@ int submit_impl(fa_ctx* ctx, int part_id, int slot, const Gather& src, float wei
     if (p->sign.on()) return fail(FA_ERR_STATE, "part %d has a sign-vote stage: it takes sign receipts (fa_submit_sign)", part_id);
     if (p->sparse.on()) return fail(FA_ERR_STATE, "part %d has a sparse-sum stage: it takes top-k receipts (fa_submit_sparse)", part_id);
     if (p->mx8sum.on()) return fail(FA_ERR_STATE, "part %d has an MX8-sum stage: it takes MX8 receipts (fa_submit_mx8_sum)", part_id);
+    if (p->lrsum.on()) return fail(FA_ERR_STATE, "part %d has a low-rank-sum stage: it takes low-rank receipts (fa_submit_lowrank_sum)", part_id);
     if ((rc = src.check("host source"))) return rc;
     const size_t si = dsize(p->in), total = src.total();
     if (total != p->n * si)
@@ -863,6 +865,7 @@ int piece_impl(fa_ctx* ctx, int part_id, int slot, size_t at, const void* src, s
     if (p->sign.on()) return fail(FA_ERR_STATE, "part %d has a sign-vote stage: it takes sign receipts (fa_submit_sign)", part_id);
     if (p->sparse.on()) return fail(FA_ERR_STATE, "part %d has a sparse-sum stage: it takes top-k receipts (fa_submit_sparse)", part_id);
     if (p->mx8sum.on()) return fail(FA_ERR_STATE, "part %d has an MX8-sum stage: it takes MX8 receipts (fa_submit_mx8_sum)", part_id);
+    if (p->lrsum.on()) return fail(FA_ERR_STATE, "part %d has a low-rank-sum stage: it takes low-rank receipts (fa_submit_lowrank_sum)", part_id);
     const size_t si = dsize(p->in);
     if (at > p->n * si || len > p->n * si - at)
         return fail(FA_ERR_ARG, "piece [%zu, %zu) outside part %d's %zu bytes", at, at + len, part_id, p->n * si);
@@ -1612,6 +1615,7 @@ int fa_submit_commit(fa_ctx* ctx, int part_id, int client_slot, float weight) {
     if (p->sign.on()) return fail(FA_ERR_STATE, "part %d has a sign-vote stage: it takes sign receipts (fa_submit_sign)", part_id);
     if (p->sparse.on()) return fail(FA_ERR_STATE, "part %d has a sparse-sum stage: it takes top-k receipts (fa_submit_sparse)", part_id);
     if (p->mx8sum.on()) return fail(FA_ERR_STATE, "part %d has an MX8-sum stage: it takes MX8 receipts (fa_submit_mx8_sum)", part_id);
+    if (p->lrsum.on()) return fail(FA_ERR_STATE, "part %d has a low-rank-sum stage: it takes low-rank receipts (fa_submit_lowrank_sum)", part_id);
     if (p->host_src[(size_t)client_slot].size()) {  // an earlier receipt kept in place would shadow the pieces
         p->host_src[(size_t)client_slot].clear();
         --p->n_host;

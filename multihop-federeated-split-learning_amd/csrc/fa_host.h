@@ -276,7 +276,8 @@ struct DevArrays {
 //   secagg           restart_round_plain, no terms        the round stays    the round stays, the terms go
 //   sign sparse      reset_round: the receipts go         the round stays    the round stays, the shadows go
 //   mx8 sum          reset_round: the receipts go         the round stays    the round stays, the shadows go
-enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kSign, kSparse, kMx8Sum, kStages };
+//   lowrank sum      reset_round: the receipts go         as sparse          the round stays, the shadows go
+enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kSign, kSparse, kMx8Sum, kLowrankSum, kStages };
 
 struct OptCfg : fa_server_opt {  // fa.h "Server optimizer"
     OptCfg(const fa_server_opt& o = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f}) : fa_server_opt(o) {}
@@ -344,6 +345,15 @@ struct Mx8SumCfg {  // fa.h "MX8-sum stage"
     bool flag = false;
     bool on() const { return flag; }
 };
+struct LowrankSumCfg {  // fa.h "Low-rank-sum stage": the part's table and the rank a receipt may have
+    std::vector<fa_lowrank_mat> mats;
+    int r_max = 0;
+    bool same(const LowrankSumCfg& o) const {
+        return r_max == o.r_max && mats.size() == o.mats.size() &&
+               (mats.empty() || !std::memcmp(mats.data(), o.mats.data(), mats.size() * sizeof(fa_lowrank_mat)));
+    }
+    bool on() const { return !mats.empty(); }
+};
 struct StageCfgs {
     OptCfg opt;
     ClipCfg clip;
@@ -358,6 +368,7 @@ struct StageCfgs {
     SignCfg sign;
     SparseCfg sparse;
     Mx8SumCfg mx8sum;
+    LowrankSumCfg lrsum;
 };
 
 // Per GPU the fp32 state over its cnt elements (v only for the adaptive rules).
@@ -499,12 +510,25 @@ struct Mx8SumStage {
     std::vector<size_t> stride, eoff;
     bool on() const { return cfg.on(); }
 };
+// ref: the device output holds a reference, as Mx8Stage::ref.  plan: per GPU the low-rank plans of its pieces back to back,
+// piece j at plan_at[g][j] with plan_len[g][j] bytes, built and uploaded by fa_set_lowrank_sum; factors: per GPU the
+// shadows of its held slots, fstride bytes apart (a whole receipt of rank r_max), allocated at the first
+// fa_submit_lowrank_sum; rank[slot]: the rank of the slot's last receipt.
+struct LowrankSumStage {
+    LowrankSumCfg cfg;
+    bool ref = false;
+    DevArrays plan, factors;
+    std::vector<std::vector<size_t>> plan_at, plan_len;
+    size_t fstride = 0;
+    std::vector<int> rank;
+    bool on() const { return cfg.on(); }
+};
 // The stages that are on in a StageCfgs or a Part, one bit per StageId.
 template <class S>
 inline unsigned stages_on(const S& s) {
     return s.opt.on() << kOpt | s.clip.on() << kClip | s.krum.on() << kKrum | s.geomed.on() << kGeomed |
            s.bulyan.on() << kBulyan | s.noise.on() << kNoise | s.mx8.on() << kMx8 | s.reply.on() << kReply | s.secagg.on() << kSecagg |
-           s.dnc.on() << kDnc | s.sign.on() << kSign | s.sparse.on() << kSparse | s.mx8sum.on() << kMx8Sum;
+           s.dnc.on() << kDnc | s.sign.on() << kSign | s.sparse.on() << kSparse | s.mx8sum.on() << kMx8Sum | s.lrsum.on() << kLowrankSum;
 }
 
 struct Part {
@@ -565,6 +589,7 @@ struct Part {
     SignStage sign;
     SparseStage sparse;
     Mx8SumStage mx8sum;
+    LowrankSumStage lrsum;
     DevArrays oavg;
 };
 

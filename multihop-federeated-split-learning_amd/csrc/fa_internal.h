@@ -295,6 +295,16 @@ void lowrank_decode_host(const fa_lowrank_mat* mats, size_t M, uint64_t n, const
                          uint64_t cnt, float* d);
 hipError_t launch_lowrank_expand(const void* plan, size_t plan_bytes, const float* f, int r, uint64_t idx0, int64_t cnt,
                                  const void* ref, fa_dtype rdt, void* dst, fa_dtype ddt, hipStream_t s);
+// The low-rank-sum stage (fa.h "Low-rank-sum stage"), fa_lowrank_sum.hip.  out[i] (dtype odt, one rounding) :=
+// fl32(widen(ref[i]) + acc_i), or acc_i with ref null, over cnt elements from the D whole receipts f[c] of rank r[c]
+// (device memory; the arrays f, r and w are host memory) under w[c] and the plan of exactly that range (device
+// memory, lowrank_plan_build); every store is checked against [0, cnt).  On a matrix acc_i is the stacked product of
+// rules 1-2, elsewhere the fmaf chain of rule 3.
+hipError_t launch_lowrank_sum(const void* plan, size_t plan_bytes, const float* const* f, const int* r, const float* w, int D,
+                              uint64_t idx0, int64_t cnt, const void* ref, fa_dtype rdt, void* out, fa_dtype odt, hipStream_t s);
+// Rules 1-4 on the host (fa_lowrank_sum_host): ascending (c, t) on a matrix, ascending c elsewhere.
+void lowrank_sum_host(const fa_lowrank_mat* mats, size_t M, uint64_t n, const float* const* f, const int* r, const float* w,
+                      int D, uint64_t idx0, uint64_t cnt, const float* ref, float* out);
 // Rot1 receipts (fa.h "Rot1 receipts"), fa_rot1.hip.  Expansion: dst[i] (dtype ddt, one rounding) := fl(widen(ref[i]) +
 // d_i), or d_i with ref null, over bucket elements [idx0, idx0 + cnt), any idx0; bits (128 words per block) and scale
 // (one per block) start at block idx0 >> 12; every store is checked against the range.  Encoding over n elements of

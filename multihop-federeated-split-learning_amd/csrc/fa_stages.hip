@@ -551,12 +551,17 @@ void free_mx8sum(fa_ctx* ctx, Part& p) {
     p.mx8sum.buf.free(ctx->gpu);
     p.mx8sum = Mx8SumStage{};
 }
+void free_lrsum(fa_ctx* ctx, Part& p) {
+    for (DevArrays* a : {&p.lrsum.plan, &p.lrsum.factors}) a->free(ctx->gpu);
+    p.lrsum = LowrankSumStage{};
+}
 void free_stages(fa_ctx* ctx, Part& p) {
     p.noise = NoiseStage{};
     free_secagg(ctx, p);
     free_sign(ctx, p);
     free_sparse(ctx, p);
     free_mx8sum(ctx, p);
+    free_lrsum(ctx, p);
     free_mx8(ctx, p);
     free_reply(ctx, p);
     free_opt(ctx, p);
@@ -1293,6 +1298,83 @@ int mx8sum_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, void* dst, 
     return FA_OK;
 }
 
+// ------------------------------------------------------------------ low-rank-sum stage
+
+int check_lrsum_clients(int D) {
+    if (D < 1 || D > FA_LOWRANK_SUM_MAX_CLIENTS)
+        return fail(FA_ERR_ARG, "lowrank sum: D = %d clients outside 1 .. %d", D, FA_LOWRANK_SUM_MAX_CLIENTS);
+    return FA_OK;
+}
+
+// The factor shadows of a part, allocated once per table and r_max: per GPU held x fstride bytes, a shadow the whole
+// receipt at rank r_max.  On failure the part keeps the stage.
+int ensure_lrsum_buf(fa_ctx* ctx, Part& p) {
+    LowrankSumStage& s = p.lrsum;
+    if (s.factors) return FA_OK;
+    s.fstride = ((size_t)fa::lowrank_len(s.cfg.mats.data(), s.cfg.mats.size(), p.n, s.cfg.r_max) * 4 + 255) / 256 * 256;
+    s.rank.assign((size_t)p.D, 0);
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.fstride); };
+    const int g = s.factors.alloc(ctx->gpu, bytes);
+    if (g < 0) return FA_OK;
+    return fail(FA_ERR_NOMEM, "lowrank sum: shadow alloc of %zu B failed on GPU %zu", bytes((size_t)g), (size_t)g);
+}
+
+int submit_lowrank_sum_impl(fa_ctx* ctx, int part_id, int slot, const float* f, size_t len, int r, float weight, int flags) {
+    Trace tr("fa_submit_lowrank_sum part %d slot %d", part_id, slot);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (flags & ~FA_HOST_PINNED) return fail(FA_ERR_ARG, "lowrank sum: unknown flags 0x%x", flags);
+    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    const LowrankSumCfg& c = p->lrsum.cfg;
+    if (!c.on()) return fail(FA_ERR_STATE, "lowrank sum: part %d has no low-rank-sum stage (fa_set_lowrank_sum)", part_id);
+    if (r < 1 || r > c.r_max)
+        return fail(FA_ERR_ARG, "lowrank sum: rank %d, part %d takes 1 .. %d (fa_set_lowrank_sum)", r, part_id, c.r_max);
+    const size_t need = (size_t)fa::lowrank_len(c.mats.data(), c.mats.size(), p->n, r);
+    if (len != need)
+        return fail(FA_ERR_ARG, "lowrank sum: %zu values, a receipt of rank %d for part %d has %zu (fa_lowrank_len)", len, r, part_id, need);
+    if (len && !f) return fail(FA_ERR_ARG, "lowrank sum: f is null");
+    if ((rc = ensure_lrsum_buf(ctx, *p))) return rc;
+    const bool pinned = (flags & FA_HOST_PINNED) != 0;
+    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
+        GpuRes& gr = ctx->gpu[(size_t)g];
+        DeviceGuard dg(gr.dev);
+        if (p->cnt[(size_t)g] == 0) return FA_OK;
+        // after the part's last reducing call: it read the shadow
+        if (hipStream_t ds = p->done_stream[(size_t)g]) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(gr.copy, p->done[(size_t)g], 0));
+        }
+        char* df = p->lrsum.factors.at((size_t)g) + (size_t)(slot - p->c0[(size_t)g]) * p->lrsum.fstride;
+        ++gr.copy_gen;  // the next reducing call waits for the copy stream
+        return mx8_h2d(gr, df, reinterpret_cast<const char*>(f), len * 4, pinned);
+    });
+    if (rc) return rc;
+    p->lrsum.rank[(size_t)slot] = r;
+    return mark_submitted(ctx, *p, slot, weight);
+}
+
+// Before the round's launches: the receipts are there.
+int lowranksum_round_begin(const Part& p) {
+    if (!p.lrsum.factors) return fail(FA_ERR_STATE, "lowrank sum: part %d has no low-rank receipts (fa_submit_lowrank_sum)", p.id);
+    return FA_OK;
+}
+
+// Rules 1-4 for piece j of GPU g (the current device), into dst (dtype odt): every client's whole receipt under w with
+// the piece's plan, the reference in the part's output (dst itself where the aggregate is reduced in place).
+int lowranksum_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, void* dst, fa_dtype odt, hipStream_t st) {
+    const LowrankSumStage& s = p.lrsum;
+    const size_t lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
+    if (cnt == 0) return FA_OK;
+    std::vector<const float*> f((size_t)p.D);
+    for (int c = 0; c < p.D; ++c)
+        f[(size_t)c] = reinterpret_cast<const float*>(s.factors.at((size_t)g) + (size_t)(c - p.c0[(size_t)g]) * s.fstride);
+    const void* ref = s.ref ? static_cast<const char*>(p.dout[(size_t)g]) + lo * dsize(p.out) : nullptr;
+    FA_HIP(fa::launch_lowrank_sum(s.plan.at((size_t)g) + s.plan_at[(size_t)g][(size_t)j], s.plan_len[(size_t)g][(size_t)j], f.data(),
+                                  s.rank.data(), w, p.D, (uint64_t)(p.off[(size_t)g] + lo), (int64_t)cnt, ref, p.out, dst, odt, st));
+    return FA_OK;
+}
+
 // ------------------------------------------------------------------ one reducing call, as the stages see it
 
 int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, StageRound* rd) {
@@ -1322,6 +1404,7 @@ int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, Stage
     if (p.sign.on()) return sign_round_begin(ctx, p);
     if (p.sparse.on()) return sparse_round_begin(p);
     if (p.mx8sum.on()) return mx8sum_round_begin(p);
+    if (p.lrsum.on()) return lowranksum_round_begin(p);
     return FA_OK;
 }
 
@@ -1351,6 +1434,8 @@ int stage_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, const StageR
         rc = sparse_piece(ctx, p, g, j, w, adst, adt, st);
     else if (p.mx8sum.on())
         rc = mx8sum_piece(ctx, p, g, j, w, adst, adt, st);
+    else if (p.lrsum.on())
+        rc = lowranksum_piece(ctx, p, g, j, w, adst, adt, st);
     else
         rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                        mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
@@ -1530,31 +1615,33 @@ int set_part_flag(fa_ctx* ctx, Part& p, bool reply, bool on) {
     return FA_OK;
 }
 
-// The low-rank plans of a part with the table in its config: per GPU one allocation with the plan of every piece's
-// range, uploaded with a plain copy (a setter is no hot path).
-int upload_lowrank_plans(fa_ctx* ctx, Part& p) {
-    Mx8Stage& s = p.mx8;
-    const std::vector<fa_lowrank_mat>& m = s.cfg.mats;
+// The low-rank plans of a part over the table m (the receipt format's, or the low-rank-sum stage's): per GPU one
+// allocation with the plan of every piece's range, uploaded with a plain copy (a setter is no hot path).
+int upload_plans(fa_ctx* ctx, Part& p, const std::vector<fa_lowrank_mat>& m, DevArrays& plan,
+                 std::vector<std::vector<size_t>>& plan_at, std::vector<std::vector<size_t>>& plan_len) {
     std::vector<std::vector<char>> blob((size_t)ctx->G);
-    s.plan_at.assign((size_t)ctx->G, {});
-    s.plan_len.assign((size_t)ctx->G, {});
+    plan_at.assign((size_t)ctx->G, {});
+    plan_len.assign((size_t)ctx->G, {});
     for (int g = 0; g < ctx->G; ++g)
         for (int j = 0; j < p.npiece[(size_t)g] && p.cnt[(size_t)g]; ++j) {
             const uint64_t i0 = p.off[(size_t)g] + piece_lo(p, g, j), pc = piece_cnt(p, g, j);
             const size_t at = blob[(size_t)g].size(), len = fa::lowrank_plan_bytes(m.data(), m.size(), p.n, i0, pc);
             blob[(size_t)g].resize(at + len);
             fa::lowrank_plan_build(m.data(), m.size(), p.n, i0, pc, blob[(size_t)g].data() + at);
-            s.plan_at[(size_t)g].push_back(at);
-            s.plan_len[(size_t)g].push_back(len);
+            plan_at[(size_t)g].push_back(at);
+            plan_len[(size_t)g].push_back(len);
         }
     const auto bytes = [&](size_t g) { return std::max<size_t>(256, blob[g].size()); };
-    const int bad = s.plan.alloc(ctx->gpu, bytes);
+    const int bad = plan.alloc(ctx->gpu, bytes);
     if (bad >= 0) return fail(FA_ERR_NOMEM, "lowrank: plan alloc of %zu B failed on GPU %d", bytes((size_t)bad), bad);
     for (size_t g = 0; g < (size_t)ctx->G; ++g) {
         DeviceGuard dg(ctx->gpu[g].dev);
-        if (!blob[g].empty()) FA_HIP(hipMemcpy(s.plan.at(g), blob[g].data(), blob[g].size(), hipMemcpyHostToDevice));
+        if (!blob[g].empty()) FA_HIP(hipMemcpy(plan.at(g), blob[g].data(), blob[g].size(), hipMemcpyHostToDevice));
     }
     return FA_OK;
+}
+int upload_lowrank_plans(fa_ctx* ctx, Part& p) {
+    return upload_plans(ctx, p, p.mx8.cfg.mats, p.mx8.plan, p.mx8.plan_at, p.mx8.plan_len);
 }
 
 // The receipt stage of a part becomes c (any of MX8, top-k and low-rank, or none).  The stage itself goes on and off as
@@ -1672,8 +1759,35 @@ int set_part_mx8sum(fa_ctx* ctx, Part& p, const Mx8SumCfg& c) {
     return FA_OK;
 }
 
+// fa_set_lowrank_sum on a part (an FA_FEDAVG part of at most FA_LOWRANK_SUM_MAX_CLIENTS clients, not rs).  Off: the plans
+// and the shadows go, after the devices' pending work.  The same table and r_max: nothing.  Another: they go as well and
+// with them what the round received; the reference stays (the part's output).  The first time: what the round received
+// so far is dropped: dense receipts are no low-rank receipts.  The plans are uploaded before the config takes the table.
+int set_part_lrsum(fa_ctx* ctx, Part& p, const LowrankSumCfg& c) {
+    if (p.lrsum.on() && c.same(p.lrsum.cfg)) return FA_OK;
+    bool ref = false;
+    if (p.lrsum.on()) {
+        if (int rc = wait_devices(ctx)) return rc;
+        ref = p.lrsum.ref;
+        free_lrsum(ctx, p);
+        if (!c.on()) return FA_OK;
+    } else {
+        if (!c.on()) return FA_OK;
+        if (int rc = host_flush(ctx, p)) return rc;
+    }
+    reset_round(p);
+    if (int rc = upload_plans(ctx, p, c.mats, p.lrsum.plan, p.lrsum.plan_at, p.lrsum.plan_len)) {
+        free_lrsum(ctx, p);
+        return rc;
+    }
+    p.lrsum.cfg = c;
+    p.lrsum.ref = ref;
+    return FA_OK;
+}
+
 int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
     switch (id) {
+        case kLowrankSum: return set_part_lrsum(ctx, p, c.lrsum);
         case kMx8Sum: return set_part_mx8sum(ctx, p, c.mx8sum);
         case kSparse: return set_part_sparse(ctx, p, c.sparse);
         case kSign: return set_part_sign(ctx, p, c.sign);
@@ -1714,7 +1828,7 @@ const StageRule kRules[kStages] = {
     {"bulyan", "Bulyan", kTrim, false, 0, "the rule needs every client on one GPU; use FA_SHARD_RANGE",
      " (the stage replaces the window of an FA_TRIMMED part)"},
     {"noise", "noise", kAvg | kTrim, false, 0, "its aggregate is not bit-specified; use FA_SHARD_RANGE", ""},
-    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg | 1u << kSign | 1u << kSparse | 1u << kMx8Sum, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
+    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg | 1u << kSign | 1u << kSparse | 1u << kMx8Sum | 1u << kLowrankSum, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
     {"mx8 reply", "reply", kAvg | kTrim, false, 0, "use FA_SHARD_RANGE", ""},
     {"secagg", "secagg", kAvg, true, 1u << kMx8, "its sum is taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage unmasks the sum of an FA_FEDAVG part)"},
@@ -1725,6 +1839,8 @@ const StageRule kRules[kStages] = {
     {"sparse", "sparse-sum", kAvg, true, 1u << kMx8, "its sums are taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage sums the updates of an FA_FEDAVG part)"},
     {"mx8 sum", "MX8-sum", kAvg, true, 1u << kMx8, "its sums are taken over every client of an element; use FA_SHARD_RANGE",
+     " (the stage sums the updates of an FA_FEDAVG part)"},
+    {"lowrank sum", "low-rank-sum", kAvg, true, 1u << kMx8, "its sums are taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage sums the updates of an FA_FEDAVG part)"},
 };
 
@@ -1770,6 +1886,7 @@ int check_for_clients(StageId id, int D, StageCfgs& c) {
     if (id == kSign) return check_sign_clients(D, c.sign.margin);
     if (id == kSparse) return check_sparse_clients(D);
     if (id == kMx8Sum) return check_mx8sum_clients(D);
+    if (id == kLowrankSum) return check_lrsum_clients(D);
     return id == kBulyan ? check_bulyan(D, c.bulyan.f) : FA_OK;
 }
 
@@ -2866,6 +2983,31 @@ int fa_submit_mx8_sum(fa_ctx* ctx, int part_id, int client_slot, const int8_t* q
     return submit_mx8_sum_impl(ctx, part_id, client_slot, q, e, weight, flags);
 }
 
+int fa_set_lowrank_sum(fa_ctx* ctx, int part_id, const fa_lowrank_mat* mats, size_t M, int r_max) {
+    g_err.clear();
+    if (!ctx) return fail(FA_ERR_ARG, "ctx is null");
+    if (part_id < 0)
+        return fail(FA_ERR_ARG, "lowrank sum: set on a part, not as a context default (a table belongs to one part's layout)");
+    StageCfgs c = requested(ctx);
+    c.lrsum = LowrankSumCfg{};
+    if (M) {
+        Part* p;
+        if (int rc = check_part(ctx, part_id, &p)) return rc;
+        if (int rc = fa_lowrank_check(mats, M, p->n)) return rc;
+        if (r_max < 1 || r_max > FA_LOWRANK_MAX_RANK)
+            return fail(FA_ERR_ARG, "lowrank sum: r_max %d outside 1 .. %d", r_max, FA_LOWRANK_MAX_RANK);
+        c.lrsum.mats.assign(mats, mats + M);
+        c.lrsum.r_max = r_max;
+    }
+    return set_stage(ctx, part_id, kLowrankSum, c);
+}
+
+int fa_submit_lowrank_sum(fa_ctx* ctx, int part_id, int client_slot, const float* f, size_t len, int r, float weight,
+                          int flags) {
+    g_err.clear();
+    return submit_lowrank_sum_impl(ctx, part_id, client_slot, f, len, r, weight, flags);
+}
+
 size_t fa_mx8_scale_bytes(size_t n) { return n / FA_MX8_BLOCK + (n % FA_MX8_BLOCK ? 1 : 0); }
 
 int fa_mx8_encode(const float* delta, size_t n, int8_t* q, uint8_t* e) {
@@ -2976,10 +3118,10 @@ int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
     g_err.clear();
     Part* p;
     if (int rc = check_part(ctx, part_id, &p)) return rc;
-    if (!p->mx8.on() && !p->reply.on() && !p->sign.on() && !p->sparse.on() && !p->mx8sum.on())
+    if (!p->mx8.on() && !p->reply.on() && !p->sign.on() && !p->sparse.on() && !p->mx8sum.on() && !p->lrsum.on())
         return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
                                   "(fa_set_mx8_reply), nor takes top-k (fa_set_topk), low-rank (fa_set_lowrank) or rot1 receipts (fa_set_rot1), "
-                                  "nor has a sign-vote (fa_set_sign), sparse-sum (fa_set_sparse_sum) or MX8-sum stage (fa_set_mx8_sum)", part_id);
+                                  "nor has a sign-vote (fa_set_sign), sparse-sum (fa_set_sparse_sum), MX8-sum (fa_set_mx8_sum) or low-rank-sum stage (fa_set_lowrank_sum)", part_id);
     if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
     if (int rc = wait_devices(ctx)) return rc;  // the part's pending work, on whatever stream
     if (p->reply.on())
