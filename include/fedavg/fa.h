@@ -692,6 +692,55 @@
  *              slots are neither read nor written by such a round; they stay allocated.
  *              Added without a new FA_ABI_VERSION: fa_lowrank_sum_device with cnt == 0 touches no device and answers
  *              FA_OK -- that is how a caller probes for it.
+ *   Rot1-sum stage (fa_set_rot1_sum, fa_submit_rot1_sum, fa_rot1_sum_device, fa_rot1_sum_host): a round of rot1 receipts
+ *              reduced in the rotated domain, without expanding them.  The transform is linear: with H the +-1 transform W,
+ *              D_s the sign diagonal of seed s and u_c the +-1 vector of owner c's bits, for the owners that share s
+ *                  sum_c w_c D_s(scale_c H u_c) = D_s H(sum_c (w_c scale_c) u_c),
+ *              so the round adds the owners' signed scalars per rotated coordinate, D adds and no multiply, runs one
+ *              real-valued transform per block and seed, and adds g once: D / 8 + 8 bytes per element with fp32 g and
+ *              output, where fa_submit_rot1 and the chain move about 12 D + 4.
+ *              Format: the rot1 receipt, unchanged (bits, scale, seed; fa_rot1_encode and fa_rot1_encode_device stay the
+ *              owner's side).  1 <= D <= FA_ROT1_SUM_MAX_CLIENTS.  Block b is elements [4096 b, 4096 b + 4096) of the
+ *              whole bucket, never of a shard or a piece.
+ *              0. Seed groups.  The owners of a round are grouped by seed; the groups are ordered by their lowest client
+ *                 slot, the owners of a group by ascending slot.  One seed for all (the server announced the rotation) is
+ *                 one group, the fast case; a seed per owner (DRIVE's independent rotations, whose quantisation errors
+ *                 average out better) is D groups: still no dense slot moves, but every owner pays a transform.  Both
+ *                 are valid, the choice is the caller's; DESIGN.md 8s says what each costs.
+ *              1. Scalar.  Per block b and owner c: t_c = fl32(w_c * scale_c,b), one IEEE multiply.
+ *              2. Rotated-domain chain.  Per group G and position j of the block (all 4096, the zero-padded tail of the
+ *                 last block included): z_j = +0; then for the owners c of G in order z_j = fl32(z_j + s), s being t_c
+ *                 with its IEEE sign bit flipped where bit j of owner c is set.  Plain adds, never contracted.
+ *              3. Transform.  v = W(z), exactly "Transform W" of Rot1 receipts: h = 1, 2, .., 2048 in that order,
+ *                 fl32(a + b) and fl32(a - b), subnormals kept.
+ *              4. Diagonal.  d_G,i is v_i with its sign flipped where the group's seed says so ("Diagonal D").
+ *              5. Sum over groups.  acc_i = +0; then for the groups in order acc_i = fl32(acc_i + d_G,i).
+ *              6. Aggregate.  a_i = fl32(widen(g_i) + acc_i), one IEEE add; without a reference (absolute mode) a_i =
+ *                 acc_i.  Elements at or beyond n are dropped.  NaN and inf in scale, w or g follow IEEE rules: a NaN
+ *                 scale, which the encoder emits for a non-finite block, makes that block NaN and no other.  NaN payloads
+ *                 are unspecified.
+ *              7. Weights, place in the round, reference, layout independence, admission: what rules 3-6 of the sparse-sum
+ *                 stage say, with fa_set_rot1_sum and fa_submit_rot1_sum in place of fa_set_sparse_sum and
+ *                 fa_submit_sparse.  The weights are the owners' shares of the *update* and g enters with weight one; a
+ *                 stands exactly where the chain's result stands: noise, server optimizers, MX8 replies, range shards,
+ *                 range pieces and fa_reduce_parts follow unchanged.  Only on an FA_FEDAVG part; a member of the
+ *                 measure-then-select family: not with the clip, Krum, DnC, geomed, secagg, sign, sparse-sum, MX8-sum or
+ *                 low-rank-sum stage, and not with any of the four receipt formats (those setters refuse a rot1-sum part
+ *                 in turn).  Not on an FA_SHARD_CLIENT_RS context, not as a context default.  A dense fa_submit to such a
+ *                 part is FA_ERR_STATE.  Setting the stage on a part drops what the round had received so far.  Shards
+ *                 and pieces are cut at multiples of 64, not 4096: as in fa_rot1_expand_device a block that a range holds
+ *                 part of is reduced whole and stored only inside the range.  A block's arithmetic never depends on the
+ *                 range: the same bits for any GPU count, pieces, pointer phase or kernel form.
+ *              8. Identities.  There is NO bit identity with the expanded route in general: that route rounds v * scale
+ *                 once per owner, this one rounds inside the transform.  There is one wherever every partial sum is exact
+ *                 in fp32: one owner, w = 1 and a scale of at most 12 significant bits give fl32(+0 + d_i) with d_i
+ *                 fa_rot1_decode's value -- its bits, except that rule 5 starts from +0, so the decoder's -0 comes out
+ *                 +0.  The error against the exact sum is bounded in DESIGN.md 8s.
+ *              Memory: per GPU and client slot one shadow in the rot1 shadow layout (516 bytes per block its range touches,
+ *              rounded up to 256), allocated at the part's first fa_submit_rot1_sum.  The part's dense slots are neither
+ *              read nor written by such a round; they stay allocated.
+ *              Added without a new FA_ABI_VERSION: fa_rot1_sum_device with cnt == 0 touches no device and answers FA_OK --
+ *              that is how a caller probes for it.
  *   FA_F16     IEEE binary16 bits.  The fp32 result is rounded once to
  *              binary16, round-to-nearest-even: values that round beyond 65504
  *              become +-inf, results below 2^-14 become fp16 subnormals (never
@@ -1470,6 +1519,45 @@ int fa_set_rot1(fa_ctx* ctx, int part_id, int on);
 #define FA_ROT1_ABSOLUTE 0x2
 int fa_submit_rot1(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* bits, const float* scale, uint64_t seed,
                    float weight, int flags);
+
+/* Rot1-sum stage (the header comment, "Rot1-sum stage"): rot1 receipts reduced in the rotated domain, without expanding
+ * them. */
+#define FA_ROT1_SUM_MAX_CLIENTS 128
+/* Rules 0-6 on the host, usable without a device: out[i] (fp32, cnt elements) is the aggregate of bucket element idx0 + i
+ * from the receipts (bits[c], scale[c], seed[c]) under w[c], c < D, and ref (fp32, cnt elements, NULL = absolute mode).
+ * bits[c] and scale[c] start at block idx0 >> 12 and cover the range.  FA_ERR_ARG as fa_rot1_sum_device. */
+int fa_rot1_sum_host(const uint32_t* const* bits, const float* const* scale, const uint64_t* seed, const float* w, int D,
+                     uint64_t idx0, size_t cnt, const float* ref, float* out);
+/* Rules 0-6 on raw device pointers, on device `gpu`, over bucket elements idx0 .. idx0 + cnt - 1 with any idx0: d_out[i]
+ * (cnt of out_dtype, one rounding) from d_ref (cnt of ref_dtype, NULL = absolute mode) and the receipts: d_bits[c] and
+ * d_scale[c] are device memory, start at block idx0 >> 12 and cover the range (128 words and one scale per block); a
+ * block that the range holds part of is reduced whole and stored only inside the range, every store checked against
+ * it.  The arrays d_bits, d_scale, seed and w themselves are host memory and are read before the call returns.  ctx may
+ * be NULL (then `gpu` is the HIP device).  Every argument is checked before any device call: the dtypes and their pair
+ * (bf16 <-> f16: FA_ERR_ARG), 1 <= D <= FA_ROT1_SUM_MAX_CLIENTS, idx0 + cnt < 2^64, and for cnt > 0 null pointers, alignment
+ * (FA_ERR_ALIGN: every d_bits[c] and d_scale[c] 4 bytes, d_ref and d_out their element) and that d_out does not overlap
+ * d_ref (FA_ERR_ARG); with cnt == 0 and valid arguments it returns FA_OK without touching a device.  Any element phase of
+ * d_ref and d_out is correct; a lane moves its 16 consecutive elements in 16-byte accesses where both are 16-byte aligned
+ * at the bucket's multiples of 16, and the bits do not depend on it.  One launch, a workgroup per block.  Async on
+ * hip_stream (NULL = the ctx's compute stream of `gpu`, or the null stream). */
+int fa_rot1_sum_device(fa_ctx* ctx, int gpu, const uint32_t* const* d_bits, const float* const* d_scale, const uint64_t* seed,
+                       const float* w, int D, uint64_t idx0, size_t cnt, const void* d_ref, fa_dtype ref_dtype, void* d_out,
+                       fa_dtype out_dtype, void* hip_stream);
+/* Gives a part the stage (part_id >= 0, on != 0): its rounds take rot1 receipts with fa_submit_rot1_sum and reduce them by
+ * rules 0-6 against the part's last output; the round under way is dropped.  Again on a part that has it: nothing.  on == 0
+ * removes the stage and frees what it allocated.  FA_ERR_ARG, naming the cause: D > FA_ROT1_SUM_MAX_CLIENTS, part_id < 0 (no
+ * context default), a part whose mode is not FA_FEDAVG, a part with a clip, Krum, DnC, geomed, secagg, sign, sparse-sum,
+ * MX8-sum, low-rank-sum or receipt stage (those setters refuse a rot1-sum part in turn), an FA_SHARD_CLIENT_RS context.
+ * In DESIGN.md 8s the stage takes 0.132 / 0.058 / 0.048 of the expanded route's device time with one seed and 0.42 / 0.41 /
+ * 0.41 with a seed per owner (D = 8 / 32 / 64, n = 64 Mi fp32): it lost nowhere, but a seed per owner costs one transform
+ * per owner and block, about 8 times a round with one seed at D = 64. */
+int fa_set_rot1_sum(fa_ctx* ctx, int part_id, int on);
+/* The rot1 receipt of client `client_slot`: bits (fa_rot1_words(n) words), scale (fa_rot1_blocks(n) values) and the seed
+ * of the whole bucket, under `weight` (rule 7).  flags: FA_HOST_PINNED as for fa_submit_rot1.  Per GPU enqueues the H2D of
+ * the words and scales of the blocks its range touches into the slot's shadow (the rot1 shadow layout, allocated at the
+ * part's first submit); the slot then counts as submitted.  FA_ERR_STATE on a part without fa_set_rot1_sum. */
+int fa_submit_rot1_sum(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* bits, const float* scale, uint64_t seed,
+                       float weight, int flags);
 
 /* Secagg stage (the header comment, "Secagg stage"): masked uint32 sums unmasked and decoded on the GPU. */
 #define FA_SECAGG_MAX_TERMS 4096

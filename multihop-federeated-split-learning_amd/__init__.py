@@ -188,6 +188,10 @@ def lib():
         "fa_lowrank_sum_device": (I, [P, I, P, S, P, P, P, I, U64, S, P, I, P, I, P]),
         "fa_set_lowrank_sum": (I, [P, I, P, S, I]),
         "fa_submit_lowrank_sum": (I, [P, I, I, P, S, I, F, I]),
+        "fa_rot1_sum_host": (I, [P, P, P, P, I, U64, S, P, P]),
+        "fa_rot1_sum_device": (I, [P, I, P, P, P, P, I, U64, S, P, I, P, I, P]),
+        "fa_set_rot1_sum": (I, [P, I, I]),
+        "fa_submit_rot1_sum": (I, [P, I, I, P, P, U64, F, I]),
         "fa_diag_secagg_unmask": (I, [P, I, P, I, S, U64, I, P, P, P, F, P, I, I, P]),  # diagnostic (outside fa.h)
         "fa_submit": (I, [P, I, I, P, F]),
         "fa_submit_pinned": (I, [P, I, I, P, F]),
@@ -745,6 +749,53 @@ def lowrank_expand_device(plan, f, r, cnt, dst, dst_dtype=F32, ref=None, ref_dty
 
 
 LOWRANK_SUM_MAX_CLIENTS = 128  # FA_LOWRANK_SUM_MAX_CLIENTS
+
+
+ROT1_SUM_MAX_CLIENTS = 128  # FA_ROT1_SUM_MAX_CLIENTS
+ROT1_SUM_DEPTH = 8  # the owners whose half-words a lane keeps in flight
+
+
+def _rot1_sum_args(bits, scale, seed, weights):
+    """The pointer arrays, the seeds (one per owner, or one for all) and the weights of D receipts (bits[c], scale[c]).
+    Returns ctypes and numpy arrays, which the caller keeps until the call returns."""
+    D = len(bits)
+    if len(scale) != D:
+        raise ValueError("need one scale per bits")
+    sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, np.uint64).reshape(-1), (D,)) if np.size(seed) == 1
+                              else np.asarray(seed, np.uint64).reshape(-1))
+    w = np.ascontiguousarray(np.ones(D) if weights is None else weights, np.float32).reshape(-1)
+    if w.size != D or sd.size != D:
+        raise ValueError("need one weight and one seed per client")
+    pb = (ctypes.c_void_p * max(1, D))(*[_addr(x) for x in bits])
+    ps = (ctypes.c_void_p * max(1, D))(*[_addr(x) for x in scale])
+    return pb, ps, sd, w, D
+
+
+def rot1_sum_host(bits, scale, seed, n, weights=None, ref=None, idx0=0):
+    """fa_rot1_sum_host (host arithmetic, fa.h "Rot1-sum stage" rules 0-6): the fp32 aggregate of bucket elements idx0 ..
+    idx0 + n - 1 from the receipts (bits[c] uint32, scale[c] float32, both from block idx0 >> 12 on; seed: one per owner
+    or one for all) under `weights` (None: ones) and ref (fp32[n], None: absolute mode)."""
+    bits = [np.ascontiguousarray(np.asarray(x, np.uint32).reshape(-1)) for x in bits]
+    scale = [np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1)) for x in scale]
+    nb = ((int(idx0) + n - 1) >> 12) - (int(idx0) >> 12) + 1 if n else 0
+    if any(x.size < nb * 128 for x in bits) or any(x.size < nb for x in scale):
+        raise ValueError("need %d words and %d scales per client" % (nb * 128, nb))
+    pb, ps, sd, w, D = _rot1_sum_args(bits, scale, seed, weights)
+    if ref is not None:
+        ref = np.ascontiguousarray(np.asarray(ref, np.float32).reshape(-1))
+    out = np.empty(n, np.float32)
+    check(lib().fa_rot1_sum_host(pb, ps, sd.ctypes.data, w.ctypes.data, D, int(idx0), n, _addr(ref), out.ctypes.data))
+    return out
+
+
+def rot1_sum_device(bits, scale, seed, n, out, out_dtype=F32, weights=None, ref=None, ref_dtype=F32, idx0=0, stream=None,
+                    gpu=0, ctx=None):
+    """fa_rot1_sum_device: out[i] = ref[i] + acc_i (ref None: acc_i) over n device-resident elements, bucket elements
+    idx0 .., from the D device-resident receipts (bits[c], scale[c]), bits / scale / idx0 as for rot1_expand_device, at any
+    element phase of ref and out.  Enqueued, not synchronized.  With n == 0 no device is touched: the feature probe."""
+    pb, ps, sd, w, D = _rot1_sum_args(bits, scale, seed, weights)
+    check(lib().fa_rot1_sum_device(ctx.handle if ctx is not None else None, gpu, pb, ps, sd.ctypes.data, w.ctypes.data, D,
+                                   int(idx0), n, _addr(ref), ref_dtype, _addr(out), out_dtype, _stream(stream)))
 
 
 def _lowrank_sum_args(f, r, weights):
@@ -1552,6 +1603,25 @@ class Aggregator:
             raise ValueError("need f float32")
         check(lib().fa_submit_lowrank_sum(self.handle, part, slot, f.ctypes.data, f.size, int(r), float(weight),
                                           HOST_PINNED if pinned else 0))
+
+    def set_rot1_sum(self, on=True, part_id=-1):
+        """fa_set_rot1_sum: the part's rounds take rot1 receipts (submit_rot1_sum) and reduce them in the rotated domain
+        without expanding them, one transform per block and seed; on=False removes the stage."""
+        check(lib().fa_set_rot1_sum(self.handle, part_id, 1 if on else 0))
+
+    def submit_rot1_sum(self, part, slot, bits, scale, seed, weight=1.0, pinned=False):
+        """fa_submit_rot1_sum: the client's update as (bits uint32[128 nb], scale float32[nb], seed), kept as it is until
+        the reducing call.  pinned: views of PinnedBuffers the caller keeps unchanged until the round is reduced."""
+        bits, scale = np.ascontiguousarray(bits), np.ascontiguousarray(scale)
+        if bits.dtype != np.uint32 or scale.dtype != np.float32:
+            raise ValueError("need bits uint32 and scale float32")
+        if part in self.parts:
+            nb = rot1_blocks(self.parts[part][0])
+            if bits.size != nb * 128 or scale.size != nb:
+                raise ValueError("bucket %d expects %d words and %d scales, got %d and %d"
+                                 % (part, nb * 128, nb, bits.size, scale.size))
+        check(lib().fa_submit_rot1_sum(self.handle, part, slot, bits.ctypes.data, scale.ctypes.data, int(seed), float(weight),
+                                       HOST_PINNED if pinned else 0))
 
     def set_rot1(self, on=True, part=None):
         """fa_set_rot1: the part takes rot1 receipts, on the stage and the reference of set_mx8 (part None: the default

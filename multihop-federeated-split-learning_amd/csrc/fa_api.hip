@@ -305,6 +305,7 @@ void set_range_runs(Part& p, int G) {
     p.sparse.ref = p.sparse.on();
     p.mx8sum.ref = p.mx8sum.on();
     p.lrsum.ref = p.lrsum.on();
+    p.rot1sum.ref = p.rot1sum.on();
     for (int g = 0; g < G; ++g) {
         p.runs[(size_t)g] = {Run{0, p.off[(size_t)g], p.cnt[(size_t)g]}};
         p.run_src[(size_t)g] = p.dout[(size_t)g];
@@ -798,6 +799,7 @@ int submit_impl(fa_ctx* ctx, int part_id, int slot, const Gather& src, float wei
     if (p->sparse.on()) return fail(FA_ERR_STATE, "part %d has a sparse-sum stage: it takes top-k receipts (fa_submit_sparse)", part_id);
     if (p->mx8sum.on()) return fail(FA_ERR_STATE, "part %d has an MX8-sum stage: it takes MX8 receipts (fa_submit_mx8_sum)", part_id);
     if (p->lrsum.on()) return fail(FA_ERR_STATE, "part %d has a low-rank-sum stage: it takes low-rank receipts (fa_submit_lowrank_sum)", part_id);
+    if (p->rot1sum.on()) return fail(FA_ERR_STATE, "part %d has a rot1-sum stage: it takes rot1 receipts (fa_submit_rot1_sum)", part_id);
     if ((rc = src.check("host source"))) return rc;
     const size_t si = dsize(p->in), total = src.total();
     if (total != p->n * si)
@@ -866,6 +868,7 @@ int piece_impl(fa_ctx* ctx, int part_id, int slot, size_t at, const void* src, s
     if (p->sparse.on()) return fail(FA_ERR_STATE, "part %d has a sparse-sum stage: it takes top-k receipts (fa_submit_sparse)", part_id);
     if (p->mx8sum.on()) return fail(FA_ERR_STATE, "part %d has an MX8-sum stage: it takes MX8 receipts (fa_submit_mx8_sum)", part_id);
     if (p->lrsum.on()) return fail(FA_ERR_STATE, "part %d has a low-rank-sum stage: it takes low-rank receipts (fa_submit_lowrank_sum)", part_id);
+    if (p->rot1sum.on()) return fail(FA_ERR_STATE, "part %d has a rot1-sum stage: it takes rot1 receipts (fa_submit_rot1_sum)", part_id);
     const size_t si = dsize(p->in);
     if (at > p->n * si || len > p->n * si - at)
         return fail(FA_ERR_ARG, "piece [%zu, %zu) outside part %d's %zu bytes", at, at + len, part_id, p->n * si);
@@ -1616,6 +1619,7 @@ int fa_submit_commit(fa_ctx* ctx, int part_id, int client_slot, float weight) {
     if (p->sparse.on()) return fail(FA_ERR_STATE, "part %d has a sparse-sum stage: it takes top-k receipts (fa_submit_sparse)", part_id);
     if (p->mx8sum.on()) return fail(FA_ERR_STATE, "part %d has an MX8-sum stage: it takes MX8 receipts (fa_submit_mx8_sum)", part_id);
     if (p->lrsum.on()) return fail(FA_ERR_STATE, "part %d has a low-rank-sum stage: it takes low-rank receipts (fa_submit_lowrank_sum)", part_id);
+    if (p->rot1sum.on()) return fail(FA_ERR_STATE, "part %d has a rot1-sum stage: it takes rot1 receipts (fa_submit_rot1_sum)", part_id);
     if (p->host_src[(size_t)client_slot].size()) {  // an earlier receipt kept in place would shadow the pieces
         p->host_src[(size_t)client_slot].clear();
         --p->n_host;

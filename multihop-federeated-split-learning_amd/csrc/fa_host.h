@@ -277,7 +277,8 @@ struct DevArrays {
 //   sign sparse      reset_round: the receipts go         the round stays    the round stays, the shadows go
 //   mx8 sum          reset_round: the receipts go         the round stays    the round stays, the shadows go
 //   lowrank sum      reset_round: the receipts go         as sparse          the round stays, the shadows go
-enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kSign, kSparse, kMx8Sum, kLowrankSum, kStages };
+//   rot1 sum         reset_round: the receipts go         the round stays    the round stays, the shadows go
+enum StageId { kOpt, kClip, kKrum, kGeomed, kBulyan, kNoise, kMx8, kReply, kSecagg, kDnc, kSign, kSparse, kMx8Sum, kLowrankSum, kRot1Sum, kStages };
 
 struct OptCfg : fa_server_opt {  // fa.h "Server optimizer"
     OptCfg(const fa_server_opt& o = fa_server_opt{FA_OPT_NONE, 0.0f, 0.0f, 0.0f, 0.0f}) : fa_server_opt(o) {}
@@ -354,6 +355,10 @@ struct LowrankSumCfg {  // fa.h "Low-rank-sum stage": the part's table and the r
     }
     bool on() const { return !mats.empty(); }
 };
+struct Rot1SumCfg {  // fa.h "Rot1-sum stage"
+    bool flag = false;
+    bool on() const { return flag; }
+};
 struct StageCfgs {
     OptCfg opt;
     ClipCfg clip;
@@ -369,6 +374,7 @@ struct StageCfgs {
     SparseCfg sparse;
     Mx8SumCfg mx8sum;
     LowrankSumCfg lrsum;
+    Rot1SumCfg rot1sum;
 };
 
 // Per GPU the fp32 state over its cnt elements (v only for the adaptive rules).
@@ -523,12 +529,24 @@ struct LowrankSumStage {
     std::vector<int> rank;
     bool on() const { return cfg.on(); }
 };
+// ref: the device output holds a reference, as Mx8Stage::ref.  buf: per GPU the shadows of its held slots in the rot1
+// shadow layout of Mx8Stage::rot, stride[g] bytes apart (the 128 words of each block its range touches, then from soff[g]
+// on their scales), allocated at the first fa_submit_rot1_sum; seed[slot]: the seed of the slot's last receipt.
+struct Rot1SumStage {
+    Rot1SumCfg cfg;
+    bool ref = false;
+    DevArrays buf;
+    std::vector<size_t> stride, soff;
+    std::vector<uint64_t> seed;
+    bool on() const { return cfg.on(); }
+};
 // The stages that are on in a StageCfgs or a Part, one bit per StageId.
 template <class S>
 inline unsigned stages_on(const S& s) {
     return s.opt.on() << kOpt | s.clip.on() << kClip | s.krum.on() << kKrum | s.geomed.on() << kGeomed |
            s.bulyan.on() << kBulyan | s.noise.on() << kNoise | s.mx8.on() << kMx8 | s.reply.on() << kReply | s.secagg.on() << kSecagg |
-           s.dnc.on() << kDnc | s.sign.on() << kSign | s.sparse.on() << kSparse | s.mx8sum.on() << kMx8Sum | s.lrsum.on() << kLowrankSum;
+           s.dnc.on() << kDnc | s.sign.on() << kSign | s.sparse.on() << kSparse | s.mx8sum.on() << kMx8Sum | s.lrsum.on() << kLowrankSum |
+           s.rot1sum.on() << kRot1Sum;
 }
 
 struct Part {
@@ -590,6 +608,7 @@ struct Part {
     SparseStage sparse;
     Mx8SumStage mx8sum;
     LowrankSumStage lrsum;
+    Rot1SumStage rot1sum;
     DevArrays oavg;
 };
 

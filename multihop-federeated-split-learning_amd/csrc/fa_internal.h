@@ -318,6 +318,22 @@ hipError_t launch_rot1_encode(const void* y, const void* sent, fa_dtype dt, int6
 // The codec on the host (fa_rot1_encode, fa_rot1_decode): plain loops over the rule.
 void rot1_encode_host(const float* delta, size_t n, uint64_t seed, uint32_t* bits, float* scale);
 void rot1_decode_host(const uint32_t* bits, const float* scale, uint64_t seed, uint64_t idx0, size_t cnt, float* d);
+// The rot1-sum stage (fa.h "Rot1-sum stage"), fa_rot1_sum.hip.  out[i] (dtype odt, one rounding) := fl32(widen(ref[i]) +
+// acc_i), or acc_i with ref null, over bucket elements [idx0, idx0 + cnt), any idx0, from the D receipts (bits[c], scale[c],
+// seed[c]) under w[c]; bits[c] (128 words per block) and scale[c] (one per block) start at block idx0 >> 12 (device memory;
+// the arrays bits, scale, seed and w are host memory); a block the range holds part of is reduced whole and every store
+// is checked against the range.  (rdt, odt) as dtype_pair_ok(in, out); out may be ref exactly (a lane reads its elements
+// before it writes them).  rot1_sum_vec (host-only): whether a lane's 16 elements move in 16-byte accesses.
+constexpr int kRot1SumDepth = 8;  // the owners whose half-words a lane keeps in flight
+bool rot1_sum_vec(uint64_t idx0, const void* ref, fa_dtype rdt, const void* out, fa_dtype odt);
+hipError_t launch_rot1_sum(const uint32_t* const* bits, const float* const* scale, const uint64_t* seed, const float* w, int D,
+                           uint64_t idx0, int64_t cnt, const void* ref, fa_dtype rdt, void* out, fa_dtype odt, const Tuning& tu,
+                           hipStream_t s);
+// Rule 0: order[k] is the owner at place k, first[k] whether place k starts a group.
+void rot1_sum_order(const uint64_t* seed, int D, int* order, uint8_t* first);
+// Rules 0-6 on the host (fa_rot1_sum_host): plain loops, block by block and group by group.
+void rot1_sum_host(const uint32_t* const* bits, const float* const* scale, const uint64_t* seed, const float* w, int D,
+                   uint64_t idx0, size_t cnt, const float* ref, float* out);
 // In-place state sync: every slot t.src[0..nc) := the chain over them (continuing `init` if given).
 hipError_t launch_sync(const ClientTable& t, int nc, fa_dtype dt, const float* init, const Split& sp,
                        const Tuning& tu, hipStream_t s);

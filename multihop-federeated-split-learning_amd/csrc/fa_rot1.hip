@@ -42,6 +42,7 @@
 #include "fa_internal.h"
 #include "fa_mx8.h"
 #include "fa_philox.h"
+#include "fa_rot1.h"
 
 #pragma clang fp contract(off)
 
@@ -49,10 +50,7 @@ namespace fa {
 
 namespace {
 
-constexpr int kRotThreads = 256, kRotLane = 16;
-static_assert(kRot1Block == kRotThreads * kRotLane, "an encoder lane owns 16 elements of its block");
 constexpr int64_t kRotMaxBlocks = 4096;  // workgroups per launch; blocks beyond it are strided
-constexpr uint32_t kRotStream = 0x524F5431u;  // counter word 3 of the diagonal: "ROT1"
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
@@ -62,18 +60,6 @@ __device__ __forceinline__ float rot1_sub(float y, float s) {
 #pragma clang fp contract(off)
     return y - s;
 }
-// Decode rule 3: D applied to fl(v * scale).
-__host__ __device__ __forceinline__ float rot1_delta(float v, float scale, uint32_t flip) {
-#pragma clang fp contract(off)
-    const float d = v * scale;
-    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, d) ^ (flip << 31));
-}
-
-// The sign words of Philox group j (elements 128 j .. 128 j + 127) under the seed's key.
-__host__ __device__ __forceinline__ void rot1_group(uint64_t j, uint32_t k0, uint32_t k1, uint32_t* r) {
-    philox4x32_10((uint32_t)j, (uint32_t)(j >> 32), 0u, kRotStream, k0, k1, r);
-}
-
 // ------------------------------------------------------------------ expansion
 
 template <typename T>
@@ -168,51 +154,6 @@ __global__ __launch_bounds__(kRotThreads) void rot1_expand_kernel(const uint32_t
 }
 
 // ------------------------------------------------------------------ encoder
-
-constexpr int kRotLds = kRot1Block + kRot1Block / 16;  // one pad word per 16
-__device__ __forceinline__ int rot_pad(int i) { return i + (i >> 4); }
-
-// The element of lane T's register e in the three layouts: the lane's own 16 elements; index bits 4 .. 7 in the
-// registers; index bits 8 .. 11 in the registers.
-enum { kLayOwn = 0, kLayMid = 1, kLayTop = 2 };
-template <int L>
-__device__ __forceinline__ int rot_elem(int T, int e) {
-    if constexpr (L == kLayOwn) return 16 * T + e;
-    else if constexpr (L == kLayMid) return 256 * (T >> 4) + 16 * e + (T & 15);
-    else return 256 * e + T;
-}
-template <int FROM, int TO>
-__device__ __forceinline__ void rot_exchange(float* z, float* lds) {
-    const int T = threadIdx.x;
-#pragma unroll
-    for (int e = 0; e < kRotLane; ++e) lds[rot_pad(rot_elem<FROM>(T, e))] = z[e];
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < kRotLane; ++e) z[e] = lds[rot_pad(rot_elem<TO>(T, e))];
-    __syncthreads();
-}
-// Four stages over the register index, in ascending h: the lower element a + b, the upper a - b.
-__device__ __forceinline__ void rot_stages(float* z) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int h = 1; h < kRotLane; h <<= 1)
-#pragma unroll
-        for (int e = 0; e < kRotLane; ++e)
-            if (!(e & h)) {
-                const float a = z[e], b = z[e + h];
-                z[e] = a + b;
-                z[e + h] = a - b;
-            }
-}
-// W over the workgroup's block: z in and out as the lane's own 16 elements, h = 1 .. 2048 in the rule's order.
-__device__ __forceinline__ void rot_transform(float* z, float* lds) {
-    rot_stages(z);
-    rot_exchange<kLayOwn, kLayMid>(z, lds);
-    rot_stages(z);
-    rot_exchange<kLayMid, kLayTop>(z, lds);
-    rot_stages(z);
-    rot_exchange<kLayTop, kLayOwn>(z, lds);
-}
 
 template <typename T>
 __global__ __launch_bounds__(kRotThreads) void rot1_encode_kernel(const void* y, const void* sent, int64_t n, int64_t nblk,
@@ -324,21 +265,6 @@ hipError_t launch_encode_t(const void* y, const void* sent, int64_t n, uint64_t 
     return hipGetLastError();
 }
 
-// The host's W and the signs of one block.
-void host_transform(float* z) {
-#pragma clang fp contract(off)
-    for (int h = 1; h < kRot1Block; h <<= 1)
-        for (int i = 0; i < kRot1Block; ++i)
-            if (!(i & h)) {
-                const float a = z[i], b = z[i + h];
-                z[i] = a + b;
-                z[i + h] = a - b;
-            }
-}
-void host_signs(uint64_t blk, uint64_t seed, uint32_t* sg) {
-    for (uint64_t g = 0; g < 32; ++g) rot1_group(blk * 32u + g, (uint32_t)seed, (uint32_t)(seed >> 32), sg + 4 * g);
-}
-
 }  // namespace
 
 hipError_t launch_rot1_expand(const uint32_t* bits, const float* scale, uint64_t seed, uint64_t idx0, int64_t cnt,
@@ -381,13 +307,13 @@ void rot1_encode_host(const float* delta, size_t n, uint64_t seed, uint32_t* bit
     std::vector<double> a(kRot1Block);
     uint32_t sg[kRot1Words];
     for (size_t b = 0; b * kRot1Block < n; ++b) {
-        host_signs(b, seed, sg);
+        rot1_host_signs(b, seed, sg);
         for (size_t i = 0; i < (size_t)kRot1Block; ++i) {
             const size_t e = b * kRot1Block + i;
             const uint32_t u = e < n ? __builtin_bit_cast(uint32_t, delta[e]) : 0u;
             z[i] = __builtin_bit_cast(float, u ^ ((sg[i >> 5] >> (i & 31) & 1u) << 31));
         }
-        host_transform(z.data());
+        rot1_host_transform(z.data());
         for (int i = 0; i < kRot1Block; ++i) a[(size_t)i] = (double)std::fabs(z[(size_t)i]);
         for (int h = 1; h < kRot1Block; h <<= 1)
             for (int i = 0; i < kRot1Block; i += 2 * h) a[(size_t)i] += a[(size_t)(i + h)];
@@ -406,9 +332,9 @@ void rot1_decode_host(const uint32_t* bits, const float* scale, uint64_t seed, u
     const uint64_t blk0 = idx0 >> 12, end = idx0 + cnt;
     for (uint64_t blk = blk0; blk * kRot1Block < end; ++blk) {
         const uint32_t* w = bits + (blk - blk0) * kRot1Words;
-        host_signs(blk, seed, sg);
+        rot1_host_signs(blk, seed, sg);
         for (int i = 0; i < kRot1Block; ++i) v[(size_t)i] = (w[i >> 5] >> (i & 31) & 1u) ? -1.0f : 1.0f;
-        host_transform(v.data());
+        rot1_host_transform(v.data());
         const uint64_t lo = std::max(idx0, blk * kRot1Block), hi = std::min(end, (blk + 1) * kRot1Block);
         for (uint64_t e = lo; e < hi; ++e) {
             const int i = (int)(e & 4095u);

@@ -555,6 +555,10 @@ void free_lrsum(fa_ctx* ctx, Part& p) {
     for (DevArrays* a : {&p.lrsum.plan, &p.lrsum.factors}) a->free(ctx->gpu);
     p.lrsum = LowrankSumStage{};
 }
+void free_rot1sum(fa_ctx* ctx, Part& p) {
+    p.rot1sum.buf.free(ctx->gpu);
+    p.rot1sum = Rot1SumStage{};
+}
 void free_stages(fa_ctx* ctx, Part& p) {
     p.noise = NoiseStage{};
     free_secagg(ctx, p);
@@ -562,6 +566,7 @@ void free_stages(fa_ctx* ctx, Part& p) {
     free_sparse(ctx, p);
     free_mx8sum(ctx, p);
     free_lrsum(ctx, p);
+    free_rot1sum(ctx, p);
     free_mx8(ctx, p);
     free_reply(ctx, p);
     free_opt(ctx, p);
@@ -1375,6 +1380,90 @@ int lowranksum_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, void* d
     return FA_OK;
 }
 
+// ------------------------------------------------------------------ rot1-sum stage
+
+int check_rot1sum_clients(int D) {
+    if (D < 1 || D > FA_ROT1_SUM_MAX_CLIENTS)
+        return fail(FA_ERR_ARG, "rot1 sum: D = %d clients outside 1 .. %d", D, FA_ROT1_SUM_MAX_CLIENTS);
+    return FA_OK;
+}
+
+inline size_t rot1_blocks(size_t off, size_t cnt);  // below, with the receipts
+void rot1_shadow_layout(const Part& p, int G, std::vector<size_t>* stride, std::vector<size_t>* soff);
+
+// The shadows of a part, allocated once: per GPU held x stride bytes in the rot1 shadow layout.  On failure the part
+// keeps the stage.
+int ensure_rot1sum_buf(fa_ctx* ctx, Part& p) {
+    Rot1SumStage& s = p.rot1sum;
+    if (s.buf) return FA_OK;
+    rot1_shadow_layout(p, ctx->G, &s.stride, &s.soff);
+    s.seed.assign((size_t)p.D, 0);
+    const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.stride[g]); };
+    const int g = s.buf.alloc(ctx->gpu, bytes);
+    if (g < 0) return FA_OK;
+    return fail(FA_ERR_NOMEM, "rot1 sum: shadow alloc of %zu B failed on GPU %zu", bytes((size_t)g), (size_t)g);
+}
+
+int submit_rot1_sum_impl(fa_ctx* ctx, int part_id, int slot, const uint32_t* bits, const float* scale, uint64_t seed,
+                         float weight, int flags) {
+    Trace tr("fa_submit_rot1_sum part %d slot %d", part_id, slot);
+    Part* p;
+    int rc = check_part(ctx, part_id, &p);
+    if (rc) return rc;
+    if (flags & ~FA_HOST_PINNED) return fail(FA_ERR_ARG, "rot1 sum: unknown flags 0x%x", flags);
+    if (slot < 0 || slot >= p->D) return fail(FA_ERR_ARG, "client slot %d out of range [0,%d)", slot, p->D);
+    if (!p->rot1sum.on()) return fail(FA_ERR_STATE, "rot1 sum: part %d has no rot1-sum stage (fa_set_rot1_sum)", part_id);
+    if (p->n > 0 && (!bits || !scale)) return fail(FA_ERR_ARG, "rot1 sum: %s is null", !bits ? "bits" : "scale");
+    if ((rc = ensure_rot1sum_buf(ctx, *p))) return rc;
+    const bool pinned = (flags & FA_HOST_PINNED) != 0;
+    rc = for_each_gpu(ctx->workers.get(), ctx->G, [&](int g) -> int {
+        GpuRes& r = ctx->gpu[(size_t)g];
+        DeviceGuard dg(r.dev);
+        const size_t off = p->off[(size_t)g], cnt = p->cnt[(size_t)g];
+        if (cnt == 0) return FA_OK;
+        // after the part's last reducing call: it read the shadow
+        if (hipStream_t ds = p->done_stream[(size_t)g]) {
+            FA_HIP(hipEventRecord(p->done[(size_t)g], ds));
+            FA_HIP(hipStreamWaitEvent(r.copy, p->done[(size_t)g], 0));
+        }
+        const size_t b0 = off >> 12, nb = rot1_blocks(off, cnt);
+        char* db = p->rot1sum.buf.at((size_t)g) + (size_t)(slot - p->c0[(size_t)g]) * p->rot1sum.stride[(size_t)g];
+        ++r.copy_gen;  // the next reducing call waits for the copy stream
+        int rc2 = mx8_h2d(r, db, reinterpret_cast<const char*>(bits + b0 * fa::kRot1Words), nb * fa::kRot1Words * 4, pinned);
+        if (!rc2) rc2 = mx8_h2d(r, db + p->rot1sum.soff[(size_t)g], reinterpret_cast<const char*>(scale + b0), nb * 4, pinned);
+        return rc2;
+    });
+    if (rc) return rc;
+    p->rot1sum.seed[(size_t)slot] = seed;
+    return mark_submitted(ctx, *p, slot, weight);
+}
+
+// Before the round's launches: the receipts are there.
+int rot1sum_round_begin(const Part& p) {
+    if (!p.rot1sum.buf) return fail(FA_ERR_STATE, "rot1 sum: part %d has no rot1 receipts (fa_submit_rot1_sum)", p.id);
+    return FA_OK;
+}
+
+// Rules 0-6 for piece j of GPU g (the current device), into dst (dtype odt): every client's words and scales from the
+// piece's first block on under w, the reference in the part's output (dst itself where the aggregate is reduced in place).
+int rot1sum_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, void* dst, fa_dtype odt, hipStream_t st) {
+    const Rot1SumStage& s = p.rot1sum;
+    const size_t off = p.off[(size_t)g], lo = piece_lo(p, g, j), cnt = piece_cnt(p, g, j);
+    if (cnt == 0) return FA_OK;
+    const size_t pb = ((off + lo) >> 12) - (off >> 12);  // the piece's first block among the GPU's
+    std::vector<const uint32_t*> bits((size_t)p.D);
+    std::vector<const float*> scale((size_t)p.D);
+    for (int c = 0; c < p.D; ++c) {
+        const char* base = s.buf.at((size_t)g) + (size_t)(c - p.c0[(size_t)g]) * s.stride[(size_t)g];
+        bits[(size_t)c] = reinterpret_cast<const uint32_t*>(base) + pb * fa::kRot1Words;
+        scale[(size_t)c] = reinterpret_cast<const float*>(base + s.soff[(size_t)g]) + pb;
+    }
+    const void* ref = s.ref ? static_cast<const char*>(p.dout[(size_t)g]) + lo * dsize(p.out) : nullptr;
+    FA_HIP(fa::launch_rot1_sum(bits.data(), scale.data(), s.seed.data(), w, p.D, (uint64_t)(off + lo), (int64_t)cnt, ref, p.out,
+                               dst, odt, ctx->tuning.tu, st));
+    return FA_OK;
+}
+
 // ------------------------------------------------------------------ one reducing call, as the stages see it
 
 int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, StageRound* rd) {
@@ -1405,6 +1494,7 @@ int stage_round_begin(fa_ctx* ctx, Part& p, const float* w, hipStream_t s, Stage
     if (p.sparse.on()) return sparse_round_begin(p);
     if (p.mx8sum.on()) return mx8sum_round_begin(p);
     if (p.lrsum.on()) return lowranksum_round_begin(p);
+    if (p.rot1sum.on()) return rot1sum_round_begin(p);
     return FA_OK;
 }
 
@@ -1436,6 +1526,8 @@ int stage_piece(fa_ctx* ctx, Part& p, int g, int j, const float* w, const StageR
         rc = mx8sum_piece(ctx, p, g, j, w, adst, adt, st);
     else if (p.lrsum.on())
         rc = lowranksum_piece(ctx, p, g, j, w, adst, adt, st);
+    else if (p.rot1sum.on())
+        rc = rot1sum_piece(ctx, p, g, j, w, adst, adt, st);
     else
         rc = reduce_on(ctx, g, tu, piece_ptrs(p, g, j, 0, p.D, ptrs), w, p.D, cnt, p.in, adst, adt, p.mode,
                        mode_arg(p.mode, p.divisor, p.trim, p.D), nullptr, st);
@@ -1785,8 +1877,25 @@ int set_part_lrsum(fa_ctx* ctx, Part& p, const LowrankSumCfg& c) {
     return FA_OK;
 }
 
+// fa_set_rot1_sum on a part (an FA_FEDAVG part of at most FA_ROT1_SUM_MAX_CLIENTS clients, not rs).  Off: the shadows go,
+// after the devices' pending work.  On a part that has the stage: nothing.  The first time: what the round received so
+// far is dropped: dense receipts are no rot1 receipts.
+int set_part_rot1sum(fa_ctx* ctx, Part& p, const Rot1SumCfg& c) {
+    if (p.rot1sum.on() == c.on()) return FA_OK;
+    if (!c.on()) {
+        if (int rc = wait_devices(ctx)) return rc;
+        free_rot1sum(ctx, p);
+        return FA_OK;
+    }
+    if (int rc = host_flush(ctx, p)) return rc;
+    reset_round(p);
+    p.rot1sum.cfg = c;
+    return FA_OK;
+}
+
 int set_part_stage(fa_ctx* ctx, Part& p, StageId id, const StageCfgs& c) {
     switch (id) {
+        case kRot1Sum: return set_part_rot1sum(ctx, p, c.rot1sum);
         case kLowrankSum: return set_part_lrsum(ctx, p, c.lrsum);
         case kMx8Sum: return set_part_mx8sum(ctx, p, c.mx8sum);
         case kSparse: return set_part_sparse(ctx, p, c.sparse);
@@ -1828,7 +1937,7 @@ const StageRule kRules[kStages] = {
     {"bulyan", "Bulyan", kTrim, false, 0, "the rule needs every client on one GPU; use FA_SHARD_RANGE",
      " (the stage replaces the window of an FA_TRIMMED part)"},
     {"noise", "noise", kAvg | kTrim, false, 0, "its aggregate is not bit-specified; use FA_SHARD_RANGE", ""},
-    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg | 1u << kSign | 1u << kSparse | 1u << kMx8Sum | 1u << kLowrankSum, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
+    {"mx8", "MX8", kAvg | kTrim, false, 1u << kSecagg | 1u << kSign | 1u << kSparse | 1u << kMx8Sum | 1u << kLowrankSum | 1u << kRot1Sum, "a GPU holding a whole slot does not hold the matching output; use FA_SHARD_RANGE", ""},
     {"mx8 reply", "reply", kAvg | kTrim, false, 0, "use FA_SHARD_RANGE", ""},
     {"secagg", "secagg", kAvg, true, 1u << kMx8, "its sum is taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage unmasks the sum of an FA_FEDAVG part)"},
@@ -1841,6 +1950,8 @@ const StageRule kRules[kStages] = {
     {"mx8 sum", "MX8-sum", kAvg, true, 1u << kMx8, "its sums are taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage sums the updates of an FA_FEDAVG part)"},
     {"lowrank sum", "low-rank-sum", kAvg, true, 1u << kMx8, "its sums are taken over every client of an element; use FA_SHARD_RANGE",
+     " (the stage sums the updates of an FA_FEDAVG part)"},
+    {"rot1 sum", "rot1-sum", kAvg, true, 1u << kMx8, "its sums are taken over every client of an element; use FA_SHARD_RANGE",
      " (the stage sums the updates of an FA_FEDAVG part)"},
 };
 
@@ -1887,6 +1998,7 @@ int check_for_clients(StageId id, int D, StageCfgs& c) {
     if (id == kSparse) return check_sparse_clients(D);
     if (id == kMx8Sum) return check_mx8sum_clients(D);
     if (id == kLowrankSum) return check_lrsum_clients(D);
+    if (id == kRot1Sum) return check_rot1sum_clients(D);
     return id == kBulyan ? check_bulyan(D, c.bulyan.f) : FA_OK;
 }
 
@@ -2161,18 +2273,24 @@ int submit_lowrank_impl(fa_ctx* ctx, int part_id, int slot, const float* f, size
 // The blocks of 4096 elements GPU g's range [off, off + cnt) touches: off >> 12 .. (off + cnt - 1) >> 12.
 inline size_t rot1_blocks(size_t off, size_t cnt) { return cnt ? ((off + cnt - 1) >> 12) - (off >> 12) + 1 : 0; }
 
-// The rot1 shadows of a part, allocated once: per GPU held x rstride bytes, a shadow the words of the blocks the GPU's
-// range touches followed by their scales.  On failure the part keeps the stage.
+// The rot1 shadow layout, per GPU (the rot1 receipts' and the rot1-sum stage's): the words of the blocks the GPU's range
+// touches, then from soff on their scales, 516 bytes per block; the stride between slots rounded up to 256.
+void rot1_shadow_layout(const Part& p, int G, std::vector<size_t>* stride, std::vector<size_t>* soff) {
+    stride->clear();
+    soff->clear();
+    for (size_t g = 0; g < (size_t)G; ++g) {
+        const size_t nb = rot1_blocks(p.off[g], p.cnt[g]);
+        soff->push_back(nb * fa::kRot1Words * 4);
+        stride->push_back((nb * (fa::kRot1Words + 1) * 4 + 255) / 256 * 256);
+    }
+}
+
+// The rot1 shadows of a part, allocated once: per GPU held x rstride bytes in the rot1 shadow layout.  On failure the
+// part keeps the stage.
 int ensure_rot1_buf(fa_ctx* ctx, Part& p) {
     Mx8Stage& s = p.mx8;
     if (s.rot) return FA_OK;
-    s.rsoff.clear();
-    s.rstride.clear();
-    for (size_t g = 0; g < (size_t)ctx->G; ++g) {
-        const size_t nb = rot1_blocks(p.off[g], p.cnt[g]);
-        s.rsoff.push_back(nb * fa::kRot1Words * 4);
-        s.rstride.push_back((nb * (fa::kRot1Words + 1) * 4 + 255) / 256 * 256);
-    }
+    rot1_shadow_layout(p, ctx->G, &s.rstride, &s.rsoff);
     const auto bytes = [&](size_t g) { return std::max<size_t>(256, (size_t)(p.c1[g] - p.c0[g]) * s.rstride[g]); };
     const int g = s.rot.alloc(ctx->gpu, bytes);
     if (g < 0) return FA_OK;
@@ -3008,6 +3126,24 @@ int fa_submit_lowrank_sum(fa_ctx* ctx, int part_id, int client_slot, const float
     return submit_lowrank_sum_impl(ctx, part_id, client_slot, f, len, r, weight, flags);
 }
 
+int fa_set_rot1_sum(fa_ctx* ctx, int part_id, int on) {
+    g_err.clear();
+    StageCfgs c = requested(ctx);
+    c.rot1sum = Rot1SumCfg{};
+    if (on) {
+        if (ctx && part_id < 0)
+            return fail(FA_ERR_ARG, "rot1 sum: set on a part, not as a context default (a round's receipts belong to one part)");
+        c.rot1sum.flag = true;
+    }
+    return set_stage(ctx, part_id, kRot1Sum, c);
+}
+
+int fa_submit_rot1_sum(fa_ctx* ctx, int part_id, int client_slot, const uint32_t* bits, const float* scale, uint64_t seed,
+                       float weight, int flags) {
+    g_err.clear();
+    return submit_rot1_sum_impl(ctx, part_id, client_slot, bits, scale, seed, weight, flags);
+}
+
 size_t fa_mx8_scale_bytes(size_t n) { return n / FA_MX8_BLOCK + (n % FA_MX8_BLOCK ? 1 : 0); }
 
 int fa_mx8_encode(const float* delta, size_t n, int8_t* q, uint8_t* e) {
@@ -3118,10 +3254,10 @@ int fa_mx8_set_reference(fa_ctx* ctx, int part_id, const void* host_src) {
     g_err.clear();
     Part* p;
     if (int rc = check_part(ctx, part_id, &p)) return rc;
-    if (!p->mx8.on() && !p->reply.on() && !p->sign.on() && !p->sparse.on() && !p->mx8sum.on() && !p->lrsum.on())
+    if (!p->mx8.on() && !p->reply.on() && !p->sign.on() && !p->sparse.on() && !p->mx8sum.on() && !p->lrsum.on() && !p->rot1sum.on())
         return fail(FA_ERR_STATE, "mx8: part %d neither takes MX8 receipts (fa_set_mx8) nor sends MX8 replies "
                                   "(fa_set_mx8_reply), nor takes top-k (fa_set_topk), low-rank (fa_set_lowrank) or rot1 receipts (fa_set_rot1), "
-                                  "nor has a sign-vote (fa_set_sign), sparse-sum (fa_set_sparse_sum), MX8-sum (fa_set_mx8_sum) or low-rank-sum stage (fa_set_lowrank_sum)", part_id);
+                                  "nor has a sign-vote (fa_set_sign), sparse-sum (fa_set_sparse_sum), MX8-sum (fa_set_mx8_sum), low-rank-sum (fa_set_lowrank_sum) or rot1-sum stage (fa_set_rot1_sum)", part_id);
     if (!host_src && p->n) return fail(FA_ERR_ARG, "mx8: host_src is null");
     if (int rc = wait_devices(ctx)) return rc;  // the part's pending work, on whatever stream
     if (p->reply.on())
